@@ -22,6 +22,8 @@ every rank renumbers its own chains.  Genome pairs are independent units of the 
 collective on the data path.
 
 Prints ONE JSON line (< 4 KB) on rank 0; the full report (per-kernel tables, counts, every leg) goes to --detail.
+`--dump-outputs DIR` writes the headline flag set's answers of its last timed step as .npy files (dump_outputs), so that two
+builds can be compared answer for answer on the same inputs.
 """
 import argparse
 import ctypes as C
@@ -385,6 +387,9 @@ class Runner:
         ctx.profile_select(None)
         # pass C: no events at all -- what a caller gets
         plain, _ = timed(steps)
+        if keep_results:   # the answers of the last timed step (copied before the counting call below writes the same buffers)
+            kept = self.status[:self.n].clone(), self.chain[:self.n].clone()
+            torch.cuda.synchronize()
         self.step(ccfg, with_stats=True)  # untimed: counts for the report
         ctx.synchronize()
         s = self.stats
@@ -394,7 +399,7 @@ class Runner:
                "counts": {"in": s.n_in, "retained": s.n_retained, "swept": s.n_swept, "chains": s.n_chains,
                           "chains_kept": s.n_chains_kept, "out": s.n_out, "device_ms_last_step": s.device_ms}}
         if keep_results:
-            out["status"], out["chain"] = self.status[:self.n].clone(), self.chain[:self.n].clone()
+            out["status"], out["chain"] = kept
         return out
 
 
@@ -466,6 +471,33 @@ def roofline(pipeline, n, steps, t, wl="100m"):
 
 def kernels_table(t, steps):
     return {k: round(v[1] / steps, 4) for k, v in sorted(t["prof"].items(), key=lambda kv: -kv[1][1])}
+
+
+DUMP_RECORDS_MAX = 3_000_000   # --dump-outputs: 20 B per record (index, status, chain) -> at most 60 MB of .npy files
+DUMP_SEED = 7
+
+
+def dump_outputs(out_dir, status, chain, n):
+    """--dump-outputs: what swg_filter_device handed its caller in the last timed step, as .npy files two builds can be compared
+    with element by element.  index.npy (float64, ascending record indices), status.npy (float32, SWG_ST_* of those records,
+    0 = filtered out) and chain.npy (float64, N of ch:Z:chain_N, 0 = none).  Every record when there are at most
+    DUMP_RECORDS_MAX, else a fixed sample of that many (numpy PCG64, seed DUMP_SEED): the same records on every run of the
+    same arguments."""
+    import numpy as np
+    import torch
+    if n <= DUMP_RECORDS_MAX:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_RECORDS_MAX, replace=False, shuffle=False))
+    at = torch.from_numpy(idx).to(status.device)
+    arrays = {"index": idx.astype(np.float64),
+              "status": status[at].cpu().numpy().astype(np.float32),
+              "chain": chain[at].cpu().numpy().view(np.uint32).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "records": n, "dumped": int(len(idx)), "sampled": len(idx) < n, "seed": DUMP_SEED if len(idx) < n else None,
+            "files": {name: str(a.dtype) for name, a in arrays.items()}}
 
 
 # ---- configs[2]: S-big1 --------------------------------------------------------------------------------------------
@@ -864,7 +896,14 @@ def main():
                          "init_process_group -> barrier / MAX-over-ranks / the chain renumbering all_reduce; NOT a scaling number")
     ap.add_argument("--detail", default="", help="file for the full report (per-kernel tables, counts, every leg); "
                                                  "default gpurun_out/bench_detail.json.  stdout carries ONE line < 4 KB")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the headline flag set's answers of its last timed step (rank 0's record "
+                         "set) as DIR/{index,status,chain}.npy, float, at most 60 MB (a fixed sample of larger record sets)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.scaling == "strong":
+        ap.error("--dump-outputs needs --scaling weak (strong scaling keeps the answers spread over the ranks)")
 
     launched = "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -940,7 +979,14 @@ def main():
         torch.cuda.synchronize()
         run = Runner(torch, sw, _lib, ctx, device, dist, cols, n, G, coll_device)
         cpu_legs = world == 1 and args.cpu_sample > 0   # the CPU legs belong to the N=1 run
-        timed = {p: run.time(p, args.steps, args.warmup, keep_results=cpu_legs) for p in order}
+        dump = bool(args.dump_outputs) and rank == 0
+        timed = {p: run.time(p, args.steps, args.warmup, keep_results=cpu_legs or (dump and p == args.pipeline)) for p in order}
+        dumped = None
+        if dump:
+            t = timed[args.pipeline]
+            dumped = dump_outputs(os.path.abspath(args.dump_outputs), t["status"], t["chain"], n)
+            if not cpu_legs:
+                del t["status"], t["chain"]
 
         # Host buffers in and out (swg_filter), PCIe included.  N = 1: four legs.  N > 1: EVERY rank runs the headline flags'
         # leg on its own shard at the same time (barrier first), and the line carries the MAX over ranks -- the scaling curve
@@ -1047,6 +1093,7 @@ def main():
                 "pcie_inclusive": pcie,
                 "arena_bytes_per_mapping": {"capacity": ctx.memory_info()[0] / n, "peak_last_call": ctx.memory_info()[1] / n},
                 "kernels_ms_per_step": head["kernels_ms_per_step"],
+                "dump_outputs": dumped,
             }
         del run, cols
         if rank == 0 and world == 1:

@@ -1,5 +1,5 @@
 """bench.py's stdout line stays under 4 KB (the driver keeps an 8 KB tail; round 2's 20 KB line was cut and unparsable).
-CPU check: summary_line() over a committed full report of a 10^8-mapping run."""
+CPU checks: summary_line() over a committed full report of a 10^8-mapping run, and the files of --dump-outputs."""
 import importlib.util
 import json
 import os
@@ -50,3 +50,35 @@ def test_line_degrades_instead_of_failing():
         assert k in out, k
     small = b.summary_line(full, None)
     assert "truncated" not in json.loads(b.fit_line(small))
+
+
+def test_dump_outputs_is_float_bounded_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: every record of a small record set; a fixed sample (the same indices on every call) of a large one, under
+    64 MB in all; float32 / float64 files holding the exact status and chain values (chain numbers are u32 in the ABI)."""
+    import numpy as np
+    import torch
+    b = _bench()
+    n = 1000
+    status = torch.arange(n, dtype=torch.int32).remainder(7).to(torch.uint8)
+    chain = torch.arange(n, dtype=torch.int32) * 3
+    chain[5] = -1   # 2^32 - 1 as the library's u32
+    d = b.dump_outputs(str(tmp_path / "small"), status, chain, n)
+    assert d["dumped"] == n and d["sampled"] is False
+    got = {k: np.load(tmp_path / "small" / f"{k}.npy") for k in ("index", "status", "chain")}
+    assert got["index"].dtype == np.float64 and got["status"].dtype == np.float32 and got["chain"].dtype == np.float64
+    assert np.array_equal(got["index"], np.arange(n)) and np.array_equal(got["status"], np.arange(n) % 7)
+    assert got["chain"][5] == 2**32 - 1 and np.array_equal(np.delete(got["chain"], 5), np.delete(np.arange(n) * 3, 5))
+
+    n = b.DUMP_RECORDS_MAX + 12_345
+    status = torch.arange(n, dtype=torch.int64).remainder(5).to(torch.uint8)
+    chain = torch.arange(n, dtype=torch.int32)
+    runs = []
+    for k in range(2):
+        d = b.dump_outputs(str(tmp_path / f"big{k}"), status, chain, n)
+        assert d["dumped"] == b.DUMP_RECORDS_MAX and d["sampled"] is True
+        files = [tmp_path / f"big{k}" / f"{x}.npy" for x in ("index", "status", "chain")]
+        assert sum(os.path.getsize(f) for f in files) < 64 << 20
+        runs.append([np.load(f) for f in files])
+    idx, st, ch = runs[0]
+    assert np.array_equal(idx, runs[1][0]) and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(st, idx % 5) and np.array_equal(ch, idx)

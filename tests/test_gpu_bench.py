@@ -167,6 +167,28 @@ def test_two_rank_launch_rehearsal():
     assert w["_line"]["pcie_default_ms"] == pytest.approx(pc["ms"], abs=0.01)
 
 
+def test_dump_outputs_are_the_timed_answers_and_repeatable(tmp_path):
+    """--dump-outputs: the headline flag set's status / chain of every record (the record set is under the sampling limit),
+    consistent with the run's counts, and identical between two runs that differ only in the number of steps (the inputs
+    do not depend on it); --steps is the number of timed steps the line reports."""
+    import numpy as np
+    common = ("--mappings", "300000", "--genomes", "21", "--only", "--cpu-sample", "0", "--no-pcie", "--e2e", "0", "--sbig1", "0",
+              "--shapes", "0")
+    runs = []
+    for k, steps in enumerate((2, 3)):
+        d = run_bench(*common, "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / f"d{k}"))
+        assert d["steps"] == steps and d["_line"]["steps"] == steps and d["ms_per_step"] > 0
+        assert d["dump_outputs"]["records"] == 300000 and d["dump_outputs"]["sampled"] is False
+        a = {x: np.load(tmp_path / f"d{k}" / f"{x}.npy") for x in ("index", "status", "chain")}
+        assert a["status"].dtype == np.float32 and a["chain"].dtype == np.float64 and a["index"].dtype == np.float64
+        assert np.array_equal(a["index"], np.arange(300000))
+        assert int((a["status"] != 0).sum()) == d["counts"]["out"] and 0 < d["counts"]["out"] < 300000
+        assert int(np.count_nonzero(a["chain"])) > 0   # default flags: scaffold chains are numbered
+        runs.append(a)
+    for x in ("status", "chain"):
+        assert np.array_equal(runs[0][x], runs[1][x]), x
+
+
 def test_smoke_entry():
     r = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.smoke(); print('smoke ok')"], capture_output=True,
                        text=True, cwd=ROOT, timeout=600)
