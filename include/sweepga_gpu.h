@@ -146,12 +146,21 @@ int swg_synchronize(swg_ctx* ctx);
  * results are copied back as soon as it is done (SWG_STREAM=0 switches that off; results are identical either way). */
 int swg_filter(swg_ctx* ctx, const swg_records* rec, const swg_config* cfg, uint8_t* status_out,
                uint32_t* chain_out, swg_stats* stats);
+/* Ranged filter (swg_filter, swg_filter64, swg_filter_device, swg_filter_device64, swg_filter_multi, swg_filter_multi64): any n,
+ * including n >= 2^31.  A record set of 2^31 records or more, or one whose one-piece footprint does not fit the memory limit
+ * (swg_set_memory_limit; no limit: the device's free memory), is cut into ranges of whole genome pairs (first two '#' parts)
+ * that each fit; results and chain numbers are those of one call.  Limits that stay: one genome pair of 2^31 records or more
+ * (SWG_ERR_RANGE); a kept-chain number of 2^32 or more (SWG_ERR_RANGE); a genome pair that alone does not fit the memory
+ * limit (SWG_ERR_OOM, the message names its size); more than 2^23 distinct genome pairs on the device path
+ * (SWG_ERR_UNSUPPORTED); the two genome-prefix rules partitioning the sequences differently (SWG_ERR_UNSUPPORTED).  Only when
+ * ranging is required.  Without a limit and below 2^31 records, swg_filter tries the streamed path first as before, and a call
+ * that fits the device in one piece runs exactly as before. */
 /* The ranges such a call would use (host code, no GPU): bounds_out[0 .. *n_chunks] are record indices, ranges of at least
  * target_records records cut where the query genome changes.  *n_chunks = 0: the records are not grouped by query genome
  * (or the reference's two genome-prefix rules partition the sequences differently) -- the call runs in one piece. */
 int swg_stream_plan(const swg_records* rec, uint64_t target_records, uint64_t* bounds_out, uint64_t bounds_capacity,
                     uint64_t* n_chunks);
-/* Same with every pointer of `rec`, status_out and chain_out in device memory of ctx's GPU.
+/* Same with every pointer of `rec`, status_out and chain_out in device memory of ctx's GPU (any n, see above).
  * Asynchronous on swg_stream(ctx) except for the small read-backs the pipeline needs. */
 int swg_filter_device(swg_ctx* ctx, const swg_records* rec, const swg_config* cfg,
                       uint8_t* status_out, uint32_t* chain_out, swg_stats* stats);
@@ -164,7 +173,7 @@ int swg_filter_device(swg_ctx* ctx, const swg_records* rec, const swg_config* cf
  * rebased per sweep segment instead -- query coordinates to the smallest one of their (query sequence, genome of the target)
  * segment, target coordinates likewise (src/paf_filter.rs:1037-1100: no step of apply_filters compares coordinates across
  * those segments) -- so that only the stretch touched by the mappings against ONE genome has to fit; beyond that
- * SWG_ERR_RANGE.  start <= end is assumed, as in any PAF.  swg_filter64: host pointers, rebased by host threads, then swg_filter (no extra PCIe bytes);
+ * SWG_ERR_RANGE.  start <= end is assumed, as in any PAF; any n (ranged as swg_filter).  swg_filter64: host pointers, rebased by host threads, then swg_filter (no extra PCIe bytes);
  * swg_filter_device64: device pointers, rebased by two kernels, then the same pipeline as swg_filter_device. */
 typedef struct swg_records64 {
   uint64_t n;
@@ -190,7 +199,8 @@ int swg_filter_device64(swg_ctx* ctx, const swg_records64* rec, const swg_config
                         uint32_t* chain_out, swg_stats* stats);
 
 /* ---- lower public seams of the reference, exercised by its tests ---------------------- */
-/* plane_sweep_query / plane_sweep_target / plane_sweep_both (src/plane_sweep_exact.rs:268,
+/* These lower seams keep the bound of fewer than 2^31 mappings / records per call, as does the ANI pre-pass below.
+ * plane_sweep_query / plane_sweep_target / plane_sweep_both (src/plane_sweep_exact.rs:268,
  * 355, 436) on ONE segment of n mappings given as host arrays.  axis: 0 query, 1 target,
  * 2 both.  keep_out[i] = 1 iff index i is in the returned Vec<usize>.  u64 coordinates as in
  * PlaneSweepMapping: values >= 2^32 are handled by shrinking the stretches no interval covers (exact for a
@@ -253,6 +263,13 @@ int swg_profile_units(swg_ctx* ctx, int i, uint64_t* units);
  * knows its sizes can avoid that by one warm-up call or by swg_reserve(). */
 int swg_memory_info(const swg_ctx* ctx, uint64_t* arena_capacity, uint64_t* arena_peak_last_call);
 int swg_reserve(swg_ctx* ctx, uint64_t arena_bytes);
+/* Device memory one filter call of this context may hold: scratch arena plus staged columns (not the caller's own device
+ * buffers).  0 (the default) = no limit beyond what the device has free.  Blocks the context holds beyond a new limit are
+ * released; the arena never grows past it.  The limit is a resource cap, not a path switch: a call whose one-piece footprint
+ * (from the per-record budgets) does not fit it -- or, without a limit, does not fit the device's free memory -- and every call
+ * of 2^31 records or more is filtered in ranges of whole genome pairs; every other call runs in one piece as before. */
+int swg_set_memory_limit(swg_ctx* ctx, uint64_t bytes);
+int swg_get_memory_limit(const swg_ctx* ctx, uint64_t* bytes);
 /* What a context's first swg_filter call would otherwise pay for inside the call (the reference has no counterpart: it has
  * no device): scratch and staging memory for about n_records_hint records (0 = none) and the library's code objects on the
  * device (one small built-in filter call).  Meant to run on its own host thread while the input is read and parsed. */
@@ -267,7 +284,8 @@ int swg_warmup(swg_ctx* ctx, uint64_t n_records_hint, uint32_t n_seq_hint, int w
  * made global again on the host (the reference numbers kept chains genome pair by genome pair in first-appearance
  * order, src/paf_filter.rs:517-521).  No collective.  Falls
  * back to ctxs[0] alone when the two genome-prefix rules of the reference partition the sequences differently.
- * Results are identical to swg_filter(ctxs[0], ...).  Errors are reported on ctxs[0]. */
+ * Results are identical to swg_filter(ctxs[0], ...).  Errors are reported on ctxs[0].  2^31 records or more, or more than a
+ * context's memory limit holds in one piece: ranges of whole genome pairs, dealt round-robin over the contexts. */
 int swg_filter_multi(swg_ctx* const* ctxs, int n_ctx, const swg_records* records, const swg_config* cfg, uint8_t* status_out,
                      uint32_t* chain_out, swg_stats* stats);
 int swg_filter_multi64(swg_ctx* const* ctxs, int n_ctx, const swg_records64* records, const swg_config* cfg, uint8_t* status_out,

@@ -13,6 +13,7 @@ K_INF = 2**64 - 1
 
 # every symbol include/sweepga_gpu.h declares
 SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "swg_stream", "swg_synchronize",
+           "swg_set_memory_limit", "swg_get_memory_limit",
            "swg_filter", "swg_filter_device", "swg_filter64", "swg_filter_device64", "swg_plane_sweep", "swg_plane_sweep_scaffolds",
            "swg_merge_chains", "swg_union_find_sets", "swg_log", "swg_log_range", "swg_profile_enable",
            "swg_profile_reset", "swg_profile_count", "swg_profile_get", "swg_profile_units", "swg_profile_select",
@@ -235,6 +236,10 @@ def load():
     lib.swg_paf_tree_filter.restype = C.c_int
     lib.swg_paf_tree_filter.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_uint64)]
+    lib.swg_set_memory_limit.restype = C.c_int
+    lib.swg_set_memory_limit.argtypes = [C.c_void_p, C.c_uint64]
+    lib.swg_get_memory_limit.restype = C.c_int
+    lib.swg_get_memory_limit.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.swg_free.restype = None
     lib.swg_free.argtypes = [C.c_void_p]
     _lib = lib
@@ -311,6 +316,16 @@ class Context:
         cap, peak = C.c_uint64(), C.c_uint64()
         self.check(self.lib.swg_memory_info(self.handle, C.byref(cap), C.byref(peak)))
         return cap.value, peak.value
+
+    def set_memory_limit(self, nbytes):
+        """Device bytes one filter call may hold (scratch arena + staged columns); 0 = no limit (the default).  A call that
+        does not fit in one piece -- and every call of 2^31 records or more -- is filtered in ranges of whole genome pairs."""
+        self.check(self.lib.swg_set_memory_limit(self.handle, C.c_uint64(int(nbytes))))
+
+    def memory_limit(self):
+        v = C.c_uint64()
+        self.check(self.lib.swg_get_memory_limit(self.handle, C.byref(v)))
+        return v.value
 
     def reserve(self, arena_bytes):
         self.check(self.lib.swg_reserve(self.handle, int(arena_bytes)))

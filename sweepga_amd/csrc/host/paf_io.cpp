@@ -601,7 +601,6 @@ int parse_text(swg_paf* p, int threads) {
     s.rec_base = n;
     n += s.recs;
   }
-  if (n >= (uint64_t(1) << 31)) return paf_error(SWG_ERR_RANGE, "more than 2^31-1 records");
   if (n != n_lines) {
     auto close_up = [&](auto& col) {
       for (auto& s : sl)
@@ -1280,7 +1279,6 @@ int swg_aln_open(const swg_aln_input* in, swg_aln** out) {
   if (n && (!in->query_name || !in->target_name || !in->query_start || !in->query_end || !in->target_start ||
             !in->target_end || !in->matches || !in->strand))
     return paf_error(SWG_ERR_INVALID, "swg_aln_open: a column is NULL");
-  if (n >= (uint64_t(1) << 31)) return paf_error(SWG_ERR_RANGE, "swg_aln_open: more than 2^31-1 alignments");
   swg_aln* a = nullptr;
   try {
     a = new swg_aln;

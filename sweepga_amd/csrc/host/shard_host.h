@@ -72,7 +72,8 @@ struct Column {
 
 struct Shard {
   uint64_t m = 0;
-  Column<uint32_t> idx, q_id, t_id, qs, qe, ts, te, matches, block, chain;
+  Column<uint64_t> idx;  // record indices, ascending
+  Column<uint32_t> q_id, t_id, qs, qe, ts, te, matches, block, chain;
   Column<double> identity;
   Column<uint8_t> strand, status;
   swg_stats stats{};
@@ -247,7 +248,7 @@ inline void scatter(const swg_records& r, const Plan& P, std::vector<Shard>* sha
       const int s = P.shard_of_pair[pair[i]];
       Shard& S = sh[s];
       const uint64_t k = pos[s]++;
-      S.idx.data()[k] = (uint32_t)i;
+      S.idx.data()[k] = i;
       S.q_id.data()[k] = r.q_id[i];
       S.t_id.data()[k] = r.t_id[i];
       S.qs.data()[k] = r.q_start[i];
@@ -285,7 +286,7 @@ inline void scatter_indices(const Plan& P, std::vector<Shard>* shards) {
     std::vector<uint64_t> pos(P.slice_off.begin() + (size_t)t * ns, P.slice_off.begin() + (size_t)(t + 1) * ns);
     for (uint64_t i = b; i < e; ++i) {
       const int s = P.shard_of_pair[pair[i]];
-      sh[s].idx.data()[pos[s]++] = (uint32_t)i;
+      sh[s].idx.data()[pos[s]++] = i;
     }
   });
 }
@@ -312,7 +313,7 @@ inline void merge(const Plan& P, const std::vector<Shard>& sh, uint8_t* status_o
     uint32_t* hi = hi_t[t].data();
     for (size_t k = (size_t)t; k < tasks.size(); k += (size_t)threads) {
       const Shard& S = sh[tasks[k].s];
-      const uint32_t* idx = S.idx.data();
+      const uint64_t* idx = S.idx.data();
       const uint32_t* ch = S.chain.data();
       for (uint64_t j = tasks[k].b; j < tasks[k].e; ++j) {
         const uint32_t c = ch[j];
@@ -342,11 +343,11 @@ inline void merge(const Plan& P, const std::vector<Shard>& sh, uint8_t* status_o
   run(threads, [&](int t) {
     for (size_t k = (size_t)t; k < tasks.size(); k += (size_t)threads) {
       const Shard& S = sh[tasks[k].s];
-      const uint32_t* idx = S.idx.data();
+      const uint64_t* idx = S.idx.data();
       const uint32_t* ch = S.chain.data();
       const uint8_t* st = S.status.data();
       for (uint64_t j = tasks[k].b; j < tasks[k].e; ++j) {
-        const uint32_t i = idx[j];
+        const uint64_t i = idx[j];
         status_out[i] = st[j];
         const uint32_t c = ch[j];
         chain_out[i] = c ? (uint32_t)((int64_t)c + shift[pair[i]]) : 0u;

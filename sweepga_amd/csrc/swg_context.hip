@@ -42,8 +42,17 @@ void swg_arena_reset(swg_ctx* ctx) {
   ctx->arena_overflow = false;
 }
 
+size_t swg_arena_budget(const swg_ctx* ctx) {
+  if (!ctx->mem_limit) return SIZE_MAX;
+  const uint64_t other = (uint64_t)ctx->io_cap + ctx->range_cap;
+  return other < ctx->mem_limit ? (size_t)(ctx->mem_limit - other) : 0;
+}
+
 int swg_arena_reserve(swg_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->arena_cap) return SWG_OK;
+  if (bytes > swg_arena_budget(ctx))
+    return swg_set_error(ctx, SWG_ERR_OOM, "a scratch arena of %zu bytes does not fit the memory limit of %llu bytes (%zu left beside "
+                         "the staging blocks)", bytes, (unsigned long long)ctx->mem_limit, swg_arena_budget(ctx));
   SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->arena) {
     SWG_HIP(ctx, hipFree(ctx->arena));
@@ -247,6 +256,7 @@ void swg_destroy(swg_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->io_block) (void)hipFree(ctx->io_block);
+  if (ctx->range_block) (void)hipFree(ctx->range_block);
   std::free(ctx->narrow_host);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
   if (ctx->ring) (void)hipHostFree(ctx->ring);
@@ -271,6 +281,28 @@ int swg_memory_info(const swg_ctx* ctx, uint64_t* arena_capacity, uint64_t* aren
   if (!ctx) return SWG_ERR_INVALID;
   if (arena_capacity) *arena_capacity = ctx->arena_cap;
   if (arena_peak_last_call) *arena_peak_last_call = ctx->arena_peak;
+  return SWG_OK;
+}
+int swg_set_memory_limit(swg_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return SWG_ERR_INVALID;
+  SWG_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->mem_limit = bytes;
+  if (bytes && (uint64_t)ctx->arena_cap + ctx->io_cap + ctx->range_cap > bytes) {
+    // what the context holds from earlier calls goes back: later calls size their blocks under the limit
+    SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->copy_stream) SWG_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    for (char** p : {&ctx->arena, &ctx->io_block, &ctx->range_block})
+      if (*p) {
+        SWG_HIP(ctx, hipFree(*p));
+        *p = nullptr;
+      }
+    ctx->arena_cap = ctx->io_cap = ctx->range_cap = 0;
+  }
+  return SWG_OK;
+}
+int swg_get_memory_limit(const swg_ctx* ctx, uint64_t* bytes) {
+  if (!ctx || !bytes) return SWG_ERR_INVALID;
+  *bytes = ctx->mem_limit;
   return SWG_OK;
 }
 int swg_reserve(swg_ctx* ctx, uint64_t arena_bytes) {

@@ -468,7 +468,6 @@ static int filter_device_body(swg_ctx* ctx, const swg_records* r, const swg_conf
 static int validate(swg_ctx* ctx, const swg_records* r, const swg_config* cfg) {
   if (!ctx) return SWG_ERR_INVALID;
   if (!r || !cfg) return swg_set_error(ctx, SWG_ERR_INVALID, "records/config is NULL");
-  if (r->n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "more than 2^31-1 records");
   // (identity may be NULL: then it is matches / max(block_len, 1), computed where it is read -- see swg_records)
   if (r->n && (!r->q_id || !r->t_id || !r->q_start || !r->q_end || !r->t_start || !r->t_end ||
                !r->matches || !r->block_len || !r->strand || !r->seq_genome_last || !r->seq_genome_two))
@@ -486,7 +485,7 @@ static int validate(swg_ctx* ctx, const swg_records* r, const swg_config* cfg) {
 // Scratch high-water marks measured on the 10^8 workload (round 3): 82 B/record for the sweep-only pipeline (32-byte record
 // slots, packed sort), 204-223 B/record with the scaffold stage.  Reserving that up front avoids the grow-and-rerun path on a
 // context's first call (and, for the streamed host path, any re-allocation between its ranges).
-int swg_filter_reserve_arena(swg_ctx* ctx, uint64_t n, const swg_records* rec, const swg_config* cfg, bool wide) {
+uint64_t swg_arena_estimate(uint64_t n, const swg_records* rec, const swg_config* cfg, bool wide) {
   // deep sequence pairs (the shape test of filter_device_body): the candidate arrays of the wavefront-per-element lists, 56 B per
   // record, come on top (the S-big1 profiles showed the first call of a fresh context running twice: 1.25 launches per call)
   const uint64_t pairs_ub = (uint64_t)rec->n_seq * rec->n_seq ? (uint64_t)rec->n_seq * rec->n_seq : 1;
@@ -499,6 +498,11 @@ int swg_filter_reserve_arena(swg_ctx* ctx, uint64_t n, const swg_records* rec, c
     for (const uint64_t g : {(uint64_t)rec->n_genome_last, (uint64_t)rec->n_genome_two})
       want += g * g <= (uint64_t(1) << 28) ? (size_t)(g * g) * sizeof(uint32_t) : (size_t)n * 4 * 12;
   }
+  return want;
+}
+int swg_filter_reserve_arena(swg_ctx* ctx, uint64_t n, const swg_records* rec, const swg_config* cfg, bool wide) {
+  size_t want = (size_t)swg_arena_estimate(n, rec, cfg, wide);
+  if (want > swg_arena_budget(ctx)) want = swg_arena_budget(ctx);  // (a hint: the run itself decides whether the limit suffices)
   if (ctx->arena_cap < want) {
     size_t free_b = 0, total_b = 0;
     const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
@@ -581,6 +585,25 @@ static int filter_device_any(swg_ctx* ctx, const swg_records* rec, const swg_rec
                              uint8_t* status_out, uint32_t* chain_out, swg_stats* stats) {
   if (rec->n && (!status_out || !chain_out)) return swg_set_error(ctx, SWG_ERR_INVALID, "output buffer is NULL");
   SWG_HIP(ctx, hipSetDevice(ctx->device));
+  {
+    // 2^31 records or more, or a one-piece footprint beyond the memory limit (no limit: beyond what the device has free): ranges
+    // of whole genome pairs (csrc/swg_range.hip).  Otherwise one piece, below.
+    bool ranged = false;
+    SWG_TRY(swg_device_needs_ranges(ctx, rec, cfg, rec64 != nullptr, &ranged));
+    if (ranged) {
+      SWG_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+      SWG_TRY(swg_filter_ranged_device(ctx, rec, rec64, cfg, status_out, chain_out, stats));
+      SWG_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+      if (stats) {
+        SWG_HIP(ctx, hipEventSynchronize(ctx->ev1));
+        float ms = 0.f;
+        SWG_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        stats->device_ms = ms;
+        stats->h2d_ms = stats->d2h_ms = 0.0;
+      }
+      return SWG_OK;
+    }
+  }
   SWG_TRY(swg_filter_reserve_arena(ctx, rec->n, rec, cfg, rec64 != nullptr));
   // sorts on truncated keys (swg_radix_drop_bits): a context that met runs too long for them stops trying -- for inputs of
   // about the size that failed (a host filtering the same kind of file again and again pays the failed attempt once)
@@ -588,60 +611,7 @@ static int filter_device_any(swg_ctx* ctx, const swg_records* rec, const swg_rec
   const int drop_level0 = ctx->sort_drop_level;
   const uint64_t readbacks0 = ctx->n_readbacks;
   SWG_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = swg_run_with_arena(ctx, [&]() -> int {
-    if (!rec64 || rec->n == 0) return filter_device_body(ctx, rec, cfg, status_out, chain_out, stats);
-    const uint64_t n = rec->n;
-    hipStream_t st = ctx->stream;
-    uint32_t* c[6];
-    for (auto& p : c) p = swg_alloc<uint32_t>(ctx, n);
-    unsigned long long* lo = swg_alloc<unsigned long long>(ctx, (size_t)rec->n_seq + 1);  // + the error word
-    SWG_CHECK_ARENA(ctx);
-    unsigned long long* bad = lo + rec->n_seq;
-    SWG_HIP(ctx, hipMemsetAsync(lo, 0xff, ((size_t)rec->n_seq + 1) * sizeof(unsigned long long), st));
-    SWG_LAUNCH(ctx, "seq_lo", seq_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
-                                                                   rec64->t_start, rec64->t_end, rec->n_seq, lo, bad));
-    SWG_LAUNCH(ctx, "rebase", rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
-                                                                   rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len,
-                                                                   rec->n_seq, lo, c[0], c[1], c[2], c[3], c[4], c[5], bad));
-    SWG_KERNEL_CHECK(ctx);
-    uint64_t hb;
-    SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad), &hb, 1));
-    if (hb != ~0ull && (hb & 7) < 4 && swg_rebase::axis_tables_fit(rec->n_seq, rec->n_genome_last)) {
-      // a sequence touched over 2^32 bases or more: the constants per sweep segment -- (sequence, genome of the other side) --
-      // instead (host/rebase.h, columns_by_axis)
-      const size_t cells = (size_t)rec->n_seq * rec->n_genome_last;
-      unsigned long long* lo2 = swg_alloc<unsigned long long>(ctx, 2 * cells + 1);
-      SWG_CHECK_ARENA(ctx);
-      unsigned long long* bad2 = lo2 + 2 * cells;
-      SWG_HIP(ctx, hipMemsetAsync(lo2, 0xff, (2 * cells + 1) * sizeof(unsigned long long), st));
-      SWG_LAUNCH(ctx, "axis_lo", axis_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end, rec64->t_start,
-                                                                     rec64->t_end, rec->seq_genome_last, rec->n_genome_last, lo2, lo2 + cells));
-      SWG_LAUNCH(ctx, "axis_rebase", axis_rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
-                                                                             rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len, rec->seq_genome_last,
-                                                                             rec->n_genome_last, lo2, lo2 + cells, c[0], c[1], c[2], c[3], bad2));
-      SWG_KERNEL_CHECK(ctx);
-      SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad2), &hb, 1));
-    }
-    if (hb != ~0ull) {
-      static const char* const F[8] = {"query_start", "query_end", "target_start", "target_end", "matches", "block_length", "?", "?"};
-      const int f = (int)(hb & 7);
-      if (f == 6)
-        return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: sequence id out of range", (unsigned long long)((hb >> 3) - 1));
-      return swg_set_error(ctx, SWG_ERR_RANGE,
-                           f >= 4 ? "record %llu: %s >= 2^32 is not supported"
-                                  : "record %llu: the stretch of its sequence that the mappings against one genome touch spans 2^32 bases or "
-                                    "more (%s): not supported by the 32-bit device layout",
-                           (unsigned long long)((hb >> 3) - 1), F[f]);
-    }
-    swg_records r32 = *rec;
-    r32.q_start = c[0];
-    r32.q_end = c[1];
-    r32.t_start = c[2];
-    r32.t_end = c[3];
-    r32.matches = c[4];
-    r32.block_len = c[5];
-    return filter_device_body(ctx, &r32, cfg, status_out, chain_out, stats);
-  });
+  int rc = swg_run_with_arena(ctx, [&]() -> int { return swg_filter_piece(ctx, rec, rec64, cfg, status_out, chain_out, stats); });
   if (rc != SWG_OK) return rc;
   if (ctx->sort_drop_level > drop_level0) ctx->sort_drop_n = rec->n;
   SWG_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -660,9 +630,67 @@ static int filter_device_any(swg_ctx* ctx, const swg_records* rec, const swg_rec
   return SWG_OK;
 }
 
+// One filter call over the whole of rec inside a fresh arena (the body swg_run_with_arena runs).  rec64 != NULL: the six 32-bit
+// columns are produced from rec64's by the rebasing kernels first.
+int swg_filter_piece(swg_ctx* ctx, const swg_records* rec, const swg_records64* rec64, const swg_config* cfg, uint8_t* status_out,
+                     uint32_t* chain_out, swg_stats* stats) {
+  if (!rec64 || rec->n == 0) return filter_device_body(ctx, rec, cfg, status_out, chain_out, stats);
+  const uint64_t n = rec->n;
+  hipStream_t st = ctx->stream;
+  uint32_t* c[6];
+  for (auto& p : c) p = swg_alloc<uint32_t>(ctx, n);
+  unsigned long long* lo = swg_alloc<unsigned long long>(ctx, (size_t)rec->n_seq + 1);  // + the error word
+  SWG_CHECK_ARENA(ctx);
+  unsigned long long* bad = lo + rec->n_seq;
+  SWG_HIP(ctx, hipMemsetAsync(lo, 0xff, ((size_t)rec->n_seq + 1) * sizeof(unsigned long long), st));
+  SWG_LAUNCH(ctx, "seq_lo", seq_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
+                                                                 rec64->t_start, rec64->t_end, rec->n_seq, lo, bad));
+  SWG_LAUNCH(ctx, "rebase", rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
+                                                                 rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len,
+                                                                 rec->n_seq, lo, c[0], c[1], c[2], c[3], c[4], c[5], bad));
+  SWG_KERNEL_CHECK(ctx);
+  uint64_t hb;
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad), &hb, 1));
+  if (hb != ~0ull && (hb & 7) < 4 && swg_rebase::axis_tables_fit(rec->n_seq, rec->n_genome_last)) {
+    // a sequence touched over 2^32 bases or more: the constants per sweep segment -- (sequence, genome of the other side) --
+    // instead (host/rebase.h, columns_by_axis)
+    const size_t cells = (size_t)rec->n_seq * rec->n_genome_last;
+    unsigned long long* lo2 = swg_alloc<unsigned long long>(ctx, 2 * cells + 1);
+    SWG_CHECK_ARENA(ctx);
+    unsigned long long* bad2 = lo2 + 2 * cells;
+    SWG_HIP(ctx, hipMemsetAsync(lo2, 0xff, (2 * cells + 1) * sizeof(unsigned long long), st));
+    SWG_LAUNCH(ctx, "axis_lo", axis_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end, rec64->t_start,
+                                                                   rec64->t_end, rec->seq_genome_last, rec->n_genome_last, lo2, lo2 + cells));
+    SWG_LAUNCH(ctx, "axis_rebase", axis_rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
+                                                                           rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len, rec->seq_genome_last,
+                                                                           rec->n_genome_last, lo2, lo2 + cells, c[0], c[1], c[2], c[3], bad2));
+    SWG_KERNEL_CHECK(ctx);
+    SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad2), &hb, 1));
+  }
+  if (hb != ~0ull) {
+    static const char* const F[8] = {"query_start", "query_end", "target_start", "target_end", "matches", "block_length", "?", "?"};
+    const int f = (int)(hb & 7);
+    if (f == 6)
+      return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: sequence id out of range", (unsigned long long)((hb >> 3) - 1));
+    return swg_set_error(ctx, SWG_ERR_RANGE,
+                         f >= 4 ? "record %llu: %s >= 2^32 is not supported"
+                                : "record %llu: the stretch of its sequence that the mappings against one genome touch spans 2^32 bases or "
+                                  "more (%s): not supported by the 32-bit device layout",
+                         (unsigned long long)((hb >> 3) - 1), F[f]);
+  }
+  swg_records r32 = *rec;
+  r32.q_start = c[0];
+  r32.q_end = c[1];
+  r32.t_start = c[2];
+  r32.t_end = c[3];
+  r32.matches = c[4];
+  r32.block_len = c[5];
+  return filter_device_body(ctx, &r32, cfg, status_out, chain_out, stats);
+}
+
 // bytes of the staging block swg_filter needs for n records over n_seq sequences (8 u32 columns + identity + strand +
 // status + chain + the two genome tables, every column rounded up to 256 bytes)
-static size_t io_block_bytes(uint64_t n, uint32_t n_seq) {
+size_t swg_io_block_bytes(uint64_t n, uint32_t n_seq) {
   const size_t col4 = ((n * 4 + 255) & ~size_t(255)), col8 = ((n * 8 + 255) & ~size_t(255)),
                col1 = ((n + 255) & ~size_t(255)), seqt = (((size_t)n_seq * 4 + 255) & ~size_t(255));
   return col4 * 8 + col8 + col1 * 2 + seqt * 2 + col4;
@@ -675,8 +703,20 @@ static int io_block_reserve(swg_ctx* ctx, size_t total) {
     ctx->io_block = nullptr;
     ctx->io_cap = 0;
   }
-  void* p = nullptr;
   size_t got = total + (total >> 3);  // a little headroom: the next file is rarely exactly this size
+  if (ctx->mem_limit) {  // under a limit: no headroom, and the arena of an earlier call makes room if it has to
+    got = total;
+    if ((uint64_t)total + ctx->range_cap > ctx->mem_limit)
+      return swg_set_error(ctx, SWG_ERR_OOM, "%zu bytes of record staging do not fit the memory limit of %llu bytes", total,
+                           (unsigned long long)ctx->mem_limit);
+    if ((uint64_t)total + ctx->range_cap + ctx->arena_cap > ctx->mem_limit && ctx->arena) {
+      SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      SWG_HIP(ctx, hipFree(ctx->arena));
+      ctx->arena = nullptr;
+      ctx->arena_cap = 0;
+    }
+  }
+  void* p = nullptr;
   hipError_t e = hipMalloc(&p, got);
   if (e != hipSuccess) {
     got = total;
@@ -689,7 +729,7 @@ static int io_block_reserve(swg_ctx* ctx, size_t total) {
   return SWG_OK;
 }
 
-int swg_io_block_reserve(swg_ctx* ctx, uint64_t n, uint32_t n_seq) { return io_block_reserve(ctx, io_block_bytes(n, n_seq)); }
+int swg_io_block_reserve(swg_ctx* ctx, uint64_t n, uint32_t n_seq) { return io_block_reserve(ctx, swg_io_block_bytes(n, n_seq)); }
 
 // Host buffers in / out: stage through device copies, then the device entry point.  The staging block lives in the
 // context (no allocation in steady state).  Only what the configuration reads crosses PCIe: `matches` and `strand` are
@@ -705,11 +745,23 @@ extern "C" int swg_filter(swg_ctx* ctx, const swg_records* rec, const swg_config
     return SWG_OK;
   }
   if (!status_out || !chain_out) return swg_set_error(ctx, SWG_ERR_INVALID, "output buffer is NULL");
+  swg_ctx* one[1] = {ctx};
+  // 2^31 records or more, or more than the memory limit holds in one piece: ranges of whole genome pairs (csrc/swg_range.hip).
+  // Without a limit and below 2^31 records the streamed path is tried first, as it always was: it needs scratch for one range
+  if (ctx->mem_limit || n > ((uint64_t(1) << 31) - 1)) {
+    bool ranged = false;
+    SWG_TRY(swg_host_needs_ranges(one, 1, rec, cfg, &ranged));
+    if (ranged) return swg_filter_ranged_host(one, 1, rec, cfg, status_out, chain_out, stats);
+  }
   {  // records grouped by query genome and enough of them: ranges uploaded while their predecessors are filtered
     int taken = 0;
-    swg_ctx* one[1] = {ctx};
     const int src = swg_stream_try(one, 1, rec, cfg, status_out, chain_out, stats, &taken);
     if (src != SWG_OK || taken) return src;
+  }
+  if (!ctx->mem_limit) {  // one piece that the device does not hold: ranges
+    bool ranged = false;
+    SWG_TRY(swg_host_needs_ranges(one, 1, rec, cfg, &ranged));
+    if (ranged) return swg_filter_ranged_host(one, 1, rec, cfg, status_out, chain_out, stats);
   }
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -717,7 +769,7 @@ extern "C" int swg_filter(swg_ctx* ctx, const swg_records* rec, const swg_config
   const bool derived_identity = rec->identity == nullptr;  // matches / max(block_len, 1), evaluated on the device
   const size_t col4 = ((n * 4 + 255) & ~size_t(255)), col8 = ((n * 8 + 255) & ~size_t(255)),
                col1 = ((n + 255) & ~size_t(255)), seqt = (((size_t)rec->n_seq * 4 + 255) & ~size_t(255));
-  SWG_TRY(io_block_reserve(ctx, io_block_bytes(n, rec->n_seq)));
+  SWG_TRY(io_block_reserve(ctx, swg_io_block_bytes(n, rec->n_seq)));
   char* blk = ctx->io_block;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -803,7 +855,7 @@ inline uint64_t ring_chunk() {  // SWG_RING_CHUNK (test knob): fewer records per
   return v;
 }
 }
-int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint32_t* idx, uint64_t m, const swg_config* cfg, uint8_t* status_sub,
+int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint64_t* idx, uint64_t m, const swg_config* cfg, uint8_t* status_sub,
                         uint32_t* chain_sub, swg_stats* stats, int threads) {
   SWG_TRY(validate(ctx, rec, cfg));
   if (m == 0) {
@@ -834,7 +886,7 @@ int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint32_t* id
   // the device block: swg_filter's layout
   const size_t col4 = ((m * 4 + 255) & ~size_t(255)), col8 = ((m * 8 + 255) & ~size_t(255)), col1 = ((m + 255) & ~size_t(255)),
                seqt = (((size_t)rec->n_seq * 4 + 255) & ~size_t(255));
-  SWG_TRY(io_block_reserve(ctx, io_block_bytes(m, rec->n_seq)));
+  SWG_TRY(io_block_reserve(ctx, swg_io_block_bytes(m, rec->n_seq)));
   char* blk = ctx->io_block;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -879,7 +931,7 @@ int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint32_t* id
       const int tt = (uint64_t)threads > cnt / 16384 + 1 ? (int)(cnt / 16384 + 1) : threads;
       swg_host::run(tt, [&](int t) {
         const uint64_t b = cnt * (uint64_t)t / tt, e = cnt * (uint64_t)(t + 1) / tt;
-        const uint32_t* ix = idx + c0;
+        const uint64_t* ix = idx + c0;
         for (int c = 0; c < 8; ++c) {
           if (!need[c]) continue;
           const uint32_t* src = static_cast<const uint32_t*>(h_col[c]);
@@ -1044,10 +1096,10 @@ extern "C" int swg_warmup(swg_ctx* ctx, uint64_t n_records_hint, uint32_t n_seq_
     const uint64_t scratch_records = n_records_hint >= (uint64_t(12) << 20) ? std::max<uint64_t>(n_records_hint / 6, uint64_t(6) << 20) : n_records_hint;
     size_t want = (size_t)scratch_records * (with_scaffold ? SWG_ARENA_B_SCAFFOLD : SWG_ARENA_B_SWEEP) + (size_t(8) << 20);
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + io_block_bytes(n_records_hint, n_seq_hint) > free_b / 2)
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + swg_io_block_bytes(n_records_hint, n_seq_hint) > free_b / 2)
       want = 0;  // not the kind of input to guess about: let the call size itself
     if (want && ctx->arena_cap < want) SWG_TRY(swg_arena_reserve(ctx, want));
-    if (want) SWG_TRY(io_block_reserve(ctx, io_block_bytes(n_records_hint, n_seq_hint ? n_seq_hint : 1)));
+    if (want) SWG_TRY(io_block_reserve(ctx, swg_io_block_bytes(n_records_hint, n_seq_hint ? n_seq_hint : 1)));
     lap("device memory reserved");
   }
   const uint32_t n = 2000;

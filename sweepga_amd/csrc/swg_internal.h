@@ -29,6 +29,11 @@ struct swg_ctx {
   char* ring = nullptr;
   size_t ring_slot_bytes = 0;
   hipEvent_t ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // device block of the ranged filter (csrc/swg_range.hip): per-pair plan arrays, a range's record indices and staged columns
+  char* range_block = nullptr;
+  size_t range_cap = 0;
+  // swg_set_memory_limit: bytes one filter call may hold on the device (arena + io_block + range_block), 0 = no limit
+  uint64_t mem_limit = 0;
   uint32_t* narrow_host = nullptr;  // swg_filter64: the rebased 32-bit columns (host side, malloc), released by swg_narrow_release
   size_t narrow_cap = 0;            //   in words
   // pinned host scratch for small read-backs
@@ -117,6 +122,8 @@ static inline T* swg_alloc(swg_ctx* ctx, size_t n) {
 }
 void swg_arena_reset(swg_ctx* ctx);
 int swg_arena_reserve(swg_ctx* ctx, size_t bytes);
+// What the memory limit leaves for the arena next to the context's other device blocks (SIZE_MAX without a limit).
+size_t swg_arena_budget(const swg_ctx* ctx);
 struct swg_arena_mark {
   size_t off;
 };
@@ -133,6 +140,18 @@ static inline int swg_run_with_arena(swg_ctx* ctx, F&& body) {
     // overflow: the body saw a nullptr and bailed out with SWG_ERR_OOM before using it
     size_t need = ctx->arena_peak + (ctx->arena_peak >> 1) + (size_t(1) << 20);
     if (need < 2 * ctx->arena_cap) need = 2 * ctx->arena_cap;
+    const size_t budget = swg_arena_budget(ctx);  // under a memory limit: grown up to it, never past it
+    if (ctx->arena_peak > budget)
+      return swg_set_error(ctx, SWG_ERR_OOM, "the call needs %zu bytes of scratch; the memory limit of %llu bytes leaves %zu",
+                           ctx->arena_peak, (unsigned long long)ctx->mem_limit, budget);
+    if (need > budget) need = budget;
+    if (!ctx->mem_limit && need > ctx->arena_peak) {  // no limit: a growth the device cannot hold shrinks to what it can
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const size_t room = free_b + ctx->arena_cap > (size_t(256) << 20) ? free_b + ctx->arena_cap - (size_t(256) << 20) : 0;
+        if (need > room && ctx->arena_peak <= room) need = room;
+      }
+    }
     int rc2 = swg_arena_reserve(ctx, need);
     if (rc2 != SWG_OK) return rc2;
   }
@@ -260,7 +279,7 @@ int swg_read_scalars(swg_ctx* ctx, const uint64_t* d_src, uint64_t* h_dst, int c
 // apply_filters over the records idx[0 .. m) (ascending) of the caller's host columns: gathered chunk by chunk into a pinned ring,
 // uploaded on the copy stream behind the gathering, filtered, results into status_sub / chain_sub [m] (swg_filter.hip; the shards
 // of swg_filter_multi when the input is not grouped by query genome)
-int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint32_t* idx, uint64_t m, const swg_config* cfg, uint8_t* status_sub,
+int swg_filter_gathered(swg_ctx* ctx, const swg_records* rec, const uint64_t* idx, uint64_t m, const swg_config* cfg, uint8_t* status_sub,
                         uint32_t* chain_sub, swg_stats* stats, int threads);
 
 static inline int swg_bits_for(uint64_t max_value) {  // bits needed to represent max_value

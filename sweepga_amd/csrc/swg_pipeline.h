@@ -24,6 +24,22 @@ int swg_stream_try(swg_ctx* const* ctxs, int n_ctx, const swg_records* r, const 
 // arena for a filter call over n records.
 int swg_io_block_reserve(swg_ctx* ctx, uint64_t n, uint32_t n_seq);
 int swg_filter_reserve_arena(swg_ctx* ctx, uint64_t n, const swg_records* rec, const swg_config* cfg, bool wide);
+// the scratch a one-piece filter call over n records is budgeted (swg_filter_reserve_arena's figure) and the staging block of
+// the host path for n records
+uint64_t swg_arena_estimate(uint64_t n, const swg_records* rec, const swg_config* cfg, bool wide);
+size_t swg_io_block_bytes(uint64_t n, uint32_t n_seq);
+// one filter call over the whole of rec in a fresh arena (rec64 != NULL: rebased from its 64-bit columns first)
+int swg_filter_piece(swg_ctx* ctx, const swg_records* rec, const swg_records64* rec64, const swg_config* cfg, uint8_t* status_out,
+                     uint32_t* chain_out, swg_stats* stats);
+
+// Ranged filter (csrc/swg_range.hip): record sets of 2^31 records or more, or beyond the memory limit, in ranges of whole genome
+// pairs.  *_needs_ranges: whether a call takes that path (the one-piece path otherwise, unchanged).
+int swg_device_needs_ranges(swg_ctx* ctx, const swg_records* rec, const swg_config* cfg, bool wide, bool* ranged);
+int swg_host_needs_ranges(swg_ctx* const* ctxs, int n_ctx, const swg_records* rec, const swg_config* cfg, bool* ranged);
+int swg_filter_ranged_device(swg_ctx* ctx, const swg_records* rec, const swg_records64* rec64, const swg_config* cfg,
+                             uint8_t* status_out, uint32_t* chain_out, swg_stats* stats);
+int swg_filter_ranged_host(swg_ctx* const* ctxs, int n_ctx, const swg_records* rec, const swg_config* cfg, uint8_t* status_out,
+                           uint32_t* chain_out, swg_stats* stats);
 
 // Scaffold stage (src/paf_filter.rs:436-747): chaining, span/identity filter, scaffold sweep,
 // anchors, inversion capture, rescue.  alive = step-1 survivors, keep1 = mapping-sweep survivors.

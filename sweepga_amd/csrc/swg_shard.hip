@@ -32,7 +32,6 @@ extern "C" int swg_filter_multi(swg_ctx* const* ctxs, int n_ctx, const swg_recor
   const uint64_t n = r->n;
   if (n_ctx == 1 || n == 0 || !r->seq_genome_last || !r->seq_genome_two || !same_partition(r))
     return swg_filter(ctx0, r, cfg, status_out, chain_out, stats);
-  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx0, SWG_ERR_RANGE, "more than 2^31-1 records");
   if (!r->q_id || !r->t_id || !r->q_start || !r->q_end || !r->t_start || !r->t_end || !r->matches || !r->block_len ||
       !r->strand || !status_out || !chain_out)   // (identity may be NULL: derived on the device, see swg_records)
     return swg_set_error(ctx0, SWG_ERR_INVALID, "a record column or an output buffer is NULL");
@@ -43,6 +42,11 @@ extern "C" int swg_filter_multi(swg_ctx* const* ctxs, int n_ctx, const swg_recor
     if (cfg->scoring_function < 0 || cfg->scoring_function > 4 || cfg->mapping_filter_mode < 0 || cfg->mapping_filter_mode > 2 ||
         cfg->scaffold_filter_mode < 0 || cfg->scaffold_filter_mode > 2)
       return swg_set_error(ctx0, SWG_ERR_INVALID, "bad scoring_function / filter mode");
+    // 2^31 records or more, or more than a context's memory limit holds in one piece: ranges of whole genome pairs, dealt
+    // round-robin over the contexts (csrc/swg_range.hip)
+    bool ranged = false;
+    SWG_TRY(swg_host_needs_ranges(ctxs, n_ctx, r, cfg, &ranged));
+    if (ranged) return swg_filter_ranged_host(ctxs, n_ctx, r, cfg, status_out, chain_out, stats);
     int taken = 0;
     const int rc = swg_stream_try(ctxs, n_ctx, r, cfg, status_out, chain_out, stats, &taken);
     if (rc != SWG_OK || taken) return rc;
