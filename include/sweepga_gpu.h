@@ -442,6 +442,52 @@ int swg_ani_median(swg_ctx* ctx, const swg_ani_input* in, const uint8_t* select,
 /* calculate_ani_stats over an open PAF (runs the ORTHOGONAL filter itself) */
 int swg_paf_ani_stats(swg_ctx* ctx, swg_paf* p, int kind, double percentile, int sort, int threads, double* ani50);
 
+/* ---- --joblist: haplotype pairs to align, chosen from MinHash sketches (src/mash.rs, src/knn_graph.rs, src/pansn.rs,
+ * src/joblist.rs, src/main.rs:791-990, 2711-2745) --------------------------------------------------------------------
+ * FASTA (host): records of every file in order; name = first whitespace token after '>'; sequence = its lines trimmed and
+ *   concatenated; lines before a file's first header are prepended to that file's first record (main.rs:963-990).
+ *   .gz / .bgz through the BGZF reader.  Errors: text in swg_fasta_last_error(). */
+typedef struct swg_fasta swg_fasta;
+int swg_fasta_open(const char* const* paths, int n_paths, int threads, swg_fasta** out);
+void swg_fasta_close(swg_fasta* f);
+uint64_t swg_fasta_num_records(const swg_fasta* f);
+const char* swg_fasta_name(const swg_fasta* f, uint64_t i);   /* owned by the handle */
+int swg_fasta_file_index(const swg_fasta* f, uint64_t i);      /* which of the paths record i came from */
+const uint64_t* swg_fasta_offsets(const swg_fasta* f);         /* [n + 1]: record i = bases[offsets[i], offsets[i + 1]) */
+const uint8_t* swg_fasta_bases(const swg_fasta* f);            /* every record's bytes, as read (case kept) */
+const char* swg_fasta_last_error(void);
+/* Per contig, the bottom-s MULTISET of min(SipHash-1-3(le64(k) || window), SipHash-1-3(le64(k) || revcomp upper-cased))
+ * over the windows of k bytes all in ACGTacgt, ascending (KmerSketch::from_sequence, mash.rs:78-131).  Contig i =
+ * seq[offsets[i], offsets[i + 1]); counts_out[n_seq]; minimizers_out[n_seq * s], row i holds counts_out[i] values.  The
+ * contigs stream through the device in fixed-size chunks (device memory does not grow with the input).  k in 1..64,
+ * s in 1..65536, else SWG_ERR_UNSUPPORTED.  timing_ms (optional, [5]): wall, H2D, hash, select (ms, device events), k-mers. */
+int swg_mash_sketch(swg_ctx* ctx, const uint8_t* seq, const uint64_t* offsets, uint64_t n_seq, int k, uint64_t s,
+                    uint64_t* counts_out, uint64_t* minimizers_out, double* timing_ms);
+/* merge_sketches (knn_graph.rs:568-582), host: the rows `members` of a [.. x stride] sketch table concatenated, sorted,
+ * deduplicated and truncated to s -> out[<= s], *out_count */
+int swg_mash_merge(const uint64_t* minimizers, const uint64_t* counts, uint64_t stride, const uint64_t* members,
+                   uint64_t n_members, uint64_t s, uint64_t* out, uint64_t* out_count);
+/* All-vs-all Mash distance (mash.rs:39-73) over n sketch rows (row i = sketches[i * stride ..], counts[i] ascending
+ * values, taken as SETS): dist_out[n * n] (diagonal 0.0), intersection / union sizes in the optional [n * n] outputs.
+ * ln is glibc's log, bit for bit.  n <= 65535. */
+int swg_mash_distances(swg_ctx* ctx, const uint64_t* sketches, const uint64_t* counts, uint64_t stride, uint64_t n, int k,
+                       double* dist_out, uint32_t* inter_out, uint32_t* union_out);
+/* generate_random_pairs (knn_graph.rs:362-386) for rows [row_begin, row_end): mask_out[(row_end - row_begin) * ceil(n / 64)],
+ * bit j of row i set when i < j and SipHash-1-3(le64(i) || le64(j)) <= (fraction * u64::MAX as f64) as u64. */
+int swg_mash_random_pairs(swg_ctx* ctx, uint64_t n, double fraction, uint64_t row_begin, uint64_t row_end, uint64_t* mask_out);
+/* Pair selection over n items (select_pairs_from_sketches, knn_graph.rs:498-560) for a --sparsify string; dist ([n * n])
+ * is needed by auto, giant:/connectivity: and tree:/knn:.  *pairs_out = 2 * *n_pairs values (i < j), sorted, released
+ * with swg_free().  ctx may be NULL when no random pairs are drawn (none, all, wfmash:). */
+int swg_select_pairs(swg_ctx* ctx, const char* strategy, const double* dist, uint64_t n, uint64_t** pairs_out, uint64_t* n_pairs);
+/* `sweepga --joblist` over PanSN FASTA (main.rs:848-960, 2711-2745; joblist.rs:124-145): one line per selected haplotype
+ * pair plus every haplotype's self pair, "wfmash -t T [-l L] -T A -Q B a.fa [b.fa] > DIR/A_vs_B.paf" with '#' etc. as
+ * '_' in the file name.  threads = T (the reference's default is 8); min_aln_length 0 omits -l; output_dir NULL = ".".
+ * Input without PanSN structure: SWG_ERR_UNSUPPORTED (the reference's per-file sweepga fallback is not emitted).
+ * *out_text is released with swg_free().  timing_ms (optional, [6]): read, sketch, merge, distances, select, total. */
+int swg_joblist(swg_ctx* ctx, const char* const* paths, int n_paths, const char* strategy, int k, uint64_t s, uint64_t threads,
+                uint64_t min_aln_length, const char* output_dir, int io_threads, char** out_text, uint64_t* out_len,
+                double* timing_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,10 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_paf_seq_offsets", "swg_aln_seq_offsets", "swg_paf_record_offsets", "swg_aln_record_offsets",
            "swg_paf_tree_filter", "swg_free", "swg_stream_plan", "swg_paf_identity_is_derived",
            "swg_alnstats_open", "swg_alnstats_open_buffer", "swg_alnstats_close", "swg_alnstats_get", "swg_alnstats_pair",
-           "swg_alnstats_report", "swg_alnstats_compare", "swg_alnstats_last_error"]
+           "swg_alnstats_report", "swg_alnstats_compare", "swg_alnstats_last_error",
+           "swg_fasta_open", "swg_fasta_close", "swg_fasta_num_records", "swg_fasta_name", "swg_fasta_file_index",
+           "swg_fasta_offsets", "swg_fasta_bases", "swg_fasta_last_error", "swg_mash_sketch", "swg_mash_merge",
+           "swg_mash_distances", "swg_mash_random_pairs", "swg_select_pairs", "swg_joblist"]
 
 
 class SwgError(RuntimeError):

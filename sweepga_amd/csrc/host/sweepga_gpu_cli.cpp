@@ -9,6 +9,8 @@
 //   name interning ............ src/sequence_index.rs:7-31 genome prefixes ... src/paf_filter.rs:1022-1030,
 //                                                          src/plane_sweep_scaffold.rs:13-22
 //   write_filtered_output ..... src/paf_filter.rs:1689-1726
+//   --joblist ................. src/main.rs:2711-2745 over FASTA input: one wfmash command per selected haplotype pair,
+//                               sketches / distances / random pairs on the GPU (swg_joblist)
 // Everything between "records parsed" and "per-record status + chain id" is one swg_filter() call.
 // There is no CPU filter in this binary: without a GPU it exits with the library's error.
 #include <unistd.h>
@@ -17,6 +19,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -192,6 +195,40 @@ int check_sparsify(const std::string& v, unsigned long* tree_near = nullptr, uns
   return 2;
 }
 
+// --joblist (src/main.rs:2711-2745): PanSN FASTA in, one `wfmash` command per selected haplotype pair out.  Every
+// --sparsify value is valid here.  The GPU is opened when there is one; strategies that need it (sketches, random pairs)
+// fail with the library's message without one.
+int run_joblist(const std::vector<std::string>& inputs, const std::string& sparsify, uint64_t k, uint64_t s, uint64_t wfmash_threads,
+                uint64_t min_aln_length, const std::string& dir, const std::string& output_file, int device) {
+  if (inputs.empty()) die(1, "--joblist requires FASTA input");
+  for (size_t i = 1; i <= dir.size(); ++i) {  // create_dir_all
+    if (i < dir.size() && dir[i] != '/') continue;
+    const std::string prefix = dir.substr(0, i);
+    struct stat sb;
+    if (stat(prefix.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode)) continue;
+    if (mkdir(prefix.c_str(), 0777) != 0 && errno != EEXIST) die(1, "Failed to create joblist output dir '" + dir + "': " + std::strerror(errno));
+  }
+  swg_ctx* ctx = nullptr;
+  if (swg_create(device, &ctx) != SWG_OK) ctx = nullptr;
+  std::vector<const char*> paths;
+  for (const auto& p : inputs) paths.push_back(p.c_str());
+  char* text = nullptr;
+  uint64_t len = 0;
+  // out-of-range values stay out of range through the narrowing; the library refuses them only where a sketch is drawn
+  const int kk = (int)std::min<uint64_t>(k, 1u << 30);
+  const int rc = swg_joblist(ctx, paths.data(), (int)paths.size(), sparsify.c_str(), kk, s, wfmash_threads, min_aln_length, dir.c_str(), 0,
+                             &text, &len, nullptr);
+  if (rc != SWG_OK) die(1, swg_last_error(ctx));
+  FILE* out = output_file.empty() ? stdout : std::fopen(output_file.c_str(), "wb");
+  if (!out) die(1, "cannot open " + output_file + ": " + std::strerror(errno));
+  if (len && std::fwrite(text, 1, len, out) != len) die(1, "write failed");
+  if (out != stdout) std::fclose(out);
+  swg_free(text);
+  std::fflush(stdout);
+  if (ctx) swg_destroy(ctx);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -204,7 +241,10 @@ int main(int argc, char** argv) {
   bool keep_self = false, no_filter = false, scaffolds_only = false, quiet = false;
   int device = 0, threads = 0;
   std::vector<int> devices;
-  std::string bad_sparsify, tree_sparsify;
+  std::string bad_sparsify, tree_sparsify, sparsify = "none", joblist_dir = ".";
+  std::vector<std::string> inputs;
+  bool joblist = false, threads_given = false;
+  uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
   for (int i = 1; i < argc; ++i) {
@@ -242,6 +282,7 @@ int main(int argc, char** argv) {
       if (rc == 2) die(2, "invalid value for --sparsify");
       if (rc == 1) bad_sparsify = v;  // reported after the --no-filter shortcut, as in main.rs:3461-3509
       tree_sparsify = rc == 3 ? v : std::string();
+      sparsify = v;
     }
     else if (a == "--device") { if (!parse_int(value(), &device) || device < 0) die(2, "invalid value for --device"); }
     else if (a == "--devices") {  // comma-separated: shard the genome pairs over several GPUs of the node
@@ -257,18 +298,32 @@ int main(int argc, char** argv) {
     }
     else if (a == "--quiet") quiet = true;
     else if (a == "--no-adaptive-scaffolds" || a == "--paf") { /* no effect for PAF input (main.rs:3515-3527) */ }
-    else if (a == "--threads" || a == "-t") { if (!parse_int(value(), &threads) || threads < 0) die(2, "invalid value for --threads"); }
+    else if (a == "--threads" || a == "-t") {
+      if (!parse_int(value(), &threads) || threads < 0) die(2, "invalid value for --threads");
+      threads_given = true;
+    }
+    else if (a == "--joblist") joblist = true;
+    else if (a == "--joblist-output-dir") joblist_dir = value();
+    else if (a == "--mash-kmer-size") { if (!parse_u64(value(), &mash_k)) die(2, "invalid value for --mash-kmer-size"); }
+    else if (a == "--mash-sketch-size") { if (!parse_u64(value(), &mash_s)) die(2, "invalid value for --mash-sketch-size"); }
     else if (a == "--help" || a == "-h") {
       std::puts("usage: sweepga-gpu <in.paf> [--output-file out.paf] [--num-mappings M] [--overlap F] [--scoring S]\n"
                 "         [--min-aln-identity I] [--min-aln-length N] [--self] [--no-filter] [--scaffold-jump N]\n"
                 "         [--scaffold-mass N] [--scaffold-filter M] [--scaffold-overlap F] [--scaffold-dist N]\n"
                 "         [--min-scaffold-identity I] [--scaffolds-only] [--ani-method M]\n"
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
+                "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
+                "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
-    else input = a;
+    else {
+      input = a;
+      inputs.push_back(a);
+    }
   }
+  if (joblist) return run_joblist(inputs, sparsify, mash_k, mash_s, threads_given ? (uint64_t)threads : 8, block_length, joblist_dir,
+                                  output_file, device);
   if (input.empty()) die(2, "usage: sweepga-gpu <in.paf> [--output-file out.paf] [filter flags]   (--help)");
 
   if (!no_filter && !bad_sparsify.empty()) die(1, "--sparsify '" + bad_sparsify + "' is not valid for post-alignment PAF/1aln filtering");
