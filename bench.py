@@ -21,6 +21,11 @@ rank filters its device-resident shard, kept-chain counts are exchanged (one all
 every rank renumbers its own chains.  Genome pairs are independent units of the filter, so there is no other
 collective on the data path.
 
+A plain run does only what the headline needs: it generates the record set, runs W warm-up steps and K steps with HIP events around
+every launch (which find the dominant kernel), times K steps of the headline flag set, writes --dump-outputs and prints its line.
+Everything else -- the other flag sets, S-big1, the CPU baselines and the parity against the oracle, the host-buffer (PCIe) legs,
+other record orders and shapes, the file-to-file leg, the pass without events and the counts -- runs under `--full` only.
+
 Prints ONE JSON line (< 4 KB) on rank 0; the full report (per-kernel tables, counts, every leg) goes to --detail.
 `--dump-outputs DIR` writes the headline flag set's answers of its last timed step as .npy files (dump_outputs), so that two
 builds can be compared answer for answer on the same inputs.
@@ -342,8 +347,10 @@ class Runner:
         if self.dist is not None:
             self.dist.barrier()
 
-    def time(self, pipeline, steps, warmup, keep_results=False):
-        """W untimed steps, barrier + synchronize, exactly K timed steps, synchronize, MAX over ranks."""
+    def time(self, pipeline, steps, warmup, keep_results=False, full=True):
+        """W untimed steps, barrier + synchronize, exactly K timed steps, synchronize, MAX over ranks.
+        full=False (a run without --full): pass A and the timed region only -- no pass C and no counting call, so the result has
+        neither `ms_per_step_unprofiled` nor `counts`."""
         torch, ctx = self.torch, self.ctx
         cfg = make_config(self.sw, pipeline)
         ccfg = cfg.to_c()
@@ -385,19 +392,21 @@ class Runner:
         ctx.profile(False)
         dom_live = ctx.profile_table().get(dom) if dom else None
         ctx.profile_select(None)
-        # pass C: no events at all -- what a caller gets
-        plain, _ = timed(steps)
+        out = {"cfg": cfg, "elapsed": elapsed, "local_elapsed": local_elapsed, "ms_per_step": elapsed / steps * 1e3,
+               "ms_per_step_all_events": all_events / steps * 1e3, "prof": prof, "prof_units": prof_units, "dom": dom, "dom_live": dom_live}
+        if full:
+            # pass C: no events at all -- what a caller gets
+            plain, _ = timed(steps)
+            out["ms_per_step_unprofiled"] = plain / steps * 1e3
         if keep_results:   # the answers of the last timed step (copied before the counting call below writes the same buffers)
             kept = self.status[:self.n].clone(), self.chain[:self.n].clone()
             torch.cuda.synchronize()
-        self.step(ccfg, with_stats=True)  # untimed: counts for the report
-        ctx.synchronize()
-        s = self.stats
-        out = {"cfg": cfg, "elapsed": elapsed, "local_elapsed": local_elapsed, "ms_per_step": elapsed / steps * 1e3,
-               "ms_per_step_all_events": all_events / steps * 1e3, "ms_per_step_unprofiled": plain / steps * 1e3,
-               "prof": prof, "prof_units": prof_units, "dom": dom, "dom_live": dom_live,
-               "counts": {"in": s.n_in, "retained": s.n_retained, "swept": s.n_swept, "chains": s.n_chains,
-                          "chains_kept": s.n_chains_kept, "out": s.n_out, "device_ms_last_step": s.device_ms}}
+        if full:
+            self.step(ccfg, with_stats=True)  # untimed: counts for the report
+            ctx.synchronize()
+            s = self.stats
+            out["counts"] = {"in": s.n_in, "retained": s.n_retained, "swept": s.n_swept, "chains": s.n_chains,
+                             "chains_kept": s.n_chains_kept, "out": s.n_out, "device_ms_last_step": s.device_ms}
         if keep_results:
             out["status"], out["chain"] = kept
         return out
@@ -595,8 +604,8 @@ def strong_scaling(torch, sw, lib_mod, ctx, device, dist, args, rank, world, col
     run = Runner(torch, sw, lib_mod, ctx, device, dist, scols, m, G, coll_device)
     res = {}
     idx_h = mine.cpu().numpy()
-    for p in PIPELINES:
-        t = run.time(p, args.steps, args.warmup, keep_results=True)
+    for p in (PIPELINES if args.full else (args.pipeline,)):
+        t = run.time(p, args.steps, args.warmup, keep_results=True, full=args.full)
         lt = torch.tensor([t["local_elapsed"] / args.steps * 1e3], dtype=torch.float64, device=coll_device)
         per_rank = [torch.zeros_like(lt) for _ in range(world)]
         if dist is not None:
@@ -627,7 +636,7 @@ def strong_scaling(torch, sw, lib_mod, ctx, device, dist, args, rank, world, col
             dist.all_reduce(cb, op=dist.ReduceOp.SUM)   # wraps modulo 2^64 like the per-shard sums
             chk = int(cb.item()) & 0xFFFFFFFFFFFFFFFF
         res[p] = {"flags": FLAGS[p], "ms_per_step": t["ms_per_step"], "value": n / (t["ms_per_step"] * 1e-3), "unit": "mappings/s",
-                  "per_rank_ms": per_rank_ms, "renumber_s": renumber_s, "counts_rank0": t["counts"], "result_checksum": f"{chk:016x}"}
+                  "per_rank_ms": per_rank_ms, "renumber_s": renumber_s, "counts_rank0": t.get("counts"), "result_checksum": f"{chk:016x}"}
     return {"mappings_total": n, "plan_s": plan_s, "partition_s": partition_s, "shard_mappings_rank0": m,
             "load_max_over_mean": float(loads.max() / loads.mean()), "loads": [int(x) for x in loads], "pipelines": res}
 
@@ -867,6 +876,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the other flag sets, the CPU baselines and the parity "
+                         "against the oracle, the host-buffer (PCIe) legs, other record orders and shapes, S-big1, the file-to-file leg, "
+                         "the no-events pass and the counts.  Without it a run sets up, warms up, times --steps steps of --pipeline, "
+                         "writes --dump-outputs and prints its line; the options of those legs then have no effect")
     ap.add_argument("--mappings", type=int, default=0, help="mappings per GPU (weak) / in total (strong); 0 = the workload's size")
     ap.add_argument("--genomes", type=int, default=100)
     ap.add_argument("--workload", default="span", choices=["span", "sbig1"],
@@ -904,6 +918,9 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.scaling == "strong":
         ap.error("--dump-outputs needs --scaling weak (strong scaling keeps the answers spread over the ranks)")
+    if not args.full:   # a plain run is the run with every leg beside the headline's timed steps switched off
+        args.only = args.no_pcie = True
+        args.cpu_sample = args.shapes = args.sbig1 = args.e2e = 0
 
     launched = "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -980,7 +997,7 @@ def main():
         run = Runner(torch, sw, _lib, ctx, device, dist, cols, n, G, coll_device)
         cpu_legs = world == 1 and args.cpu_sample > 0   # the CPU legs belong to the N=1 run
         dump = bool(args.dump_outputs) and rank == 0
-        timed = {p: run.time(p, args.steps, args.warmup, keep_results=cpu_legs or (dump and p == args.pipeline)) for p in order}
+        timed = {p: run.time(p, args.steps, args.warmup, keep_results=cpu_legs or (dump and p == args.pipeline), full=args.full) for p in order}
         dumped = None
         if dump:
             t = timed[args.pipeline]
@@ -1045,8 +1062,8 @@ def main():
             for p in order:
                 t = timed[p]
                 e = {"flags": FLAGS[p], "ms_per_step": t["ms_per_step"], "ms_per_step_all_events": t["ms_per_step_all_events"],
-                     "ms_per_step_unprofiled": t["ms_per_step_unprofiled"],
-                     "value": n * world / (t["ms_per_step"] * 1e-3), "unit": "mappings/s", "steps": args.steps, "warmup": args.warmup, "counts": t["counts"],
+                     "ms_per_step_unprofiled": t.get("ms_per_step_unprofiled"),
+                     "value": n * world / (t["ms_per_step"] * 1e-3), "unit": "mappings/s", "steps": args.steps, "warmup": args.warmup, "counts": t.get("counts"),
                      "roofline": roofline(p, n, args.steps, t, "sbig1_10m" if args.workload == "sbig1" else "100m"),
                      "kernels_ms_per_step": kernels_table(t, args.steps)}
                 if cpu_legs:

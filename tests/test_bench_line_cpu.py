@@ -32,6 +32,37 @@ def test_summary_line_of_a_full_report_is_small():
     assert line["parity_ok"] is True and line["detail"] == "gpurun_out/bench_detail.json"
 
 
+def test_summary_line_of_a_plain_report():
+    """A run without --full reports the headline alone (the other legs are null in its report): the line keeps the contract keys
+    and the headline's roofline, and has no key of a leg that did not run."""
+    b = _bench()
+    full = json.load(open(os.path.join(ROOT, "profiles", "r02_v3_bench_100m.json")))
+    head = full["config"].get("pipeline") or "default"
+    plain = dict(full, pipelines={head: dict(full["pipelines"][head], cpu_baseline=None, cpu_baseline_all_cores=None,
+                                                    parity_vs_oracle_on_sample=None, parity_all_threads=None)},
+                 ms_per_step_unprofiled=None, counts=None)
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "parity_vs_oracle_on_sample", "parity_all_threads", "pcie_inclusive", "shapes",
+              "sbig1", "end_to_end"):
+        plain[k] = None
+    line = json.loads(b.fit_line(b.summary_line(plain, None)))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in line, k
+    assert line["value"] == round(full["value"], 4) and line["ms_per_step"] == round(full["ms_per_step"], 4)
+    assert line["roofline"]["kernel"] == full["roofline"]["kernel"] and line["ms_per_step_unprofiled"] is None
+    assert not [k for k in line if k.startswith(("sbig1_", "pcie_", "e2e_", "parity", "cpu_baseline")) or k.endswith("_pipeline_frac")]
+    assert "truncated" not in line
+
+
+def test_full_is_an_option_and_off_by_default():
+    """`--full` exists (the help is printed without touching a GPU) and is a switch: a plain command line does not set it."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout
+    assert "[--full]" in " ".join(r.stdout.split())   # takes no value
+
+
 def test_line_degrades_instead_of_failing():
     """A report that outgrows the limit still yields ONE parsable line under it (optional keys go first, `truncated` says
     which) -- never an exception after a multi-minute run."""

@@ -1,10 +1,13 @@
-"""bench.py contract (ONE stdout line under 4 KB with `roofline` and `cpu_baseline`; the full report -- the three flag sets
-under `pipelines`, the S-big1 leg, the PCIe leg -- in the --detail file) and, through its all-threads parity leg, a multi-million-record parity check of all three flag sets on
-a scaled-down S-pan workload.  Also --gpus validation, the strong-scaling mode on one GPU, and smoke()."""
+"""bench.py contract (ONE stdout line under 4 KB with `roofline` and, under --full, `cpu_baseline`; the full report -- the flag sets
+under `pipelines`, the S-big1 leg, the PCIe leg -- in the --detail file) and, through the all-threads parity leg of --full, a
+multi-million-record parity check of all flag sets on a scaled-down S-pan workload.  A run without --full does the headline's
+steps alone, with the same answers, and spends little time outside them.  Also --gpus validation, the strong-scaling mode on one
+GPU, and smoke()."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -36,7 +39,7 @@ def run_bench(*args, env=None, expect_rc=0):
 @pytest.fixture(scope="module")
 def line():
     n = 4_000_000
-    return n, run_bench("--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1", "--cpu-sample", "300000",
+    return n, run_bench("--full", "--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1", "--cpu-sample", "300000",
                         "--parity-mappings", str(n), "--sbig1", "300000", "--sbig1-parity-sweep", "300000",
                         "--sbig1-parity-scaffold", "60000", "--e2e", "0")
 
@@ -129,7 +132,7 @@ def test_gpus_flag_is_validated():
 
 def test_strong_scaling_mode_one_gpu():
     n = 2_000_000
-    d = run_bench("--scaling", "strong", "--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1")
+    d = run_bench("--full", "--scaling", "strong", "--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1")
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["_line_bytes"] < 4096 and d["_line"]["strong"]["mappings_total"] == n
     ss = d["strong_scaling"]
     assert ss["mappings_total"] == n and ss["shard_mappings_rank0"] == n and ss["load_max_over_mean"] == 1.0
@@ -145,7 +148,7 @@ def test_two_rank_launch_rehearsal():
     instead of RCCL).  Strong mode: the fingerprint of (record, status, GLOBAL chain number) over both shards must equal
     the unsharded run's, for every flag set.  Not a scaling measurement."""
     n = 2_000_000
-    common = ("--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1")
+    common = ("--full", "--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1")
     one = run_bench("--scaling", "strong", *common)
     two = run_bench("--scaling", "strong", "--gpus", "2", "--rehearse", *common)
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and "gloo" in two["_line"]["rehearsal"]
@@ -169,24 +172,71 @@ def test_two_rank_launch_rehearsal():
 
 def test_dump_outputs_are_the_timed_answers_and_repeatable(tmp_path):
     """--dump-outputs: the headline flag set's status / chain of every record (the record set is under the sampling limit),
-    consistent with the run's counts, and identical between two runs that differ only in the number of steps (the inputs
-    do not depend on it); --steps is the number of timed steps the line reports."""
+    identical between runs that differ only in the number of steps (the inputs do not depend on it) and between a run without
+    and a run with --full, and consistent with the counts that --full reports; --steps is the number of timed steps the line
+    reports."""
     import numpy as np
-    common = ("--mappings", "300000", "--genomes", "21", "--only", "--cpu-sample", "0", "--no-pcie", "--e2e", "0", "--sbig1", "0",
-              "--shapes", "0")
-    runs = []
-    for k, steps in enumerate((2, 3)):
-        d = run_bench(*common, "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / f"d{k}"))
+    common = ("--mappings", "300000", "--genomes", "21")
+    legs_off = ("--only", "--cpu-sample", "0", "--no-pcie", "--e2e", "0", "--sbig1", "0", "--shapes", "0")
+    runs, counts = [], None
+    for k, (steps, extra) in enumerate(((2, ()), (3, ()), (2, ("--full", *legs_off)))):
+        d = run_bench(*common, *extra, "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / f"d{k}"))
         assert d["steps"] == steps and d["_line"]["steps"] == steps and d["ms_per_step"] > 0
         assert d["dump_outputs"]["records"] == 300000 and d["dump_outputs"]["sampled"] is False
         a = {x: np.load(tmp_path / f"d{k}" / f"{x}.npy") for x in ("index", "status", "chain")}
         assert a["status"].dtype == np.float32 and a["chain"].dtype == np.float64 and a["index"].dtype == np.float64
         assert np.array_equal(a["index"], np.arange(300000))
-        assert int((a["status"] != 0).sum()) == d["counts"]["out"] and 0 < d["counts"]["out"] < 300000
         assert int(np.count_nonzero(a["chain"])) > 0   # default flags: scaffold chains are numbered
+        if extra:
+            counts = d["counts"]
+        else:
+            assert d["counts"] is None   # the counting call belongs to --full
         runs.append(a)
-    for x in ("status", "chain"):
-        assert np.array_equal(runs[0][x], runs[1][x]), x
+    assert 0 < counts["out"] < 300000
+    for a in runs:
+        assert int((a["status"] != 0).sum()) == counts["out"]
+        for x in ("status", "chain"):
+            assert np.array_equal(runs[0][x], a[x]), x
+
+
+CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                 "dtype", "data", "config", "roofline", "detail")
+
+
+def test_plain_run_does_the_headline_alone():
+    """Without --full: the contract keys and the headline's roofline as under --full, one flag set timed, and none of the other
+    legs -- also when their options are given."""
+    n = 1_000_000
+    d = run_bench("--mappings", str(n), "--genomes", "21", "--steps", "2", "--warmup", "1", "--cpu-sample", "300000", "--sbig1", "300000")
+    ln = d["_line"]
+    assert d["_line_bytes"] < 4096
+    for k in CONTRACT_KEYS:
+        assert k in ln, k
+    assert ln["metric"].startswith("PAF mappings/sec") and ln["unit"] == "mappings/s" and ln["higher_is_better"] is True
+    assert ln["dtype"] == "u32 coordinates, f64 scores" and ln["n_gpus"] == 1 and ln["steps"] == 2 and ln["warmup"] == 1
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert ln["value"] == pytest.approx(d["value"], rel=1e-6) and ln["ms_per_step"] == pytest.approx(d["ms_per_step"], abs=1e-3)
+    assert d["config"]["flags"] == "(defaults)" and list(d["pipelines"]) == ["default"]
+    rf = d["roofline"]
+    assert rf["kernel"] in d["kernels_ms_per_step"] and rf["kernel_avg_ms"] > 0 and rf["algorithmic_bytes_per_mapping"] == 47
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "parity_all_threads", "pcie_inclusive", "shapes", "sbig1", "end_to_end", "counts",
+              "ms_per_step_unprofiled"):
+        assert d[k] is None, k
+    assert not [k for k in ln if k.startswith(("sbig1_", "pcie_", "e2e_", "sweep_", "full_", "c5_", "parity", "cpu_baseline"))]
+    assert not [k for k in ln if k.endswith("_default_ms")]
+
+
+def test_plain_run_spends_little_outside_its_steps():
+    """The headline workload (10^8 mappings) without --full: the whole run, from process start to exit, less its (steps + warmup)
+    x ms_per_step, is at most 30 s."""
+    steps, warmup = 5, 1
+    t0 = time.perf_counter()
+    d = run_bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup))
+    wall = time.perf_counter() - t0
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    print(f"plain run: wall {wall:.2f} s, ms_per_step {d['ms_per_step']:.3f}, outside its steps {outside:.2f} s")
+    assert d["config"]["mappings_per_gpu"] == 100_000_000
+    assert outside <= 30.0, outside
 
 
 def test_smoke_entry():

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 WL=${WL:-span}
-COMMON="--workload $WL --only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0 --steps 1 --warmup 0"
+COMMON="--workload $WL --steps 1 --warmup 0"
 pass () {
   d=$1; shift
   timeout -k 5 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$d -- python3 $R/bench.py --pipeline $P $COMMON > $OUT/$d.log 2>&1 || echo "$d: rc=$? $(grep -m1 -i 'exceeds\|error' $OUT/$d.log | cut -c1-160)"

@@ -2,9 +2,9 @@
 """Per-kernel HBM traffic from two rocprofv3 PMC runs (FETCH_SIZE and WRITE_SIZE collected in SEPARATE passes,
 as /opt/skills/guides/MI355X_MICROARCH.md prescribes) -> the JSON bench.py reads for `roofline.traffic`.
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --others 0
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_write -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --others 0
-  python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write 100000000 > profiles/rNN_vMM_hbm_traffic_sweep_100m.json
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d pmc_fetch -- python3 bench.py --steps 1 --warmup 0 --full --only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d pmc_write -- python3 bench.py --steps 1 --warmup 0 --full --only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0
+  python tools/pmc_traffic.py pmc_fetch pmc_write 100000000 > profiles/rNN_vMM_hbm_traffic_default_100m.json
 
 Both counters are in KB per dispatch; hbm_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (the gfx950 FETCH_SIZE x2
 correction, calibrated on os_pass which reads exactly 12 B per pair)."""
@@ -108,7 +108,8 @@ def collect(d, counter):
 
 def main():
     fetch_dir, write_dir, n = sys.argv[1], sys.argv[2], int(sys.argv[3])
-    # filter calls inside one profiled bench.py run (--steps 1 --warmup 0: all-events pass + timed region + no-events pass + statistics = 4)
+    # filter calls inside one profiled bench.py --full run (--steps 1 --warmup 0: all-events pass + timed region + no-events pass + statistics = 4;
+    # without --full there are the first two only)
     calls = int(sys.argv[4]) if len(sys.argv) > 4 else 4
     (fe, ex_f, last_f), (wr, ex_w, last_w) = collect(fetch_dir, "FETCH_SIZE"), collect(write_dir, "WRITE_SIZE")
     executions = max(ex_f, ex_w)

@@ -14,7 +14,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export SWG_CALL_MARKER=1   # an empty launch opens every filter call: tools/pmc_traffic.py cuts the traces there
-COMMON="--only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0"
+COMMON="--full --only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0"
 run_set () {  # $1 = workload flag value, $2 = file suffix, $3 = mappings, $4 = flag sets, $5 = flag sets with SQ tables
   WL=$1; SUF=$2; NM=$3; PIPES=$4; SQPIPES=$5
   for p in $PIPES; do

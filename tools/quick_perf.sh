@@ -9,7 +9,7 @@ SBIG=${3:-}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0"
+COMMON="--full --only --cpu-sample 0 --no-pcie --e2e 0 --sbig1 0"
 one () {
   wl=$1; p=$2
   python3 $R/bench.py --workload $wl --pipeline $p --steps 8 --warmup 2 $COMMON --detail $OUT/${wl}_$p.json > $OUT/${wl}_$p.log 2>&1
