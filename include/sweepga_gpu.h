@@ -408,6 +408,57 @@ int swg_alnstats_compare(const swg_alnstats* a, const swg_alnstats* b, const cha
                          char** out_text, uint64_t* out_len);
 const char* swg_alnstats_last_error(void);
 
+/* ---- alnstats on the device: the same statistics from record columns, "before" and "after" a filter call in one pass --------
+ * The integer results of parse_paf (:103-161) over n records given as columns -- q_id, t_id, q_start, q_end and matches are
+ * read, nothing else -- under a sequence -> genome map the caller supplies (alnstats' own rule is the prefix up to and
+ * including the last '#', the whole name without one; any other partition of the sequences works).  status == NULL: one
+ * result set, ALL records.  status != NULL: a second set, KEPT, over the records with status != 0 -- the rule of
+ * swg_paf_write -- from the same launches.  Sums are u64 and wrap as the reference's release build does; mapping length =
+ * q_end - q_start in 32 bits (start <= end is assumed, as everywhere in this library).  Integers only: coverage and the
+ * averages are derived on the host, in the reference's operation order.  n >= 2^31 records or n_seq > 2^31 sequences:
+ * SWG_ERR_RANGE.  A sequence or genome id out of range: SWG_ERR_INVALID.  Scratch (the distinct-pair hash set, 16 to 32 bytes
+ * per record at most, the genome-pair table, and for host columns 21 bytes per record of staging) comes from the context's
+ * arena: SWG_ERR_OOM when the memory limit does not hold it. */
+typedef struct swg_alnstats_pair_counts {
+  uint32_t q_genome, t_genome; /* ORDERED pair of genome ids (query genome, target genome) */
+  uint64_t bases, matches;     /* sums over the pair's inter-genome records */
+  uint64_t first_record;       /* smallest index of such a record: the pairs are listed in ascending order of it */
+} swg_alnstats_pair_counts;
+typedef struct swg_alnstats_counts {
+  uint64_t total_mappings, total_bases, total_matches;
+  uint64_t self_mappings;     /* q_id == t_id */
+  uint64_t inter_chromosomal; /* different sequences of one genome */
+  uint64_t inter_genome;      /* the genomes differ (tested after self, before inter-chromosomal, :140-152) */
+  uint64_t chr_pair_count;    /* distinct (q_id, t_id) over every record of the set */
+  uint64_t n_pairs;           /* out: genome pairs that occur; never more than min(n, n_genome * n_genome) */
+  uint64_t pair_capacity;     /* in: entries `pairs` can hold */
+  swg_alnstats_pair_counts* pairs; /* in: caller-owned [pair_capacity] or NULL; written only when n_pairs <= pair_capacity
+                                      (otherwise the call still returns SWG_OK: compare the two and call again) */
+  uint64_t* seq_last;         /* in: caller-owned [n_seq] or NULL.  Per sequence, the last line of the set that names it:
+                                 2 * record + side, side 1 = as target (:132-133 insert the target after the query, so on
+                                 one line the target's length has the last word); UINT64_MAX = no record of the set names it */
+} swg_alnstats_counts;
+/* rec: host pointers; seq_genome[rec->n_seq] and status[n] on the host.  all / kept: either may be NULL (kept is ignored
+ * when status is NULL). */
+int swg_alnstats_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                         const uint8_t* status, swg_alnstats_counts* all, swg_alnstats_counts* kept);
+/* The same with the five columns of rec, seq_genome and status in device memory of ctx's GPU (status as swg_filter_device
+ * leaves it); the counts structures and the arrays they point to stay on the host.  No record column is copied to the host. */
+int swg_alnstats_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                const uint8_t* status, swg_alnstats_counts* all, swg_alnstats_counts* kept);
+/* Statistics of the records of an open PAF, computed on the device.  status == NULL: every record (what swg_alnstats_open
+ * gives for the same file).  status != NULL: *all_out as before and *kept_out over the records with status != 0 (what
+ * swg_alnstats_open gives for the file swg_paf_write would write).  Either out may be NULL.  The handles are ordinary ones:
+ * swg_alnstats_get, _pair, _report, _compare and _close work on them.  Sequence lengths are read from the text the handle
+ * keeps -- column 2 or 7 of the one line per sequence the device names -- so no length column exists and nothing more crosses
+ * PCIe than the five columns.  An unparsable length on one of THOSE lines is SWG_ERR_INVALID with the host tool's message; on a
+ * line that no sequence's size depends on it goes unnoticed, where the host tool stops.  A file in which column 3, 4, 10 or 11
+ * of some line does not parse, or whose cg:Z: tag overrode column 10, is rare: its six columns are checked and column 10 read
+ * again line by line on the host first (same errors as swg_alnstats_open).  Errors: text in swg_alnstats_last_error().
+ * A PAF with no records needs no device (ctx may be NULL then).  .1aln handles keep no text to read lengths from: the
+ * swg_alnstats_records seam works on swg_aln_records, swg_paf_alnstats has no .1aln twin. */
+int swg_paf_alnstats(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, swg_alnstats** all_out, swg_alnstats** kept_out);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -27,6 +27,7 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_paf_tree_filter", "swg_free", "swg_stream_plan", "swg_paf_identity_is_derived",
            "swg_alnstats_open", "swg_alnstats_open_buffer", "swg_alnstats_close", "swg_alnstats_get", "swg_alnstats_pair",
            "swg_alnstats_report", "swg_alnstats_compare", "swg_alnstats_last_error",
+           "swg_alnstats_records", "swg_alnstats_records_device", "swg_paf_alnstats",
            "swg_fasta_open", "swg_fasta_close", "swg_fasta_num_records", "swg_fasta_name", "swg_fasta_file_index",
            "swg_fasta_offsets", "swg_fasta_bases", "swg_fasta_last_error", "swg_mash_sketch", "swg_mash_merge",
            "swg_mash_distances", "swg_mash_random_pairs", "swg_select_pairs", "swg_joblist"]
@@ -105,6 +106,17 @@ class SwgAniInput(C.Structure):
         ("block_len", C.c_void_p),
         ("total_genome_size", C.c_double),
     ]
+
+
+class SwgAlnstatsPairCounts(C.Structure):
+    _fields_ = [("q_genome", C.c_uint32), ("t_genome", C.c_uint32), ("bases", C.c_uint64), ("matches", C.c_uint64),
+                ("first_record", C.c_uint64)]
+
+
+class SwgAlnstatsCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("total_mappings", "total_bases", "total_matches", "self_mappings", "inter_chromosomal",
+                                           "inter_genome", "chr_pair_count", "n_pairs", "pair_capacity")] + \
+               [("pairs", C.POINTER(SwgAlnstatsPairCounts)), ("seq_last", C.POINTER(C.c_uint64))]
 
 
 _lib = None
@@ -245,6 +257,13 @@ def load():
     lib.swg_get_memory_limit.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.swg_free.restype = None
     lib.swg_free.argtypes = [C.c_void_p]
+    for name in ("swg_alnstats_records", "swg_alnstats_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgAlnstatsCounts),
+                      C.POINTER(SwgAlnstatsCounts)]
+    lib.swg_paf_alnstats.restype = C.c_int
+    lib.swg_paf_alnstats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = lib
     return lib
 

@@ -20,6 +20,9 @@
 #include "../../../include/sweepga_gpu.h"
 #include "host_internal.h"
 
+const char* const SWG_ALNSTATS_FIELD_ERR[6] = {"Invalid query length", "Invalid query start", "Invalid query end",
+                                               "Invalid target length", "Invalid match count", "Invalid block length"};
+
 namespace {
 
 using sv = std::string_view;
@@ -62,8 +65,6 @@ bool parse_u64(sv s, uint64_t* out) {  // str::parse::<u64>: optional '+', digit
   return true;
 }
 
-const char* const FIELD_ERR[6] = {"Invalid query length", "Invalid query start", "Invalid query end",
-                                  "Invalid target length", "Invalid match count", "Invalid block length"};
 
 struct Part {
   uint64_t total_mappings = 0, total_bases = 0, total_matches = 0, self_mappings = 0, inter_chromosomal = 0, inter_genome = 0;
@@ -177,7 +178,7 @@ int compute(const char* text, size_t len, int threads, swg_alnstats** out) {
   // merge in file order
   uint64_t base = 0;
   for (auto& P : parts) {
-    if (P.err_field >= 0) return stats_error(SWG_ERR_INVALID, "%s (line %llu)", FIELD_ERR[P.err_field], (unsigned long long)(base + P.err_line + 1));
+    if (P.err_field >= 0) return stats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[P.err_field], (unsigned long long)(base + P.err_line + 1));
     base += P.lines;
   }
   auto* S = new swg_alnstats;
@@ -326,6 +327,52 @@ void two_rows(std::string* o, const char* title, const std::string& f1, const st
 }
 
 }  // namespace
+
+int swg_alnstats_error(int code, const char* fmt, ...) {
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+// The handle of one device result set.  calculate_coverage_stats (:42-73) as compute() above runs it: the pairs in order of
+// first appearance, coverage = 100 * bases / size of the query genome, summed in that order.
+int swg_alnstats_from_counts(const swg_alnstats_result& r, const std::vector<std::string>& genome_name,
+                             const std::vector<uint64_t>& genome_size, swg_alnstats** out) {
+  *out = nullptr;
+  try {
+    auto* S = new swg_alnstats;
+    swg_alnstats_summary& s = S->sum;
+    s.total_mappings = r.total_mappings;
+    s.total_bases = r.total_bases;
+    s.total_matches = r.total_matches;
+    s.self_mappings = r.self_mappings;
+    s.inter_chromosomal = r.inter_chromosomal;
+    s.inter_genome = r.inter_genome;
+    s.chr_pair_count = r.chr_pair_count;
+    double sum = 0.0;
+    for (const swg_alnstats_pair_counts& p : r.pairs) {
+      const double cov = 100.0 * (double)p.bases / (double)genome_size[p.q_genome];
+      S->pair_q.push_back(genome_name[p.q_genome]);
+      S->pair_t.push_back(genome_name[p.t_genome]);
+      S->pair_bases.push_back(p.bases);
+      S->pair_matches.push_back(p.matches);
+      S->pair_cov.push_back(cov);
+      sum += cov;
+      s.above_95_pct += cov > 95.0;
+    }
+    s.genome_pairs = S->pair_cov.size();
+    s.avg_coverage = s.genome_pairs ? sum / (double)s.genome_pairs : 0.0;
+    s.avg_identity = s.total_bases > 0 ? (double)s.total_matches / (double)s.total_bases : 0.0;  // :75-81
+    *out = S;
+    return SWG_OK;
+  } catch (const std::bad_alloc&) {
+    return stats_error(SWG_ERR_OOM, "out of host memory");
+  }
+}
 
 extern "C" {
 

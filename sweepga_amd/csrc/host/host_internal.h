@@ -10,10 +10,36 @@
 int swg_host_text_load(const char* path, int threads, const char** data, size_t* len, void** handle);
 void swg_host_text_release(void* handle);
 
-// ---- --joblist (fasta_io.cpp, swg_mash.hip, mash_host.cpp) ----
 struct swg_ctx;
 struct swg_fasta;
 int swg_set_error(swg_ctx* ctx, int code, const char* fmt, ...);
+
+// ---- alnstats on the device (swg_alnstats.hip, alnstats.cpp, paf_io.cpp) ----
+#ifdef SWEEPGA_GPU_H
+#include <string>
+#include <vector>
+// one result set of the device statistics with library-owned storage (the C ABI copies it into the caller's arrays)
+struct swg_alnstats_result {
+  uint64_t total_mappings = 0, total_bases = 0, total_matches = 0, self_mappings = 0, inter_chromosomal = 0, inter_genome = 0,
+           chr_pair_count = 0;
+  std::vector<swg_alnstats_pair_counts> pairs;  // ascending first_record
+  std::vector<uint64_t> seq_last;               // [n_seq], UINT64_MAX = absent
+};
+// columns of rec on the host (on_device = false: staged in the arena) or on the device, seq_genome / status likewise
+int swg_alnstats_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome,
+                     const uint8_t* status, swg_alnstats_result* all, swg_alnstats_result* kept);
+// an ordinary swg_alnstats handle from one result set: genome g's name (trailing '#' kept) and size (sum of the last-seen
+// lengths of its sequences in the set); calculate_coverage_stats (:42-73) in the order of the pairs
+int swg_alnstats_from_counts(const swg_alnstats_result& r, const std::vector<std::string>& genome_name,
+                             const std::vector<uint64_t>& genome_size, swg_alnstats** out);
+// the text side of swg_paf_alnstats (paf_io.cpp; host code only, so that the host translation units link without the device ones)
+int swg_paf_stats_prepare(const swg_paf* p, swg_records* rec, std::vector<uint32_t>* col10, const uint32_t** seq_genome);
+int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res /* [2]: ALL, KEPT */, swg_alnstats** const* outs /* [2], NULL = not wanted */);
+int swg_alnstats_error(int code, const char* fmt, ...);  // sets swg_alnstats_last_error()
+extern const char* const SWG_ALNSTATS_FIELD_ERR[6];      // "Invalid query length" ... for columns 2, 3, 4, 7, 10, 11
+#endif
+
+// ---- --joblist (fasta_io.cpp, swg_mash.hip, mash_host.cpp) ----
 // detect_file_type's FASTA test over text already loaded
 bool swg_fasta_text_is_fasta(const char* p, size_t n);
 // the sketch of swg_mash_sketch, handed over contig by contig: emit(user, contig, ascending values, count), in contig order

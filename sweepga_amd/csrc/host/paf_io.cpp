@@ -382,6 +382,7 @@ struct Slice {
   const char* err_what = nullptr;
   bool wide = false;             // met a coordinate / matches / block length >= 2^32
   bool custom_identity = false;  // a record whose identity is not matches / max(block length, 1) (a dv:f: tag had the last word)
+  bool stats_irregular = false;  // a record whose column 3, 4, 10 or 11 did not parse, or whose cg:Z: tag replaced column 10 by another value
 };
 
 }  // namespace
@@ -401,6 +402,7 @@ struct swg_paf {
   std::vector<uint32_t> g_last, g_two;
   swg_records rec{};
   bool identity_derived = false;     // every record's identity is matches / max(block length, 1)
+  bool stats_irregular = false;      // the columns are not what alnstats reads from some line (swg_paf_alnstats checks the text first)
   double load_ms = 0, parse_ms = 0;
   // ANI view (filled by swg_paf_ani_input)
   bool have_ani = false;
@@ -521,7 +523,9 @@ int parse_text(swg_paf* p, int threads) {
       auto fld = [&](int i) { return std::string_view(f[i], (size_t)(f[i + 1] - 1 - f[i])); };
       auto u64_or = [&](int i, uint64_t d) {
         uint64_t v;
-        return parse_u64(f[i], (size_t)(f[i + 1] - 1 - f[i]), &v) ? v : d;
+        if (parse_u64(f[i], (size_t)(f[i + 1] - 1 - f[i]), &v)) return v;
+        if (i != 7 && i != 8) s.stats_irregular = true;  // alnstats stops at such a line (it reads columns 3, 4, 10, 11; not 8, 9)
+        return d;
       };
       auto narrow = [&](uint64_t v) {
         if (v > 0xffffffffull) s.wide = true;
@@ -542,6 +546,7 @@ int parse_text(swg_paf* p, int threads) {
           } else if (tg[0] == 'c' && tg[1] == 'g' && tg[3] == 'Z') {
             uint64_t cm;
             if (cigar_eq_total(tg + 5, tl - 5, &cm) && cm > 0) {
+              if (cm != matches) s.stats_irregular = true;  // (compared with the value before it: column 10 or an equal override)
               matches = cm;
               identity = (double)cm / denom;
             }
@@ -586,6 +591,7 @@ int parse_text(swg_paf* p, int threads) {
   for (auto& s : sl) {
     wide = wide || s.wide;
     if (s.custom_identity) p->identity_derived = false;
+    if (s.stats_irregular) p->stats_irregular = true;
   }
   if (wide) {
     for (auto& w : p->wide) w.alloc(cap);
@@ -865,6 +871,82 @@ int swg_paf_text(const swg_paf* p, const char** text, uint64_t* len) {
   *len = p->text.len;
   return SWG_OK;
 }
+
+}  // extern "C"
+
+// The text side of swg_paf_alnstats (swg_alnstats.hip, which runs the device part between the two): host code only.
+//   prepare: the records and genome map the device reads.  A file in which alnstats would not read what the columns hold
+//            (flagged while parsing) has its six columns checked and column 10 read again, line by line, with the host tool's errors.
+//   finish:  the device names, per sequence, the last line of the set that mentions it and on which side (:132-133, last writer
+//            wins); column 2 or 7 of just those lines is read here and summed per genome, then the handles are built.
+namespace {
+// column k (0-based, < 11) of record r
+inline const char* stats_column(const swg_paf* p, uint64_t r, int k, size_t* len) {
+  const char* b = p->text.data + p->rec_off[r];
+  const char* e = b + p->rec_len[r];
+  for (; k > 0; --k) b = static_cast<const char*>(std::memchr(b, '\t', (size_t)(e - b))) + 1;  // a record has >= 11 columns
+  const void* t = std::memchr(b, '\t', (size_t)(e - b));
+  *len = t ? (size_t)(static_cast<const char*>(t) - b) : (size_t)(e - b);
+  return b;
+}
+}  // namespace
+
+int swg_paf_stats_prepare(const swg_paf* p, swg_records* rec, std::vector<uint32_t>* col10, const uint32_t** seq_genome) {
+  static const int COL[6] = {1, 2, 3, 6, 9, 10};
+  *rec = p->rec;
+  *seq_genome = p->g_last.data();
+  if (!p->stats_irregular) return SWG_OK;
+  const uint64_t n = p->rec.n;
+  col10->resize(n);
+  for (uint64_t r = 0; r < n; ++r)
+    for (int j = 0; j < 6; ++j) {
+      size_t len;
+      const char* b = stats_column(p, r, COL[j], &len);
+      uint64_t v;
+      if (!parse_u64(b, len, &v))
+        return swg_alnstats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[j], (unsigned long long)(p->rank[r] + 1));
+      if (j == 4) {
+        if (v > 0xffffffffull) return swg_alnstats_error(SWG_ERR_RANGE, "match count >= 2^32 on line %llu", (unsigned long long)(p->rank[r] + 1));
+        (*col10)[r] = (uint32_t)v;
+      }
+    }
+  rec->matches = col10->data();
+  return SWG_OK;
+}
+
+int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res, swg_alnstats** const* outs) {
+  const uint64_t n = p->rec.n;
+  const uint32_t G = n ? p->rec.n_genome_last : 0;
+  std::vector<std::string> gname(G);
+  for (size_t s = 0; s < p->names.size() && n; ++s) gname[p->g_last[s]] = prefix_last(p->names[s]);
+  int rc = SWG_OK;
+  for (int k = 0; k < 2 && rc == SWG_OK; ++k) {
+    if (!outs[k]) continue;
+    std::vector<uint64_t> gsize(G, 0);
+    for (size_t s = 0; s < res[k].seq_last.size(); ++s) {
+      const uint64_t v = res[k].seq_last[s];
+      if (v == UINT64_MAX) continue;
+      size_t len;
+      const char* b = stats_column(p, v >> 1, (v & 1) ? 6 : 1, &len);
+      uint64_t size;
+      if (!parse_u64(b, len, &size)) {
+        rc = swg_alnstats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[(v & 1) ? 3 : 0], (unsigned long long)(p->rank[v >> 1] + 1));
+        break;
+      }
+      gsize[p->g_last[s]] += size;
+    }
+    if (rc == SWG_OK) rc = swg_alnstats_from_counts(res[k], gname, gsize, outs[k]);
+  }
+  if (rc != SWG_OK)  // no half result
+    for (int k = 0; k < 2; ++k)
+      if (outs[k] && *outs[k]) {
+        swg_alnstats_close(*outs[k]);
+        *outs[k] = nullptr;
+      }
+  return rc;
+}
+
+extern "C" {
 
 int swg_paf_write(const swg_paf* p, const char* out_path, const uint8_t* status, const uint32_t* chain, int threads,
                   uint64_t* n_written) {

@@ -229,6 +229,31 @@ int run_joblist(const std::vector<std::string>& inputs, const std::string& spars
   return 0;
 }
 
+// --stats: the bytes `alnstats <input> <output>` prints for the two files (compare_stats), with --stats-detailed followed by
+// the two `alnstats <file> -d` reports (input, then output).  "-" = standard error: standard output may carry the PAF.
+void write_stats_report(const std::string& path, const swg_alnstats* before, const swg_alnstats* after, const std::string& in_label,
+                        const std::string& out_label, bool detailed) {
+  std::string all;
+  char* text = nullptr;
+  uint64_t len = 0;
+  if (swg_alnstats_compare(before, after, in_label.c_str(), out_label.c_str(), &text, &len) != SWG_OK)
+    die(3, std::string("--stats: ") + swg_alnstats_last_error());
+  all.assign(text, len);
+  swg_free(text);
+  if (detailed)
+    for (int k = 0; k < 2; ++k) {
+      if (swg_alnstats_report(k ? after : before, (k ? out_label : in_label).c_str(), 1, &text, &len) != SWG_OK)
+        die(3, std::string("--stats-detailed: ") + swg_alnstats_last_error());
+      all.append(text, len);
+      swg_free(text);
+    }
+  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+  if (!all.empty() && std::fwrite(all.data(), 1, all.size(), f) != all.size()) die(2, "write to " + path + " failed");
+  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+  if (f == stderr) std::fflush(stderr);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -243,7 +268,8 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   std::string bad_sparsify, tree_sparsify, sparsify = "none", joblist_dir = ".";
   std::vector<std::string> inputs;
-  bool joblist = false, threads_given = false;
+  bool joblist = false, threads_given = false, stats_detailed = false;
+  std::string stats_path;  // --stats: empty = no report
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -302,6 +328,8 @@ int main(int argc, char** argv) {
       if (!parse_int(value(), &threads) || threads < 0) die(2, "invalid value for --threads");
       threads_given = true;
     }
+    else if (a == "--stats") { stats_path = value(); if (stats_path.empty()) die(2, "empty value for --stats"); }
+    else if (a == "--stats-detailed") stats_detailed = true;
     else if (a == "--joblist") joblist = true;
     else if (a == "--joblist-output-dir") joblist_dir = value();
     else if (a == "--mash-kmer-size") { if (!parse_u64(value(), &mash_k)) die(2, "invalid value for --mash-kmer-size"); }
@@ -312,8 +340,12 @@ int main(int argc, char** argv) {
                 "         [--scaffold-mass N] [--scaffold-filter M] [--scaffold-overlap F] [--scaffold-dist N]\n"
                 "         [--min-scaffold-identity I] [--scaffolds-only] [--ani-method M]\n"
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
+                "         [--stats REPORT|-] [--stats-detailed]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
+                "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
+                "                      computed on the device from the records and their status (- = standard error)\n"
+                "  --stats-detailed    with --stats: followed by the two `alnstats <file> -d` reports (input, then output)\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -442,6 +474,13 @@ int main(int argc, char** argv) {
       std::fputc('\n', out);
       pos = end + 1;
     }
+    if (!stats_path.empty()) {  // no device is opened on this path: the host tool's statistics of the same lines, twice
+      std::fflush(out);
+      swg_alnstats* sa = nullptr;
+      if (swg_alnstats_open_buffer(text, len, threads, &sa) != SWG_OK) die(3, std::string("--stats: ") + swg_alnstats_last_error());
+      write_stats_report(stats_path, sa, sa, input, out_path, stats_detailed);
+      swg_alnstats_close(sa);
+    }
     swg_paf_close(paf);
     gpu_init.join();
     return 0;
@@ -471,7 +510,10 @@ int main(int argc, char** argv) {
 
   // ---- tree sparsification of the input (src/main.rs:3640-3688): the filter then runs on the surviving lines, whose ranks
   // are their positions in the sparsified text (the reference filters the temporary tree-filtered file)
+  swg_alnstats* stats_before = nullptr;  // --stats: the input's statistics when the filter does not see the whole input
   if (!tree_sparsify.empty()) {
+    if (!stats_path.empty() && swg_paf_alnstats(ctx, paf, nullptr, &stats_before, nullptr) != SWG_OK)
+      die(3, std::string("--stats: ") + swg_alnstats_last_error());
     const char* text;
     uint64_t len;
     swg_paf_text(paf, &text, &len);
@@ -526,6 +568,21 @@ int main(int argc, char** argv) {
   }
   const auto t2 = clk::now();
 
+  // ---- --stats: before / after from the columns and the status the filter left, ahead of the write
+  if (!stats_path.empty()) {
+    swg_alnstats *sa = nullptr, *sk = nullptr;
+    if (swg_paf_alnstats(ctx, paf, status.data(), stats_before ? nullptr : &sa, &sk) != SWG_OK) die(3, std::string("--stats: ") + swg_alnstats_last_error());
+    write_stats_report(stats_path, stats_before ? stats_before : sa, sk, input, out_path, stats_detailed);
+    if (!quiet) {
+      const double ms = std::chrono::duration<double, std::milli>(clk::now() - t2).count();
+      std::fprintf(stderr, "[sweepga-gpu] --stats: %.1f ms\n", ms);
+    }
+    swg_alnstats_close(sa);
+    swg_alnstats_close(sk);
+    swg_alnstats_close(stats_before);
+  }
+  const auto t2s = clk::now();
+
   // ---- write_filtered_output (paf_filter.rs:1689-1726): input order, original bytes + tags
   uint64_t kept = 0;
   if (swg_paf_write(paf, out_path.c_str(), status.data(), chain.data(), threads, &kept) != SWG_OK) die(2, swg_paf_last_error());
@@ -538,7 +595,7 @@ int main(int argc, char** argv) {
                  "[sweepga-gpu] %llu records -> %llu kept | read %.1f ms (load %.1f, parse %.1f), filter %.1f ms (device %.1f, h2d %.1f, "
                  "d2h %.1f), write %.1f ms | device start-up %.1f ms beside the read (create %.1f, warm-up %.1f), %.1f ms waited for\n",
                  (unsigned long long)n, (unsigned long long)kept, ms(t0, t1), load_ms, parse_ms, ms(t1b, t2), st.device_ms, st.h2d_ms,
-                 st.d2h_ms, ms(t2, t3), create_ms + warm_ms, create_ms, warm_ms, ms(t1, t1b));
+                 st.d2h_ms, ms(t2s, t3), create_ms + warm_ms, create_ms, warm_ms, ms(t1, t1b));
   }
   if (!quiet) {
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

@@ -1,0 +1,509 @@
+// alnstats (src/bin/alnstats.rs:103-161) over record columns on the device: the integer results of parse_paf for ALL records
+// and, from the same launches, for the records a filter call KEPT (status != 0).  Everything is a sum, a count, a minimum or a
+// maximum of integers keyed by something the host supplies, so the results do not depend on the order of the work:
+//
+//   alnstats_seqpair   distinct (q_id, t_id): open-addressing hash SET over q_id * n_seq + t_id (bit 63 of a slot: some KEPT
+//                      record has the pair).  Runs of one pair inside a wavefront insert once.
+//   alnstats_reduce    the scalar sums and counts (registers -> wavefront -> work-group -> one atomic per work-group and
+//                      quantity); per ordered genome pair sum(bases), sum(matches) and min(record) -- runs of one pair are
+//                      summed across the lanes of the wavefront first (segmented add under a ballot of "same key as the lane
+//                      before"), then in a small LDS table of the work-group, then one atomic per (work-group, pair, quantity);
+//                      per sequence max(2 * record + side), the line that has the last word on its length.  A work-group walks
+//                      its contiguous share of the records BACKWARDS: the first value it offers a sequence is its largest, every
+//                      later one is turned away by a plain load.
+//   alnstats_collect   the occupied entries of the genome-pair table as a list (the host orders it by first record).
+//
+// The genome-pair table is keyed by gq * G + gt under ANY sequence -> genome map (a parameter: alnstats' last-'#' rule here,
+// the filter's two-part prefix for whoever needs per-pair sums next): dense G x G while that is small, open addressing over
+// the pairs that occur beyond it -- at most the distinct (q_id, t_id) pairs, which the first kernel has counted by then.
+// Integer atomics only; no floating point.
+#include <algorithm>
+#include <new>
+
+#include "swg_internal.h"
+#include "host/host_internal.h"
+
+namespace {
+
+constexpr int TB = 256;                    // threads per work-group
+constexpr int WAVES = TB / 64;
+constexpr int LSLOTS = 256;                // LDS genome-pair slots per work-group
+constexpr int LPROBES = 8;                 // ... probed this far, then the run goes to the global table directly
+constexpr uint32_t NONE32 = 0xffffffffu;
+constexpr unsigned long long EMPTY = ~0ull;
+constexpr unsigned long long KEPT_BIT = 1ull << 63;
+constexpr uint64_t DENSE_LIMIT = uint64_t(1) << 20;  // G * G entries of 40 bytes
+enum { S_MAPPINGS = 0, S_BASES, S_MATCHES, S_SELF, S_INTER_GENOME, S_INTER_CHR, S_COUNT };
+// device scalars: [set][S_COUNT], then distinct pairs [2], listed genome pairs [2], bad-id flag
+enum { D_DISTINCT = 2 * S_COUNT, D_LISTED = D_DISTINCT + 2, D_BAD = D_LISTED + 2, D_TOTAL };
+
+struct StatTable {
+  unsigned long long* keys;  // hashed: [mask + 1], EMPTY = free; nullptr = dense (slot = key)
+  unsigned long long* sums;  // [slots][4]: bases ALL, matches ALL, bases KEPT, matches KEPT
+  uint32_t* first;           // [slots][2]: smallest record index ALL, KEPT (NONE32 = none)
+  uint32_t mask;
+  uint64_t slots;
+};
+struct PairOut {  // one listed genome pair
+  unsigned long long key, bases, matches, first;
+};
+
+__device__ __forceinline__ uint32_t hash32(unsigned long long key) { return (uint32_t)((key * 0x9e3779b97f4a7c15ull) >> 32); }
+
+__device__ __forceinline__ uint64_t stat_slot(const StatTable& t, unsigned long long key) {  // inserts when absent
+  if (!t.keys) return key;
+  uint32_t h = hash32(key) & t.mask;
+  for (;;) {
+    unsigned long long k = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == EMPTY) {
+      k = atomicCAS(&t.keys[h], EMPTY, key);
+      if (k == EMPTY) k = key;
+    }
+    if (k == key) return h;
+    h = (h + 1) & t.mask;  // the table has twice the slots of the keys that can occur: a free one always comes
+  }
+}
+
+__device__ __forceinline__ void stat_add(const StatTable& t, unsigned long long key, const unsigned long long v[4], uint32_t f_all,
+                                         uint32_t f_kept) {
+  const uint64_t s = stat_slot(t, key);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (v[j]) atomicAdd(&t.sums[s * 4 + j], v[j]);
+  atomicMin(&t.first[s * 2], f_all);
+  if (f_kept != NONE32) atomicMin(&t.first[s * 2 + 1], f_kept);
+}
+
+// runs of equal keys along the lanes of a wavefront: `heads` = ballot of "first lane of its run" -> one past the run's last lane
+__device__ __forceinline__ int run_end(uint64_t heads, int lane) {
+  const uint64_t above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
+  return above ? __builtin_ctzll(above) : 64;
+}
+__device__ __forceinline__ uint64_t lane_range(int from, int to) {  // bits [from, to), to <= 64
+  const uint64_t upto = to == 64 ? ~0ull : (1ull << to) - 1ull;
+  return upto & ~((1ull << from) - 1ull);
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+  return v;
+}
+
+// ---- distinct (q_id, t_id) ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TB) void alnstats_seqpair_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
+                                                              const uint8_t* __restrict__ status, uint32_t n_seq,
+                                                              unsigned long long* __restrict__ keys, uint32_t mask,
+                                                              unsigned long long* __restrict__ scalars) {
+  const int lane = threadIdx.x & 63;
+  uint32_t new_all = 0, new_kept = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * TB;
+  for (uint64_t base = (uint64_t)blockIdx.x * TB; base < n; base += stride) {  // uniform trip count per work-group
+    const uint64_t i = base + threadIdx.x;
+    unsigned long long key = EMPTY;
+    bool kept = false;
+    if (i < n) {
+      const uint32_t q = q_id[i], t = t_id[i];
+      if (q < n_seq && t < n_seq) {  // (ids out of range are reported by the reduction kernel)
+        key = (unsigned long long)q * n_seq + t;
+        kept = status && status[i] != 0;
+      }
+    }
+    const unsigned long long before = __shfl_up(key, 1);
+    const bool head = lane == 0 || key != before;
+    const uint64_t heads = __ballot(head), keptmask = __ballot(kept);
+    if (head && key != EMPTY) {
+      const bool any_kept = (keptmask & lane_range(lane, run_end(heads, lane))) != 0;
+      uint32_t h = hash32(key) & mask;
+      for (;;) {
+        unsigned long long k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == EMPTY) {
+          k = atomicCAS(&keys[h], EMPTY, key);
+          if (k == EMPTY) {
+            k = key;
+            ++new_all;
+          }
+        }
+        if ((k & ~KEPT_BIT) == key) {
+          if (any_kept && !(k & KEPT_BIT) && !(atomicOr(&keys[h], KEPT_BIT) & KEPT_BIT)) ++new_kept;
+          break;
+        }
+        h = (h + 1) & mask;
+      }
+    }
+  }
+  const unsigned long long a = wave_sum(new_all), k = wave_sum(new_kept);
+  if (lane == 0) {
+    if (a) atomicAdd(&scalars[D_DISTINCT], a);
+    if (k) atomicAdd(&scalars[D_DISTINCT + 1], k);
+  }
+}
+
+// ---- sums, genome-pair table, last line per sequence ----------------------------------------------------------------------
+__device__ __forceinline__ void offer_last(uint32_t* slot, uint32_t v) {
+  if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(slot, v);
+}
+
+__global__ __launch_bounds__(TB) void alnstats_reduce_kernel(uint64_t n, uint64_t per_group, const uint32_t* __restrict__ q_id,
+                                                             const uint32_t* __restrict__ t_id, const uint32_t* __restrict__ q_start,
+                                                             const uint32_t* __restrict__ q_end, const uint32_t* __restrict__ matches,
+                                                             const uint8_t* __restrict__ status, const uint32_t* __restrict__ seq_genome,
+                                                             uint32_t n_seq, uint32_t n_genome, StatTable T,
+                                                             uint32_t* __restrict__ seq_last,  // [2][n_seq]: 2 * record + side + 1, 0 = none
+                                                             unsigned long long* __restrict__ scalars) {
+  __shared__ unsigned long long l_key[LSLOTS];
+  __shared__ unsigned long long l_sum[LSLOTS][4];
+  __shared__ uint32_t l_first[LSLOTS][2];
+  __shared__ unsigned long long l_red[WAVES][2 * S_COUNT];
+  __shared__ uint32_t l_bad;
+  for (int s = threadIdx.x; s < LSLOTS; s += TB) {
+    l_key[s] = EMPTY;
+    l_sum[s][0] = l_sum[s][1] = l_sum[s][2] = l_sum[s][3] = 0;
+    l_first[s][0] = l_first[s][1] = NONE32;
+  }
+  if (threadIdx.x == 0) l_bad = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t b0 = (uint64_t)blockIdx.x * per_group;
+  const uint64_t b1 = b0 + per_group < n ? b0 + per_group : n;
+  unsigned long long acc[2][S_COUNT] = {};
+  bool bad = false;
+  const uint64_t iters = b1 > b0 ? (b1 - b0 + TB - 1) / TB : 0;
+  for (uint64_t it = iters; it-- > 0;) {  // backwards: see the head of the file
+    const uint64_t i = b0 + it * TB + threadIdx.x;
+    unsigned long long key = EMPTY;
+    unsigned long long v[4] = {0, 0, 0, 0};
+    bool kept = false;
+    if (i < b1) {
+      const uint32_t q = q_id[i], t = t_id[i];
+      const uint32_t gq = q < n_seq ? seq_genome[q] : NONE32, gt = t < n_seq ? seq_genome[t] : NONE32;
+      if (gq >= n_genome || gt >= n_genome) {
+        bad = true;
+      } else {
+        const uint32_t len = q_end[i] - q_start[i], m = matches[i];
+        kept = status && status[i] != 0;
+        const int cls = q == t ? S_SELF : gq != gt ? S_INTER_GENOME : S_INTER_CHR;  // the precedence of :140-152
+        const uint32_t vq = 2u * (uint32_t)i + 1u, vt = vq + 1u;
+        acc[0][S_MAPPINGS] += 1;
+        acc[0][S_BASES] += len;
+        acc[0][S_MATCHES] += m;
+        acc[0][S_SELF] += cls == S_SELF;  // (no indexing by cls: the counters stay in registers)
+        acc[0][S_INTER_GENOME] += cls == S_INTER_GENOME;
+        acc[0][S_INTER_CHR] += cls == S_INTER_CHR;
+        offer_last(&seq_last[q], vq);
+        offer_last(&seq_last[t], vt);
+        if (kept) {
+          acc[1][S_MAPPINGS] += 1;
+          acc[1][S_BASES] += len;
+          acc[1][S_MATCHES] += m;
+          acc[1][S_SELF] += cls == S_SELF;
+          acc[1][S_INTER_GENOME] += cls == S_INTER_GENOME;
+          acc[1][S_INTER_CHR] += cls == S_INTER_CHR;
+          offer_last(&seq_last[(size_t)n_seq + q], vq);
+          offer_last(&seq_last[(size_t)n_seq + t], vt);
+        }
+        if (cls == S_INTER_GENOME) {
+          key = (unsigned long long)gq * n_genome + gt;
+          v[0] = len;
+          v[1] = m;
+          v[2] = kept ? len : 0;
+          v[3] = kept ? m : 0;
+        }
+      }
+    }
+    // runs of one genome pair along the lanes: summed towards the run's first lane
+    const unsigned long long before = __shfl_up(key, 1);
+    const bool head = lane == 0 || key != before;
+    const uint64_t heads = __ballot(head), keptmask = __ballot(kept);
+    if (__ballot(key != EMPTY) == 0) continue;  // wavefront-uniform
+    const int end = run_end(heads, lane);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned long long o = __shfl_down(v[j], d);
+        if (lane + d < end) v[j] += o;
+      }
+    }
+    if (head && key != EMPTY) {
+      const uint64_t kf = keptmask & lane_range(lane, end);
+      const uint32_t f_all = (uint32_t)i, f_kept = kf ? (uint32_t)(i - lane + __builtin_ctzll(kf)) : NONE32;
+      uint32_t h = hash32(key) & (LSLOTS - 1);
+      bool placed = false;
+      for (int p = 0; p < LPROBES && !placed; ++p) {
+        unsigned long long k = l_key[h];
+        if (k == EMPTY) {
+          k = atomicCAS(&l_key[h], EMPTY, key);
+          if (k == EMPTY) k = key;
+        }
+        if (k == key) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (v[j]) atomicAdd(&l_sum[h][j], v[j]);
+          atomicMin(&l_first[h][0], f_all);
+          if (f_kept != NONE32) atomicMin(&l_first[h][1], f_kept);
+          placed = true;
+        }
+        h = (h + 1) & (LSLOTS - 1);
+      }
+      if (!placed) stat_add(T, key, v, f_all, f_kept);  // more pairs in this share than the LDS table takes (shuffled input)
+    }
+  }
+  if (bad) l_bad = 1;
+  __syncthreads();
+  for (int s = threadIdx.x; s < LSLOTS; s += TB)
+    if (l_key[s] != EMPTY) stat_add(T, l_key[s], l_sum[s], l_first[s][0], l_first[s][1]);
+#pragma unroll
+  for (int k = 0; k < 2 * S_COUNT; ++k) {
+    const unsigned long long s = wave_sum(acc[k / S_COUNT][k % S_COUNT]);
+    if (lane == 0) l_red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * S_COUNT) {
+    unsigned long long s = 0;
+    for (int w = 0; w < WAVES; ++w) s += l_red[w][threadIdx.x];
+    if (s) atomicAdd(&scalars[threadIdx.x], s);
+  }
+  if (threadIdx.x == 0 && l_bad) atomicOr(&scalars[D_BAD], 1ull);
+}
+
+// ---- the occupied genome pairs as lists ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TB) void alnstats_collect_kernel(StatTable T, uint64_t cap, PairOut* __restrict__ out_all, PairOut* __restrict__ out_kept,
+                                                              unsigned long long* __restrict__ scalars) {
+  const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool in = s < T.slots;
+  const uint32_t f_all = in ? T.first[s * 2] : NONE32, f_kept = in ? T.first[s * 2 + 1] : NONE32;
+  const unsigned long long key = !in ? 0 : T.keys ? T.keys[s] : s;
+  // one atomic per wavefront and list: the lanes that hold an entry take consecutive places
+  auto place = [&](bool have, unsigned long long* counter) -> unsigned long long {
+    const uint64_t m = __ballot(have);
+    if (!m) return 0;
+    unsigned long long base = 0;
+    if (lane == __builtin_ctzll(m)) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = __shfl(base, __builtin_ctzll(m));
+    return base + __popcll(m & ((1ull << lane) - 1ull));
+  };
+  const unsigned long long a = place(f_all != NONE32, &scalars[D_LISTED]);
+  if (f_all != NONE32 && a < cap) out_all[a] = PairOut{key, T.sums[s * 4], T.sums[s * 4 + 1], f_all};
+  const unsigned long long k = place(f_kept != NONE32, &scalars[D_LISTED + 1]);
+  if (f_kept != NONE32 && k < cap) out_kept[k] = PairOut{key, T.sums[s * 4 + 2], T.sums[s * 4 + 3], f_kept};
+}
+
+uint64_t pow2_at_least(uint64_t v) {
+  uint64_t c = 1024;
+  while (c < v) c <<= 1;
+  return c;
+}
+
+struct DevCols {
+  const uint32_t *q_id, *t_id, *q_start, *q_end, *matches, *seq_genome;
+  const uint8_t* status;
+};
+
+// inside an arena frame
+int alnstats_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_alnstats_result* all,
+                    swg_alnstats_result* kept) {
+  hipStream_t st = ctx->stream;
+  unsigned long long* scalars = swg_alloc<unsigned long long>(ctx, D_TOTAL);
+  uint32_t* seq_last = swg_alloc<uint32_t>(ctx, 2 * (size_t)n_seq);
+  // distinct (q_id, t_id): at most min(n, n_seq^2) keys in twice the slots
+  const uint64_t seq_pairs_max = (uint64_t)n_seq * n_seq < n ? (uint64_t)n_seq * n_seq : n;
+  const uint64_t set_cap = pow2_at_least(2 * seq_pairs_max);
+  unsigned long long* set_keys = swg_alloc<unsigned long long>(ctx, set_cap);
+  SWG_CHECK_ARENA(ctx);
+  SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
+  SWG_HIP(ctx, hipMemsetAsync(seq_last, 0, 2 * (size_t)n_seq * sizeof(uint32_t), st));
+  SWG_HIP(ctx, hipMemsetAsync(set_keys, 0xff, set_cap * sizeof(unsigned long long), st));
+  const uint64_t tiles = (n + TB - 1) / TB;
+  const uint64_t max_groups = (uint64_t)ctx->num_cu * 8;
+  {
+    const unsigned grid = (unsigned)(tiles < max_groups ? tiles : max_groups);
+    SWG_LAUNCH(ctx, "alnstats_seqpair", alnstats_seqpair_kernel<<<grid, TB, 0, st>>>(n, d.q_id, d.t_id, d.status, n_seq, set_keys,
+                                                                                       (uint32_t)(set_cap - 1), scalars));
+    SWG_KERNEL_CHECK(ctx);
+  }
+  uint64_t distinct[2];
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars) + D_DISTINCT, distinct, 2));
+  // genome pairs that occur <= distinct sequence pairs
+  const uint64_t g2 = (uint64_t)G * G;
+  const uint64_t pairs_max = g2 < distinct[0] ? g2 : distinct[0];
+  StatTable T{};
+  if (g2 <= DENSE_LIMIT) {
+    T.slots = g2;
+  } else {
+    T.slots = pow2_at_least(2 * pairs_max);
+    T.mask = (uint32_t)(T.slots - 1);
+    T.keys = swg_alloc<unsigned long long>(ctx, T.slots);
+  }
+  T.sums = swg_alloc<unsigned long long>(ctx, T.slots * 4);
+  T.first = swg_alloc<uint32_t>(ctx, T.slots * 2);
+  const uint64_t cap = pairs_max ? pairs_max : 1;
+  PairOut* out_all = swg_alloc<PairOut>(ctx, cap);
+  PairOut* out_kept = swg_alloc<PairOut>(ctx, d.status ? cap : 1);
+  SWG_CHECK_ARENA(ctx);
+  if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
+  SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * 4 * sizeof(unsigned long long), st));
+  SWG_HIP(ctx, hipMemsetAsync(T.first, 0xff, T.slots * 2 * sizeof(uint32_t), st));
+  {
+    const uint64_t groups = tiles < max_groups ? tiles : max_groups;
+    const uint64_t per_group = (tiles + groups - 1) / groups * TB;
+    const unsigned grid = (unsigned)((n + per_group - 1) / per_group);
+    SWG_LAUNCH(ctx, "alnstats_reduce", alnstats_reduce_kernel<<<grid, TB, 0, st>>>(n, per_group, d.q_id, d.t_id, d.q_start, d.q_end, d.matches,
+                                                                                     d.status, d.seq_genome, n_seq, G, T, seq_last, scalars));
+    SWG_KERNEL_CHECK(ctx);
+  }
+  SWG_LAUNCH(ctx, "alnstats_collect",
+             alnstats_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, cap, out_all, out_kept, scalars));
+  SWG_KERNEL_CHECK(ctx);
+  uint64_t h[D_TOTAL];
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_TOTAL));
+  if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "alnstats: a sequence id >= n_seq or a genome id >= n_genome");
+  if (h[D_LISTED] > cap || h[D_LISTED + 1] > cap)
+    return swg_set_error(ctx, SWG_ERR_HIP, "alnstats: internal: %llu genome pairs listed, %llu expected at most",
+                         (unsigned long long)h[D_LISTED], (unsigned long long)cap);
+  std::vector<uint32_t> last((size_t)2 * n_seq);
+  std::vector<PairOut> list[2];
+  list[0].resize(h[D_LISTED]);
+  list[1].resize(d.status ? h[D_LISTED + 1] : 0);
+  SWG_HIP(ctx, hipMemcpyAsync(last.data(), seq_last, last.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (!list[0].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[0].data(), out_all, list[0].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+  if (!list[1].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[1].data(), out_kept, list[1].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+  SWG_HIP(ctx, hipStreamSynchronize(st));
+  swg_alnstats_result* res[2] = {all, d.status ? kept : nullptr};
+  for (int s = 0; s < 2; ++s) {
+    swg_alnstats_result* r = res[s];
+    if (!r) continue;
+    const uint64_t* c = h + s * S_COUNT;
+    r->total_mappings = c[S_MAPPINGS];
+    r->total_bases = c[S_BASES];
+    r->total_matches = c[S_MATCHES];
+    r->self_mappings = c[S_SELF];
+    r->inter_genome = c[S_INTER_GENOME];
+    r->inter_chromosomal = c[S_INTER_CHR];
+    r->chr_pair_count = distinct[s];
+    std::sort(list[s].begin(), list[s].end(), [](const PairOut& a, const PairOut& b) { return a.first < b.first; });
+    r->pairs.resize(list[s].size());
+    for (size_t k = 0; k < list[s].size(); ++k) {
+      const PairOut& o = list[s][k];
+      r->pairs[k] = swg_alnstats_pair_counts{(uint32_t)(o.key / G), (uint32_t)(o.key % G), o.bases, o.matches, o.first};
+    }
+    r->seq_last.resize(n_seq);
+    for (uint32_t q = 0; q < n_seq; ++q) {
+      const uint32_t v = last[(size_t)s * n_seq + q];
+      r->seq_last[q] = v ? (uint64_t)v - 1 : UINT64_MAX;
+    }
+  }
+  return SWG_OK;
+}
+
+void clear_result(swg_alnstats_result* r, uint32_t n_seq) {
+  if (!r) return;
+  *r = swg_alnstats_result{};
+  r->seq_last.assign(n_seq, UINT64_MAX);
+}
+
+int hand_over(swg_ctx* ctx, const swg_alnstats_result& r, swg_alnstats_counts* c) {
+  (void)ctx;
+  if (!c) return SWG_OK;
+  c->total_mappings = r.total_mappings;
+  c->total_bases = r.total_bases;
+  c->total_matches = r.total_matches;
+  c->self_mappings = r.self_mappings;
+  c->inter_chromosomal = r.inter_chromosomal;
+  c->inter_genome = r.inter_genome;
+  c->chr_pair_count = r.chr_pair_count;
+  c->n_pairs = r.pairs.size();
+  if (c->pairs && c->n_pairs <= c->pair_capacity) std::copy(r.pairs.begin(), r.pairs.end(), c->pairs);
+  if (c->seq_last) std::copy(r.seq_last.begin(), r.seq_last.end(), c->seq_last);
+  return SWG_OK;
+}
+
+int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                swg_alnstats_counts* all, swg_alnstats_counts* kept) {
+  if (!ctx) return SWG_ERR_INVALID;
+  try {
+    swg_alnstats_result ra, rk;
+    SWG_TRY(swg_alnstats_run(ctx, rec, on_device, seq_genome, n_genome, status, all ? &ra : nullptr, kept && status ? &rk : nullptr));
+    SWG_TRY(hand_over(ctx, ra, all));
+    if (status) SWG_TRY(hand_over(ctx, rk, kept));
+    return SWG_OK;
+  } catch (const std::bad_alloc&) {
+    return swg_set_error(ctx, SWG_ERR_OOM, "out of host memory");
+  }
+}
+
+}  // namespace
+
+int swg_alnstats_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome,
+                     const uint8_t* status, swg_alnstats_result* all, swg_alnstats_result* kept) {
+  if (!ctx) return SWG_ERR_INVALID;
+  if (!rec) return swg_set_error(ctx, SWG_ERR_INVALID, "alnstats: NULL records");
+  const uint64_t n = rec->n;
+  const uint32_t n_seq = rec->n_seq;
+  clear_result(all, n_seq);
+  clear_result(kept, n_seq);
+  if (n == 0) return SWG_OK;
+  if (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->matches || !seq_genome)
+    return swg_set_error(ctx, SWG_ERR_INVALID, "alnstats: NULL column (q_id, t_id, q_start, q_end, matches and seq_genome are read)");
+  if (n_seq == 0 || n_genome == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "alnstats: records without sequences or genomes");
+  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "alnstats: 2^31 records or more in one call");
+  if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "alnstats: more than 2^31 sequences");
+  SWG_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (ctx->arena_cap == 0) {
+    const size_t want = (size_t)n * 64 + (size_t(8) << 20), budget = swg_arena_budget(ctx);
+    SWG_TRY(swg_arena_reserve(ctx, want < budget ? want : budget));
+  }
+  return swg_run_with_arena(ctx, [&]() -> int {
+    DevCols d{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches, seq_genome, status};
+    if (!on_device) {
+      uint32_t* col[5];
+      for (auto& c : col) c = swg_alloc<uint32_t>(ctx, n);
+      uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
+      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
+      SWG_CHECK_ARENA(ctx);
+      const uint32_t* src[5] = {rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches};
+      for (int k = 0; k < 5; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
+      d = DevCols{col[0], col[1], col[2], col[3], col[4], g, s8};
+    }
+    return alnstats_device(ctx, n, n_seq, n_genome, d, all, kept);
+  });
+}
+
+extern "C" int swg_alnstats_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                    const uint8_t* status, swg_alnstats_counts* all, swg_alnstats_counts* kept) {
+  return records_abi(ctx, rec, false, seq_genome, n_genome, status, all, kept);
+}
+
+extern "C" int swg_alnstats_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                           const uint8_t* status, swg_alnstats_counts* all, swg_alnstats_counts* kept) {
+  return records_abi(ctx, rec, true, seq_genome, n_genome, status, all, kept);
+}
+
+// Statistics of an open PAF: records and genome map from the handle, the integers from the device, the sequence sizes and the
+// handles from the handle's text (host/paf_io.cpp).  Errors: swg_alnstats_last_error().
+extern "C" int swg_paf_alnstats(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, swg_alnstats** all_out, swg_alnstats** kept_out) {
+  if (all_out) *all_out = nullptr;
+  if (kept_out) *kept_out = nullptr;
+  if (!p) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_alnstats: NULL handle");
+  const uint64_t n = swg_paf_records(p)->n;
+  if (n && !ctx) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_alnstats: NULL context");
+  try {
+    swg_records rec;
+    std::vector<uint32_t> col10;
+    const uint32_t* seq_genome = nullptr;
+    SWG_TRY(swg_paf_stats_prepare(p, &rec, &col10, &seq_genome));
+    swg_alnstats_result res[2];
+    if (n) {
+      const int rc = swg_alnstats_run(ctx, &rec, false, seq_genome, rec.n_genome_last, status, &res[0], status ? &res[1] : nullptr);
+      if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+    }
+    swg_alnstats** const outs[2] = {all_out, status ? kept_out : nullptr};
+    return swg_paf_stats_finish(p, res, outs);
+  } catch (const std::bad_alloc&) {
+    return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+  }
+}
