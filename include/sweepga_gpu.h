@@ -380,6 +380,73 @@ int swg_paf_tree_filter(const char* text, uint64_t len, uint64_t k_nearest, uint
                         char** out_text, uint64_t* out_len);
 void swg_free(void* p);
 
+/* ---- tree sparsification on RECORDS: a keep flag per record from the device, and the filter on the kept subset -------------
+ * The same selection as swg_paf_tree_filter (one implementation serves both) over record columns instead of text, for callers
+ * whose records are columns already: an open handle, device-resident records, a .1aln handle (which keeps no text).
+ *
+ * swg_tree_select_pairs: steps 2-3 alone, host code, no GPU.  n_pairs unordered pairs of DIFFERENT genomes (pair_a[k], pair_b[k]:
+ * genome ids in either order, every pair listed once) with their sums; genome_prefix[n_genome] are distinct NUL-terminated
+ * strings (they decide the canonical order of a pair, the tie order and the hash).  selected[k] = 1 when pair k survives.
+ * A sum of 2^53 or more: SWG_ERR_RANGE (the reference accumulates in f64; below 2^53 integer sums are the same numbers). */
+int swg_tree_select_pairs(uint32_t n_genome, const char* const* genome_prefix, uint64_t n_pairs, const uint32_t* pair_a,
+                          const uint32_t* pair_b, const uint64_t* sum_matches, const uint64_t* sum_block_len, uint64_t k_nearest,
+                          uint64_t k_farthest, double random_fraction, uint8_t* selected);
+/* keep[i] = 1 when record i survives the sparsification, 0 otherwise (a record whose two genomes are equal never survives,
+ * src/tree_filter.rs:183-186); *n_kept (optional) their number.  Read: q_id, t_id, matches, block_len of rec, and
+ * seq_genome[rec->n_seq] (genome ids < n_genome; the reference's rule is the two-part prefix, i.e. rec->seq_genome_two of a
+ * handle, but any partition works).  The per-pair sums are integer reductions on the device (kernels in csrc/swg_sparsify.hip),
+ * the selection runs on the host over (pair sums, genome_prefix), the mask is written by the device.  Host pointers for the four
+ * columns, seq_genome and keep (staged: 17 bytes per record); genome_prefix are host strings in both entries -- the device never
+ * sees a string.  n >= 2^31: SWG_ERR_RANGE.  A pair's sum >= 2^53: SWG_ERR_RANGE.  An id out of range: SWG_ERR_INVALID.  Scratch
+ * (the pair table: 24 bytes per genome pair when n_genome^2 <= 2^20, else up to 128 bytes per record) comes from the context's
+ * arena: SWG_ERR_OOM when the memory limit does not hold it. */
+int swg_tree_select_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                            const char* const* genome_prefix, uint64_t k_nearest, uint64_t k_farthest, double random_fraction,
+                            uint8_t* keep, uint64_t* n_kept);
+/* The same with the four columns, seq_genome and keep in device memory of ctx's GPU; no record column is copied to the host. */
+int swg_tree_select_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                   const char* const* genome_prefix, uint64_t k_nearest, uint64_t k_farthest, double random_fraction,
+                                   uint8_t* keep, uint64_t* n_kept);
+/* swg_filter_device on the records with keep[i] != 0, answered in the caller's record indices: the columns that are non-NULL in rec
+ * are compacted in input order on the device, the unchanged swg_filter_device runs on them, and the results are scattered back.
+ * Contract: for kept records, status and chain number are exactly what swg_filter_device gives on the compacted columns; dropped
+ * records get 0 / 0; every entry of status_out[n] and chain_out[n] is written.  keep == NULL is swg_filter_device.  Sequence ids
+ * are NOT renumbered: the compacted columns keep the ids (and the two sequence -> genome tables) of the full input.  The
+ * reference has no ids -- it keys by names and orders by record position -- and no answer here depends on the order of ids
+ * (DESIGN.md section 12), so this equals filtering the sparsified text parsed afresh.  n >= 2^31: SWG_ERR_RANGE.  The compacted
+ * columns live in a block of the context beside the arena; under a memory limit the filter call inside runs under what the limit
+ * leaves beside them.  stats (optional): those of the inner call, n_in = rec->n. */
+int swg_filter_subset_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* keep, const swg_config* cfg, uint8_t* status_out,
+                             uint32_t* chain_out, swg_stats* stats);
+/* Host pointers: compacted by host threads, then the unchanged swg_filter (streamed path included) / swg_filter_multi. */
+int swg_filter_subset(swg_ctx* ctx, const swg_records* rec, const uint8_t* keep, const swg_config* cfg, uint8_t* status_out,
+                      uint32_t* chain_out, swg_stats* stats);
+int swg_filter_subset_multi(swg_ctx* const* ctxs, int n_ctx, const swg_records* rec, const uint8_t* keep, const swg_config* cfg,
+                            uint8_t* status_out, uint32_t* chain_out, swg_stats* stats);
+/* The two-part-prefix genome table of a handle (src/tree_filter.rs:15-24: the first two '#' parts + '#', the whole name without a
+ * '#'): prefix of genome id g < swg_*_num_genomes_two() under records->seq_genome_two, owned by the handle. */
+uint32_t swg_paf_num_genomes_two(const swg_paf* p);
+const char* swg_paf_genome_two_prefix(const swg_paf* p, uint32_t g);
+uint32_t swg_aln_num_genomes_two(const swg_aln* a);
+const char* swg_aln_genome_two_prefix(const swg_aln* a, uint32_t g);
+/* The mask of an open PAF: keep[n] on the host, what swg_paf_tree_filter keeps of the handle's text, record for record.
+ * *route (optional) says how it was made: SWG_TREE_ROUTE_DEVICE from the handle's columns (swg_tree_select_records), or
+ * SWG_TREE_ROUTE_TEXT by the text pass over the text the handle keeps -- same answer, slower -- for a handle whose columns are not
+ * what that pass reads (swg_paf_tree_needs_text() == 1): a cg:Z: total replaced column 10 by another value; column 10 or 11 did
+ * not parse; a '#'-led line with 11 fields (a record for the handle, a comment for the tree pass); a file with values >= 2^32 (64-bit
+ * columns, rebased); and, found only when summing, a pair's sum >= 2^53.  ctx may be NULL for a handle without records or one
+ * that takes the text route.  `threads` is reserved (both routes ignore it). */
+#define SWG_TREE_ROUTE_DEVICE 0
+#define SWG_TREE_ROUTE_TEXT 1
+int swg_paf_tree_needs_text(const swg_paf* p);
+int swg_paf_tree_select(swg_ctx* ctx, const swg_paf* p, uint64_t k_nearest, uint64_t k_farthest, double random_fraction, int threads,
+                        uint8_t* keep, uint64_t* n_kept, int* route);
+/* The twin for a .1aln record handle: apply_tree_filter_to_1aln (src/tree_filter.rs:286-…) sums aln.matches over
+ * aln.query_end - aln.query_start (:314-317) -- not over the record's block length, which is query span + target span -- so that
+ * is the length summed here.  No text, so no other route: a pair's sum >= 2^53 is SWG_ERR_RANGE. */
+int swg_aln_tree_select(swg_ctx* ctx, const swg_aln* a, uint64_t k_nearest, uint64_t k_farthest, double random_fraction,
+                        uint8_t* keep, uint64_t* n_kept);
+
 /* ---- alnstats (src/bin/alnstats.rs): statistics of a PAF and the comparison of two ------------------------------------
  * parse_paf (:103-164) over host threads: lines with fewer than 11 fields are skipped; a line whose columns 2, 3, 4, 7,
  * 10 or 11 do not parse as u64 ends the run as in the reference (SWG_ERR_INVALID, "Invalid query length" ... in

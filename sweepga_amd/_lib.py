@@ -30,7 +30,11 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_alnstats_records", "swg_alnstats_records_device", "swg_paf_alnstats",
            "swg_fasta_open", "swg_fasta_close", "swg_fasta_num_records", "swg_fasta_name", "swg_fasta_file_index",
            "swg_fasta_offsets", "swg_fasta_bases", "swg_fasta_last_error", "swg_mash_sketch", "swg_mash_merge",
-           "swg_mash_distances", "swg_mash_random_pairs", "swg_select_pairs", "swg_joblist"]
+           "swg_mash_distances", "swg_mash_random_pairs", "swg_select_pairs", "swg_joblist",
+           "swg_tree_select_pairs", "swg_tree_select_records", "swg_tree_select_records_device", "swg_filter_subset",
+           "swg_filter_subset_device", "swg_filter_subset_multi", "swg_paf_tree_select", "swg_paf_tree_needs_text",
+           "swg_aln_tree_select", "swg_paf_num_genomes_two", "swg_paf_genome_two_prefix", "swg_aln_num_genomes_two",
+           "swg_aln_genome_two_prefix"]
 
 
 class SwgError(RuntimeError):
@@ -264,6 +268,36 @@ def load():
                       C.POINTER(SwgAlnstatsCounts)]
     lib.swg_paf_alnstats.restype = C.c_int
     lib.swg_paf_alnstats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.swg_tree_select_pairs.restype = C.c_int
+    lib.swg_tree_select_pairs.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.c_uint64, C.c_double, C.c_void_p]
+    for name in ("swg_tree_select_records", "swg_tree_select_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint64,
+                      C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
+    for name in ("swg_filter_subset", "swg_filter_subset_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.POINTER(SwgConfig), C.c_void_p, C.c_void_p, C.POINTER(SwgStats)]
+    lib.swg_filter_subset_multi.restype = C.c_int
+    lib.swg_filter_subset_multi.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(SwgRecords), C.c_void_p, C.POINTER(SwgConfig),
+                                            C.c_void_p, C.c_void_p, C.POINTER(SwgStats)]
+    lib.swg_paf_tree_select.restype = C.c_int
+    lib.swg_paf_tree_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_int, C.c_void_p,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    lib.swg_paf_tree_needs_text.restype = C.c_int
+    lib.swg_paf_tree_needs_text.argtypes = [C.c_void_p]
+    lib.swg_aln_tree_select.restype = C.c_int
+    lib.swg_aln_tree_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
+    for name in ("swg_paf_num_genomes_two", "swg_aln_num_genomes_two"):
+        f = getattr(lib, name)
+        f.restype = C.c_uint32
+        f.argtypes = [C.c_void_p]
+    for name in ("swg_paf_genome_two_prefix", "swg_aln_genome_two_prefix"):
+        f = getattr(lib, name)
+        f.restype = C.c_char_p
+        f.argtypes = [C.c_void_p, C.c_uint32]
     _lib = lib
     return lib
 

@@ -37,6 +37,33 @@ int swg_paf_stats_prepare(const swg_paf* p, swg_records* rec, std::vector<uint32
 int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res /* [2]: ALL, KEPT */, swg_alnstats** const* outs /* [2], NULL = not wanted */);
 int swg_alnstats_error(int code, const char* fmt, ...);  // sets swg_alnstats_last_error()
 extern const char* const SWG_ALNSTATS_FIELD_ERR[6];      // "Invalid query length" ... for columns 2, 3, 4, 7, 10, 11
+
+// ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
+// one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
+// are the same numbers.
+struct swg_tree_pair {
+  uint32_t a, b;
+  double matches, block;
+};
+constexpr uint64_t SWG_TREE_SUM_LIMIT = uint64_t(1) << 53;
+// identity per pair, neighbour ranking (ties: neighbour prefix ascending), SipHash-1-3 random pairs (src/tree_filter.rs:79-160):
+// THE selection, for the text route and the record routes alike
+void swg_tree_select(const std::vector<std::string>& prefix, const std::vector<swg_tree_pair>& pairs, uint64_t k_nearest,
+                     uint64_t k_farthest, double random_fraction, std::vector<uint8_t>* selected);
+// the text route's verdicts as a mask over records whose lines start at rec_off[0 .. n) (ascending) of the same text
+int swg_tree_text_mask(const char* text, uint64_t len, uint64_t k_nearest, uint64_t k_farthest, double random_fraction,
+                       const uint64_t* rec_off, uint64_t n, uint8_t* keep, uint64_t* n_kept);
+// what swg_paf_tree_select / swg_aln_tree_select need of a handle (paf_io.cpp)
+struct swg_tree_handle_view {
+  const swg_records* rec = nullptr;
+  const std::vector<std::string>* prefix_two = nullptr;  // [rec->n_genome_two]
+  bool text_route = false;                               // PAF only: the columns are not what the text route reads
+  const char* text = nullptr;                            // PAF only
+  uint64_t text_len = 0;
+  const uint64_t* rec_off = nullptr;
+};
+void swg_paf_tree_view(const swg_paf* p, swg_tree_handle_view* v);
+void swg_aln_tree_view(const swg_aln* a, swg_tree_handle_view* v);
 #endif
 
 // ---- --joblist (fasta_io.cpp, swg_mash.hip, mash_host.cpp) ----

@@ -329,10 +329,18 @@ std::string prefix_two(std::string_view n) {  // src/plane_sweep_scaffold.rs:13-
   r += '#';
   return r;
 }
-uint32_t genome_table(const std::vector<std::string>& names, std::string (*fn)(std::string_view), std::vector<uint32_t>* out) {
+// prefixes (optional): genome id -> its prefix string, ids in order of first appearance among the sequence ids
+uint32_t genome_table(const std::vector<std::string>& names, std::string (*fn)(std::string_view), std::vector<uint32_t>* out,
+                      std::vector<std::string>* prefixes = nullptr) {
   std::unordered_map<std::string, uint32_t> g;
   out->assign(names.empty() ? 1 : names.size(), 0);
-  for (size_t i = 0; i < names.size(); ++i) (*out)[i] = g.emplace(fn(names[i]), (uint32_t)g.size()).first->second;
+  if (prefixes) prefixes->clear();
+  for (size_t i = 0; i < names.size(); ++i) {
+    const auto ins = g.emplace(fn(names[i]), (uint32_t)g.size());
+    if (ins.second && prefixes) prefixes->push_back(ins.first->first);
+    (*out)[i] = ins.first->second;
+  }
+  if (g.empty() && prefixes) prefixes->emplace_back();
   return g.empty() ? 1u : (uint32_t)g.size();
 }
 
@@ -383,6 +391,8 @@ struct Slice {
   bool wide = false;             // met a coordinate / matches / block length >= 2^32
   bool custom_identity = false;  // a record whose identity is not matches / max(block length, 1) (a dv:f: tag had the last word)
   bool stats_irregular = false;  // a record whose column 3, 4, 10 or 11 did not parse, or whose cg:Z: tag replaced column 10 by another value
+  bool tree_irregular = false;   // a record whose matches / block length are not what the tree sparsification's text pass reads from its
+                                 // line (column 10 or 11 did not parse, a cg:Z: total replaced column 10), or that is no alignment there ('#'-led)
 };
 
 }  // namespace
@@ -400,8 +410,10 @@ struct swg_paf {
   std::vector<uint64_t> rec_off_q, rec_off_t;  // ... off each RECORD's query / target coordinates (rebased per sweep segment)
   std::vector<std::string> names;
   std::vector<uint32_t> g_last, g_two;
+  std::vector<std::string> g_two_prefix;  // genome id under the two-part rule -> prefix (src/tree_filter.rs:15-24 = plane_sweep_scaffold.rs:13-22)
   swg_records rec{};
   bool identity_derived = false;     // every record's identity is matches / max(block length, 1)
+  bool tree_irregular = false;       // swg_paf_tree_select takes the text route: see Slice::tree_irregular; also a file with 64-bit values
   bool stats_irregular = false;      // the columns are not what alnstats reads from some line (swg_paf_alnstats checks the text first)
   double load_ms = 0, parse_ms = 0;
   // ANI view (filled by swg_paf_ani_input)
@@ -525,6 +537,7 @@ int parse_text(swg_paf* p, int threads) {
         uint64_t v;
         if (parse_u64(f[i], (size_t)(f[i + 1] - 1 - f[i]), &v)) return v;
         if (i != 7 && i != 8) s.stats_irregular = true;  // alnstats stops at such a line (it reads columns 3, 4, 10, 11; not 8, 9)
+        if (i == 9 || i == 10) s.tree_irregular = true;
         return d;
       };
       auto narrow = [&](uint64_t v) {
@@ -546,7 +559,7 @@ int parse_text(swg_paf* p, int threads) {
           } else if (tg[0] == 'c' && tg[1] == 'g' && tg[3] == 'Z') {
             uint64_t cm;
             if (cigar_eq_total(tg + 5, tl - 5, &cm) && cm > 0) {
-              if (cm != matches) s.stats_irregular = true;  // (compared with the value before it: column 10 or an equal override)
+              if (cm != matches) s.stats_irregular = s.tree_irregular = true;  // (compared with the value before it: column 10 or an equal override)
               matches = cm;
               identity = (double)cm / denom;
             }
@@ -554,6 +567,7 @@ int parse_text(swg_paf* p, int threads) {
         }
         tg = te + 1;
       }
+      if (*b == '#') s.tree_irregular = true;  // (a record has 11 fields, so b < e) a comment line to the tree pass, a record here
       p->q_id[k] = s.names.get(fld(0), 0);
       p->t_id[k] = s.names.get(fld(5), 1);
       if (wide) {
@@ -592,8 +606,10 @@ int parse_text(swg_paf* p, int threads) {
     wide = wide || s.wide;
     if (s.custom_identity) p->identity_derived = false;
     if (s.stats_irregular) p->stats_irregular = true;
+    if (s.tree_irregular) p->tree_irregular = true;
   }
   if (wide) {
+    p->tree_irregular = true;  // the new route is for the plain 32-bit layout
     for (auto& w : p->wide) w.alloc(cap);
     pass2(true);
     lap("pass 2 again (64-bit columns)");
@@ -655,7 +671,7 @@ int parse_text(swg_paf* p, int threads) {
   });
   lap("name merge + remap");
   const uint32_t n_last = genome_table(p->names, prefix_last, &p->g_last);
-  const uint32_t n_two = genome_table(p->names, prefix_two, &p->g_two);
+  const uint32_t n_two = genome_table(p->names, prefix_two, &p->g_two, &p->g_two_prefix);
   if (wide) {
     const uint32_t n_seq = (uint32_t)(p->names.empty() ? 1 : p->names.size());
     p->seq_offset.assign(n_seq, 0);
@@ -857,6 +873,11 @@ const uint64_t* swg_paf_record_offsets(const swg_paf* p, int axis) {
 }
 uint64_t swg_paf_num_lines(const swg_paf* p) { return p ? p->n_lines : 0; }
 const uint64_t* swg_paf_ranks(const swg_paf* p) { return p ? p->rank.data() : nullptr; }
+uint32_t swg_paf_num_genomes_two(const swg_paf* p) { return p ? (uint32_t)p->g_two_prefix.size() : 0; }
+const char* swg_paf_genome_two_prefix(const swg_paf* p, uint32_t g) {
+  return (p && g < p->g_two_prefix.size()) ? p->g_two_prefix[g].c_str() : nullptr;
+}
+int swg_paf_tree_needs_text(const swg_paf* p) { return p && p->tree_irregular ? 1 : 0; }
 uint32_t swg_paf_num_sequences(const swg_paf* p) { return p ? (uint32_t)p->names.size() : 0; }
 const char* swg_paf_sequence_name(const swg_paf* p, uint32_t id) {
   return (p && id < p->names.size()) ? p->names[id].c_str() : nullptr;
@@ -1314,6 +1335,7 @@ struct swg_aln {
   std::vector<uint8_t> strand;
   std::vector<std::string> names;
   std::vector<uint32_t> g_last, g_two;
+  std::vector<std::string> g_two_prefix;  // genome id under the two-part rule -> prefix
   std::vector<uint64_t> seq_offset;  // what rebasing took off each sequence's coordinates (empty: nothing, or per record:)
   std::vector<uint64_t> rec_off_q, rec_off_t;  // ... off each RECORD's query / target coordinates (rebased per sweep segment)
   swg_records rec{};
@@ -1444,7 +1466,7 @@ int swg_aln_open(const swg_aln_input* in, swg_aln** out) {
       }
     }
     const uint32_t n_last = genome_table(a->names, prefix_last, &a->g_last);
-    const uint32_t n_two = genome_table(a->names, prefix_two, &a->g_two);
+    const uint32_t n_two = genome_table(a->names, prefix_two, &a->g_two, &a->g_two_prefix);
     swg_records& r = a->rec;
     r.n = n;
     r.q_id = a->q_id.data();
@@ -1476,9 +1498,26 @@ const uint64_t* swg_aln_record_offsets(const swg_aln* a, int axis) {
   if (!a || a->rec_off_q.empty()) return nullptr;
   return axis ? a->rec_off_t.data() : a->rec_off_q.data();
 }
+uint32_t swg_aln_num_genomes_two(const swg_aln* a) { return a ? (uint32_t)a->g_two_prefix.size() : 0; }
+const char* swg_aln_genome_two_prefix(const swg_aln* a, uint32_t g) {
+  return (a && g < a->g_two_prefix.size()) ? a->g_two_prefix[g].c_str() : nullptr;
+}
 uint32_t swg_aln_num_sequences(const swg_aln* a) { return a ? (uint32_t)a->names.size() : 0; }
 const char* swg_aln_sequence_name(const swg_aln* a, uint32_t id) {
   return (a && id < a->names.size()) ? a->names[id].c_str() : nullptr;
 }
 
 }  // extern "C"
+
+void swg_paf_tree_view(const swg_paf* p, swg_tree_handle_view* v) {
+  v->rec = &p->rec;
+  v->prefix_two = &p->g_two_prefix;
+  v->text_route = p->tree_irregular;
+  v->text = p->text.data;
+  v->text_len = p->text.len;
+  v->rec_off = p->rec_off.data();
+}
+void swg_aln_tree_view(const swg_aln* a, swg_tree_handle_view* v) {
+  v->rec = &a->rec;
+  v->prefix_two = &a->g_two_prefix;
+}

@@ -508,25 +508,24 @@ int main(int argc, char** argv) {
   if (need_ani) set_identities(ani_percentile);
   if (need_ani && !quiet) std::fprintf(stderr, "[sweepga-gpu] ANI pre-pass (%s): median %.6f in %.1f ms\n", ani_method_s.c_str(), ani_percentile, ani_ms);
 
-  // ---- tree sparsification of the input (src/main.rs:3640-3688): the filter then runs on the surviving lines, whose ranks
-  // are their positions in the sparsified text (the reference filters the temporary tree-filtered file)
-  swg_alnstats* stats_before = nullptr;  // --stats: the input's statistics when the filter does not see the whole input
+  // ---- tree sparsification of the input (src/main.rs:3640-3688).  The reference filters a temporary tree-filtered file; here the
+  // sparsification is a keep flag per record of the handle that is already open, the filter runs on the kept subset and answers
+  // in the handle's record indices, and the writer takes the full-length status: no second text buffer, no second parse.  A
+  // dropped record has status 0 and is not written, so the output is the filter's output on the sparsified text.
+  std::vector<uint8_t> tree_keep;
+  const auto t1c = clk::now();
   if (!tree_sparsify.empty()) {
-    if (!stats_path.empty() && swg_paf_alnstats(ctx, paf, nullptr, &stats_before, nullptr) != SWG_OK)
-      die(3, std::string("--stats: ") + swg_alnstats_last_error());
-    const char* text;
-    uint64_t len;
-    swg_paf_text(paf, &text, &len);
-    char* kept_text = nullptr;
-    uint64_t kept_len = 0;
-    if (swg_paf_tree_filter(text, len, tree_near, tree_far, tree_rand, &kept_text, &kept_len) != SWG_OK) die(2, "tree sparsification failed");
-    swg_paf_close(paf);
-    paf = nullptr;
-    if (swg_paf_open_buffer(kept_text, kept_len, threads, &paf) != SWG_OK) die(2, swg_paf_last_error());
-    swg_free(kept_text);
-    r = swg_paf_records(paf);
-    n = r->n;
+    tree_keep.resize(n ? n : 1);
+    uint64_t n_tree = 0;
+    int route = SWG_TREE_ROUTE_DEVICE;
+    if (swg_paf_tree_select(ctx, paf, tree_near, tree_far, tree_rand, threads, tree_keep.data(), &n_tree, &route) != SWG_OK)
+      die(2, std::string("tree sparsification failed: ") + (ctx ? swg_last_error(ctx) : ""));
+    if (!quiet)
+      std::fprintf(stderr, "[sweepga-gpu] --sparsify %s: %s, %llu records -> %llu kept by the sparsification, %.1f ms\n", tree_sparsify.c_str(),
+                   route == SWG_TREE_ROUTE_DEVICE ? "device mask" : "text fall-back", (unsigned long long)n, (unsigned long long)n_tree,
+                   std::chrono::duration<double, std::milli>(clk::now() - t1c).count());
   }
+  const uint8_t* const keep_mask = tree_sparsify.empty() ? nullptr : tree_keep.data();
 
   // ---- apply_filters on the GPU
   // result columns: uninitialised storage (the filter writes every entry; zero-filling 0.5 GB on this thread first cost
@@ -557,8 +556,9 @@ int main(int argc, char** argv) {
       std::memset(status.data(), 0xff, n);
       std::memset(chain.data(), 0xff, n * sizeof(uint32_t));
     }
-    const int rc = ctxs.size() > 1 ? swg_filter_multi(ctxs.data(), (int)ctxs.size(), &rr, &cfg, status.data(), chain.data(), &st)
-                                   : swg_filter(ctx, &rr, &cfg, status.data(), chain.data(), &st);
+    // (keep_mask == NULL: swg_filter / swg_filter_multi themselves)
+    const int rc = ctxs.size() > 1 ? swg_filter_subset_multi(ctxs.data(), (int)ctxs.size(), &rr, keep_mask, &cfg, status.data(), chain.data(), &st)
+                                   : swg_filter_subset(ctx, &rr, keep_mask, &cfg, status.data(), chain.data(), &st);
     if (rc != SWG_OK) die(3, std::string("filter failed: ") + swg_last_error(ctx));
     if (poison) {
       for (uint64_t i = 0; i < n; ++i)
@@ -571,15 +571,15 @@ int main(int argc, char** argv) {
   // ---- --stats: before / after from the columns and the status the filter left, ahead of the write
   if (!stats_path.empty()) {
     swg_alnstats *sa = nullptr, *sk = nullptr;
-    if (swg_paf_alnstats(ctx, paf, status.data(), stats_before ? nullptr : &sa, &sk) != SWG_OK) die(3, std::string("--stats: ") + swg_alnstats_last_error());
-    write_stats_report(stats_path, stats_before ? stats_before : sa, sk, input, out_path, stats_detailed);
+    // (with --sparsify too: "before" is the whole input, "after" what is written -- one call on the one handle)
+    if (swg_paf_alnstats(ctx, paf, status.data(), &sa, &sk) != SWG_OK) die(3, std::string("--stats: ") + swg_alnstats_last_error());
+    write_stats_report(stats_path, sa, sk, input, out_path, stats_detailed);
     if (!quiet) {
       const double ms = std::chrono::duration<double, std::milli>(clk::now() - t2).count();
       std::fprintf(stderr, "[sweepga-gpu] --stats: %.1f ms\n", ms);
     }
     swg_alnstats_close(sa);
     swg_alnstats_close(sk);
-    swg_alnstats_close(stats_before);
   }
   const auto t2s = clk::now();
 

@@ -21,18 +21,13 @@
 #include <new>
 
 #include "swg_internal.h"
+#include "swg_pair_table.h"
 #include "host/host_internal.h"
 
 namespace {
 
-constexpr int TB = 256;                    // threads per work-group
-constexpr int WAVES = TB / 64;
-constexpr int LSLOTS = 256;                // LDS genome-pair slots per work-group
-constexpr int LPROBES = 8;                 // ... probed this far, then the run goes to the global table directly
-constexpr uint32_t NONE32 = 0xffffffffu;
-constexpr unsigned long long EMPTY = ~0ull;
+using namespace swg_pair_table;  // TB, LSLOTS, EMPTY, hash32, table_slot, lds_slot, run_end, lane_range, run_sum, wave_sum
 constexpr unsigned long long KEPT_BIT = 1ull << 63;
-constexpr uint64_t DENSE_LIMIT = uint64_t(1) << 20;  // G * G entries of 40 bytes
 enum { S_MAPPINGS = 0, S_BASES, S_MATCHES, S_SELF, S_INTER_GENOME, S_INTER_CHR, S_COUNT };
 // device scalars: [set][S_COUNT], then distinct pairs [2], listed genome pairs [2], bad-id flag
 enum { D_DISTINCT = 2 * S_COUNT, D_LISTED = D_DISTINCT + 2, D_BAD = D_LISTED + 2, D_TOTAL };
@@ -48,20 +43,8 @@ struct PairOut {  // one listed genome pair
   unsigned long long key, bases, matches, first;
 };
 
-__device__ __forceinline__ uint32_t hash32(unsigned long long key) { return (uint32_t)((key * 0x9e3779b97f4a7c15ull) >> 32); }
-
 __device__ __forceinline__ uint64_t stat_slot(const StatTable& t, unsigned long long key) {  // inserts when absent
-  if (!t.keys) return key;
-  uint32_t h = hash32(key) & t.mask;
-  for (;;) {
-    unsigned long long k = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == EMPTY) {
-      k = atomicCAS(&t.keys[h], EMPTY, key);
-      if (k == EMPTY) k = key;
-    }
-    if (k == key) return h;
-    h = (h + 1) & t.mask;  // the table has twice the slots of the keys that can occur: a free one always comes
-  }
+  return t.keys ? table_slot(t.keys, t.mask, key) : key;
 }
 
 __device__ __forceinline__ void stat_add(const StatTable& t, unsigned long long key, const unsigned long long v[4], uint32_t f_all,
@@ -72,22 +55,6 @@ __device__ __forceinline__ void stat_add(const StatTable& t, unsigned long long 
     if (v[j]) atomicAdd(&t.sums[s * 4 + j], v[j]);
   atomicMin(&t.first[s * 2], f_all);
   if (f_kept != NONE32) atomicMin(&t.first[s * 2 + 1], f_kept);
-}
-
-// runs of equal keys along the lanes of a wavefront: `heads` = ballot of "first lane of its run" -> one past the run's last lane
-__device__ __forceinline__ int run_end(uint64_t heads, int lane) {
-  const uint64_t above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-  return above ? __builtin_ctzll(above) : 64;
-}
-__device__ __forceinline__ uint64_t lane_range(int from, int to) {  // bits [from, to), to <= 64
-  const uint64_t upto = to == 64 ? ~0ull : (1ull << to) - 1ull;
-  return upto & ~((1ull << from) - 1ull);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-  return v;
 }
 
 // ---- distinct (q_id, t_id) ---------------------------------------------------------------------------------------------
@@ -217,34 +184,18 @@ __global__ __launch_bounds__(TB) void alnstats_reduce_kernel(uint64_t n, uint64_
     const uint64_t heads = __ballot(head), keptmask = __ballot(kept);
     if (__ballot(key != EMPTY) == 0) continue;  // wavefront-uniform
     const int end = run_end(heads, lane);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned long long o = __shfl_down(v[j], d);
-        if (lane + d < end) v[j] += o;
-      }
-    }
+    run_sum(v, lane, end);
     if (head && key != EMPTY) {
       const uint64_t kf = keptmask & lane_range(lane, end);
       const uint32_t f_all = (uint32_t)i, f_kept = kf ? (uint32_t)(i - lane + __builtin_ctzll(kf)) : NONE32;
-      uint32_t h = hash32(key) & (LSLOTS - 1);
-      bool placed = false;
-      for (int p = 0; p < LPROBES && !placed; ++p) {
-        unsigned long long k = l_key[h];
-        if (k == EMPTY) {
-          k = atomicCAS(&l_key[h], EMPTY, key);
-          if (k == EMPTY) k = key;
-        }
-        if (k == key) {
+      const int h = lds_slot(l_key, key);
+      const bool placed = h >= 0;
+      if (placed) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (v[j]) atomicAdd(&l_sum[h][j], v[j]);
-          atomicMin(&l_first[h][0], f_all);
-          if (f_kept != NONE32) atomicMin(&l_first[h][1], f_kept);
-          placed = true;
-        }
-        h = (h + 1) & (LSLOTS - 1);
+        for (int j = 0; j < 4; ++j)
+          if (v[j]) atomicAdd(&l_sum[h][j], v[j]);
+        atomicMin(&l_first[h][0], f_all);
+        if (f_kept != NONE32) atomicMin(&l_first[h][1], f_kept);
       }
       if (!placed) stat_add(T, key, v, f_all, f_kept);  // more pairs in this share than the LDS table takes (shuffled input)
     }
@@ -288,12 +239,6 @@ __global__ __launch_bounds__(TB) void alnstats_collect_kernel(StatTable T, uint6
   if (f_all != NONE32 && a < cap) out_all[a] = PairOut{key, T.sums[s * 4], T.sums[s * 4 + 1], f_all};
   const unsigned long long k = place(f_kept != NONE32, &scalars[D_LISTED + 1]);
   if (f_kept != NONE32 && k < cap) out_kept[k] = PairOut{key, T.sums[s * 4 + 2], T.sums[s * 4 + 3], f_kept};
-}
-
-uint64_t pow2_at_least(uint64_t v) {
-  uint64_t c = 1024;
-  while (c < v) c <<= 1;
-  return c;
 }
 
 struct DevCols {

@@ -257,6 +257,7 @@ void swg_destroy(swg_ctx* ctx) {
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->io_block) (void)hipFree(ctx->io_block);
   if (ctx->range_block) (void)hipFree(ctx->range_block);
+  if (ctx->subset_block) (void)hipFree(ctx->subset_block);
   std::free(ctx->narrow_host);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
   if (ctx->ring) (void)hipHostFree(ctx->ring);
@@ -287,16 +288,16 @@ int swg_set_memory_limit(swg_ctx* ctx, uint64_t bytes) {
   if (!ctx) return SWG_ERR_INVALID;
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   ctx->mem_limit = bytes;
-  if (bytes && (uint64_t)ctx->arena_cap + ctx->io_cap + ctx->range_cap > bytes) {
+  if (bytes && (uint64_t)ctx->arena_cap + ctx->io_cap + ctx->range_cap + ctx->subset_cap > bytes) {
     // what the context holds from earlier calls goes back: later calls size their blocks under the limit
     SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->copy_stream) SWG_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    for (char** p : {&ctx->arena, &ctx->io_block, &ctx->range_block})
+    for (char** p : {&ctx->arena, &ctx->io_block, &ctx->range_block, &ctx->subset_block})
       if (*p) {
         SWG_HIP(ctx, hipFree(*p));
         *p = nullptr;
       }
-    ctx->arena_cap = ctx->io_cap = ctx->range_cap = 0;
+    ctx->arena_cap = ctx->io_cap = ctx->range_cap = ctx->subset_cap = 0;
   }
   return SWG_OK;
 }

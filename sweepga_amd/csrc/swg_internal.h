@@ -32,6 +32,11 @@ struct swg_ctx {
   // device block of the ranged filter (csrc/swg_range.hip): per-pair plan arrays, a range's record indices and staged columns
   char* range_block = nullptr;
   size_t range_cap = 0;
+  // device block of swg_filter_subset_device (csrc/swg_sparsify.hip): the compacted columns, the kept records' indices and results,
+  // which live across the arena reset of the filter call on them.  Under a memory limit the block exists only during such a call,
+  // which lowers mem_limit by the block's size for the filter call inside it
+  char* subset_block = nullptr;
+  size_t subset_cap = 0;
   // swg_set_memory_limit: bytes one filter call may hold on the device (arena + io_block + range_block), 0 = no limit
   uint64_t mem_limit = 0;
   uint32_t* narrow_host = nullptr;  // swg_filter64: the rebased 32-bit columns (host side, malloc), released by swg_narrow_release
