@@ -3242,12 +3242,12 @@ int pair_walk_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks
 // with everything decided on the device -- the plan, the list's length, and whether another round is needed: ROUNDS rounds
 // are enqueued, a round behind a round that changed nothing returns at once, and rounds that have not settled by then set
 // `fallback_bit` in *flags.  own / pred double as the walk's own score and predecessor arrays (the long chunks' positions belong
-// to no other chunk).
-int pair_walk_long_launch(swg_ctx* ctx, uint32_t cap_long, const uint32_t* n_long_dev, const uint32_t* long_list, const SpecBlock* chunks,
+// to no other chunk).  Everything is enqueued on `st` (the scratch below is this leg's own: it may run beside the chunks' walk).
+int pair_walk_long_launch(swg_ctx* ctx, hipStream_t st, uint32_t cap_long, const uint32_t* n_long_dev, const uint32_t* long_list, const SpecBlock* chunks,
                           uint32_t n_members_cap, const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te,
                           uint64_t max_gap, unsigned long long* own, uint32_t* pred, uint32_t* flags, uint32_t fallback_bit) {
   if (cap_long == 0) return SWG_OK;
-  hipStream_t st = ctx->stream;
+  swg_on_stream on(ctx, st);
   constexpr int ROUNDS = 4;
   const uint32_t cap_spec = n_members_cap / 512 + cap_long + 1;
   SpecBlock* desc = swg_alloc<SpecBlock>(ctx, cap_spec);

@@ -959,7 +959,7 @@ int chain_table_build(swg_ctx* ctx, const swg_records* r, const uint8_t* alive, 
 int pair_label_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks_dev, const SpecBlock* chunks, const uint32_t* pred,
                       const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te, const uint32_t* s_m,
                       const uint32_t* s_b, uint64_t min_len, double min_ident, uint32_t* hd, uint8_t* ok_head, HeadRec* rec,
-                      unsigned long long* n_heads, uint32_t cap_long, const uint32_t* n_long_dev, const uint32_t* long_list) {
+                      unsigned long long* n_heads) {
   if (cap_chunks == 0) return SWG_OK;
   static const uint64_t lper = getenv("SWG_LABEL_BLOCKS") ? (uint64_t)atoi(getenv("SWG_LABEL_BLOCKS")) : 128;  // (work-groups per CU in the grid)
   const uint64_t lb = cap_chunks < (uint64_t)ctx->num_cu * lper ? cap_chunks : (uint64_t)ctx->num_cu * lper;
@@ -972,12 +972,21 @@ int pair_label_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunk
                                                                              nullptr, min_len, min_ident, hd, ok_head, rec, n_heads,
                                                                              n_chunks_dev));
   SWG_KERNEL_CHECK(ctx);
-  if (cap_long) {
-    const unsigned lg = cap_long < (uint32_t)ctx->num_cu * 2 ? cap_long : (unsigned)ctx->num_cu * 2;  // (32 registers: two work-groups of 1,024 per CU)
-    SWG_LAUNCH(ctx, "chain_label_long", chain_label_long_kernel<<<lg, 1024, 0, ctx->stream>>>(cap_long, n_long_dev, long_list, chunks, pred, s_qs, s_qe, s_ts,
-                                                                                  s_te, s_m, s_b, min_len, min_ident, hd, ok_head, rec, n_heads));
-    SWG_KERNEL_CHECK(ctx);
-  }
+  return SWG_OK;
+}
+
+// chain_label_long_kernel over the list of the long chunks.  It writes hd / ok_head / rec at the long chunks' positions only
+// (chain_label_kernel skips those chunks) and adds to *n_heads atomically: the two labellings may run side by side.
+int pair_label_long_launch(swg_ctx* ctx, hipStream_t st, uint32_t cap_long, const uint32_t* n_long_dev, const uint32_t* long_list, const SpecBlock* chunks,
+                           const uint32_t* pred, const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te,
+                           const uint32_t* s_m, const uint32_t* s_b, uint64_t min_len, double min_ident, uint32_t* hd, uint8_t* ok_head,
+                           HeadRec* rec, unsigned long long* n_heads) {
+  if (cap_long == 0) return SWG_OK;
+  swg_on_stream on(ctx, st);
+  const unsigned lg = cap_long < (uint32_t)ctx->num_cu * 2 ? cap_long : (unsigned)ctx->num_cu * 2;  // (32 registers: two work-groups of 1,024 per CU)
+  SWG_LAUNCH(ctx, "chain_label_long", chain_label_long_kernel<<<lg, 1024, 0, st>>>(cap_long, n_long_dev, long_list, chunks, pred, s_qs, s_qe, s_ts,
+                                                                       s_te, s_m, s_b, min_len, min_ident, hd, ok_head, rec, n_heads));
+  SWG_KERNEL_CHECK(ctx);
   return SWG_OK;
 }
 

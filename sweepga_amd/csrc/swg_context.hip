@@ -125,6 +125,27 @@ int swg_read_scalars(swg_ctx* ctx, const uint64_t* d_src, uint64_t* h_dst, int c
   return SWG_OK;
 }
 
+int swg_side_stream(swg_ctx* ctx, hipStream_t* out) {
+  if (!ctx->side_stream) {
+    // the events first: nothing points at a stream without them, and a failure leaves the context as it was
+    hipEvent_t f = nullptr, j = nullptr;
+    hipStream_t s = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&f, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&j, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      if (j) (void)hipEventDestroy(j);
+      if (f) (void)hipEventDestroy(f);
+      return swg_set_error(ctx, e == hipErrorOutOfMemory ? SWG_ERR_OOM : SWG_ERR_HIP, "creating the side stream failed: %s", hipGetErrorString(e));
+    }
+    ctx->ev_fork = f;
+    ctx->ev_join = j;
+    ctx->side_stream = s;
+  }
+  *out = ctx->side_stream;
+  return SWG_OK;
+}
+
 swg_prof_scope::swg_prof_scope(swg_ctx* c, const char* kernel_name, uint64_t units) : ctx(c) {
   if (!ctx || !ctx->prof_on) return;
   if (!ctx->prof_only.empty() && ctx->prof_only != kernel_name) return;  // swg_profile_select: events around one kernel only
@@ -147,13 +168,14 @@ swg_prof_scope::swg_prof_scope(swg_ctx* c, const char* kernel_name, uint64_t uni
   };
   a = get();
   b = get();
-  if (a) (void)hipEventRecord(a, ctx->stream);
+  stream = ctx->launch_stream ? ctx->launch_stream : ctx->stream;
+  if (a) (void)hipEventRecord(a, stream);
 }
 
 swg_prof_scope::~swg_prof_scope() {
   if (!ctx || name < 0) return;
   if (a && b) {
-    (void)hipEventRecord(b, ctx->stream);
+    (void)hipEventRecord(b, stream);
     ctx->prof_pending_list.push_back({name, a, b});
   }
 }
@@ -161,6 +183,7 @@ swg_prof_scope::~swg_prof_scope() {
 int swg_prof_collect(swg_ctx* ctx) {
   if (ctx->prof_pending_list.empty()) return SWG_OK;
   SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->side_stream) SWG_HIP(ctx, hipStreamSynchronize(ctx->side_stream));  // (joined by every call that used it: returns at once)
   for (auto& p : ctx->prof_pending_list) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
@@ -254,6 +277,7 @@ void swg_destroy(swg_ctx* ctx) {
   if (!ctx) return;
   if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->io_block) (void)hipFree(ctx->io_block);
   if (ctx->range_block) (void)hipFree(ctx->range_block);
@@ -274,6 +298,9 @@ void swg_destroy(swg_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->copy_stream);
     (void)hipStreamDestroy(ctx->copy_stream);
   }
+  if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
+  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+  if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

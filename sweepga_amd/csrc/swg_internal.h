@@ -13,6 +13,11 @@ struct swg_ctx {
   int device = -1;
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;  // H2D copies of the streamed host path (created on first use)
+  // second compute stream (created on first use, swg_side_stream): the long-unit leg of the pair-resident stage runs on it beside
+  // the short-unit kernels (swg_pair.hip).  ev_fork: recorded on `stream`, waited for by the side stream; ev_join: the reverse
+  hipStream_t side_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipStream_t launch_stream = nullptr;  // where the launches being enqueued go when not `stream` (swg_on_stream): the profiler's events follow
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // bump arena for per-call scratch; grown (never shrunk) between calls
   char* arena = nullptr;
@@ -75,12 +80,26 @@ struct swg_prof_scope {
   swg_ctx* ctx;
   int name = -1;
   hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t stream = nullptr;  // where the two events are recorded: ctx->launch_stream if set, else ctx->stream
   // units: elements this launch works on (0 = unknown: the whole record set of the call)
   swg_prof_scope(swg_ctx* c, const char* kernel_name, uint64_t units = 0);
   ~swg_prof_scope();
 };
 // Resolves pending event pairs into the per-name table (synchronises the stream).
 int swg_prof_collect(swg_ctx* ctx);
+// The launches enqueued while one of these lives go to `s`, not to ctx->stream: swg_prof_scope records its events there, so a
+// label is timed on the stream its kernel runs on.  (The launch sites keep one textual form, SWG_LAUNCH(ctx, "label", kernel<<<..,
+// s>>>), which the label check of the test suite and tools/pmc_traffic.py read.)
+struct swg_on_stream {
+  swg_ctx* ctx;
+  hipStream_t before;
+  swg_on_stream(swg_ctx* c, hipStream_t s) : ctx(c), before(c->launch_stream) { c->launch_stream = s; }
+  ~swg_on_stream() { ctx->launch_stream = before; }
+  swg_on_stream(const swg_on_stream&) = delete;
+  swg_on_stream& operator=(const swg_on_stream&) = delete;
+};
+// The context's side stream and its two events, created on the first call (all three or none).
+int swg_side_stream(swg_ctx* ctx, hipStream_t* out);
 
 extern thread_local std::string swg_create_error;
 

@@ -2811,18 +2811,65 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
     SWG_LAUNCH(ctx, "pair_gate", pair_gate_kernel<<<1, 64, 0, st>>>(C));
     SWG_KERNEL_CHECK(ctx);
   }
-  SWG_TRY(pair_walk_launch(ctx, cap_chunks, &C->n_chunks, chunks, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred));
   const bool long_possible = ncls[2] + ncls[3] > 0;  // (a chunk of LABEL_CAP_ELEMS members needs a pair of at least as many)
-  if (long_possible) {
-    SWG_TRY(pair_walk_long_launch(ctx, cap_long, &C->n_long, long_list, chunks, n, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred,
+  const uint32_t* lab_m = need_wid ? s_m : nullptr;
+  const uint32_t* lab_b = need_wid ? s_b : nullptr;
+  // The two legs.  Short: the walk and the labelling of the chunks (kernels that fill the chip).  Long: the block-speculative walk
+  // and the labelling of the chunks of LABEL_CAP_ELEMS members and more (a dozen small kernels bound by dependent-chain latency,
+  // then one work-group per long chunk).  Both only read what the sorts wrote; the long chunks' positions of bps / pred / hd /
+  // ok_head / head_rec belong to the long leg alone (chain_walk_kernel and chain_label_kernel skip those chunks), n_heads and the
+  // flags are atomics, and neither leg reads the other's verdict.
+  auto short_leg = [&]() -> int {
+    SWG_TRY(pair_walk_launch(ctx, cap_chunks, &C->n_chunks, chunks, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred));
+    return SWG_OK;
+  };
+  auto short_label = [&]() -> int {
+    return pair_label_launch(ctx, cap_chunks, &C->n_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, lab_m, lab_b, cfg->min_scaffold_length,
+                             cfg->min_scaffold_identity, hd, ok_head, head_rec, &C->n_heads);
+  };
+  auto long_walk = [&](hipStream_t ls) -> int {
+    SWG_TRY(pair_walk_long_launch(ctx, ls, cap_long, &C->n_long, long_list, chunks, n, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred,
                                   &C->flags, PF_FALLBACK));
-    if (!by_hash) {
-      SWG_LAUNCH(ctx, "pair_gate", pair_gate_kernel<<<1, 64, 0, st>>>(C));
+    if (!by_hash) {  // (a long unit that did not settle: n_long goes to zero before the long labelling reads it)
+      swg_on_stream on(ctx, ls);
+      SWG_LAUNCH(ctx, "pair_gate", pair_gate_kernel<<<1, 64, 0, ls>>>(C));
       SWG_KERNEL_CHECK(ctx);
     }
+    return SWG_OK;
+  };
+  auto long_label = [&](hipStream_t ls) -> int {
+    return pair_label_long_launch(ctx, ls, cap_long, &C->n_long, long_list, chunks, pred, s_qs, s_qe, s_ts, s_te, lab_m, lab_b,
+                                  cfg->min_scaffold_length, cfg->min_scaffold_identity, hd, ok_head, head_rec, &C->n_heads);
+  };
+  // SWG_PAIR_OVERLAP=0: one leg after the other on the context's stream.  Inputs grouped through the hash table are too small for
+  // the long leg to matter and keep that order too.
+  static const bool overlap_knob = !(getenv("SWG_PAIR_OVERLAP") && atoi(getenv("SWG_PAIR_OVERLAP")) == 0);
+  if (overlap_knob && long_possible && !by_hash) {
+    hipStream_t side = nullptr;
+    SWG_TRY(swg_side_stream(ctx, &side));
+    // fork behind the first gate (a call the sorts gave up has no chunks and no long chunks: both legs return at once)
+    SWG_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
+    SWG_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_fork, 0));
+    // the long leg's launches first: its queue is busy by the time the walk of the chunks fills the chip.  Its gate may zero
+    // n_chunks while the short leg reads it: on a call that is handed over anyway, whose kernels from here on all return on
+    // PF_FALLBACK -- work for nothing at worst, never another answer.
+    int rc = long_walk(side);
+    if (rc == SWG_OK) rc = long_label(side);
+    if (rc == SWG_OK) rc = short_leg();
+    if (rc == SWG_OK) rc = short_label();
+    // join, on every way out: what follows -- pair_finish, the read-back, and after an error or a hand-over the caller's reuse of
+    // the arena -- must find the side stream finished
+    hipError_t je = hipEventRecord(ctx->ev_join, side);
+    if (je == hipSuccess) je = hipStreamWaitEvent(st, ctx->ev_join, 0);
+    if (je != hipSuccess || rc != SWG_OK) (void)hipStreamSynchronize(side);
+    SWG_TRY(rc);
+    SWG_HIP(ctx, je);
+  } else {
+    SWG_TRY(short_leg());
+    if (long_possible) SWG_TRY(long_walk(st));
+    SWG_TRY(short_label());
+    if (long_possible) SWG_TRY(long_label(st));
   }
-  SWG_TRY(pair_label_launch(ctx, cap_chunks, &C->n_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, need_wid ? s_m : nullptr, need_wid ? s_b : nullptr, cfg->min_scaffold_length,
-                            cfg->min_scaffold_identity, hd, ok_head, head_rec, &C->n_heads, long_possible ? cap_long : 0u, &C->n_long, long_list));
   // ---- a scaffold filter with limits: plane_sweep_both over the chain table of the whole input
   uint8_t* kept_flags = nullptr;
   uint32_t *chain_base = nullptr, *np_arr = nullptr;
