@@ -526,6 +526,56 @@ int swg_alnstats_records_device(swg_ctx* ctx, const swg_records* rec, const uint
  * swg_alnstats_records seam works on swg_aln_records, swg_paf_alnstats has no .1aln twin. */
 int swg_paf_alnstats(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, swg_alnstats** all_out, swg_alnstats** kept_out);
 
+/* ---- breadth: merged-interval coverage per ordered genome pair, on the device ---------------------
+ * alnstats' coverage sums mapping lengths, so overlapping mappings count once each; breadth is the number of bases under AT
+ * LEAST ONE mapping.  Over the records whose two genomes differ under the map the caller supplies (alnstats' inter-genome
+ * rule: self and intra-genome records are ignored), per ordered pair (query genome, target genome):
+ *   q_bases = sum(q_end - q_start), t_bases = sum(t_end - t_start);
+ *   q_union = sum over the sequences s of the query genome of |union of [q_start, q_end)| over the pair's records with
+ *             q_id == s; t_union likewise per sequence of the target genome over [t_start, t_end).
+ * Intervals are half-open, zero-length ones add nothing, touching ones join without double counting, and the intervals of one
+ * sequence against two genomes are never merged with each other.  start <= end is assumed.  q_id, t_id and the four
+ * coordinate columns are read (32-bit layout).  status == NULL: one result set, ALL records; status != NULL: a second set,
+ * KEPT, over the records with status != 0 -- the rule of swg_paf_write -- from the same launches.  The pairs are listed in
+ * ascending first_record, one to one with swg_alnstats_pair_counts of the same input.  Every value is a sum of integers and
+ * does not depend on the order of the records (first_record and the listing order aside).  Capacity protocol and errors as
+ * the alnstats record seams: n_pairs > pair_capacity still returns SWG_OK and leaves `pairs` alone; n >= 2^31 records:
+ * SWG_ERR_RANGE; a sequence or genome id out of range: SWG_ERR_INVALID; a NULL context: SWG_ERR_INVALID (there is no CPU
+ * path).  Scratch comes from the context's arena, SWG_ERR_OOM when the memory limit does not hold it: 28 bytes per record
+ * (two 8-byte key buffers, two 4-byte value buffers, one 4-byte buffer of ends; both axes use the same ones), plus the radix
+ * sort's own histograms, plus the segment set and the genome-pair table (sized by what occurs).  swg_breadth_records stages
+ * its host columns there too: 25 more bytes per record (six columns and the status byte). */
+typedef struct swg_breadth_pair {
+  uint32_t q_genome, t_genome; /* ORDERED pair of genome ids (query genome, target genome) */
+  uint64_t q_bases, t_bases;   /* summed lengths on either side */
+  uint64_t q_union, t_union;   /* bases under at least one mapping on either side */
+  uint64_t first_record;       /* smallest index of a record of the pair */
+} swg_breadth_pair;
+typedef struct swg_breadth_counts {
+  uint64_t n_pairs;        /* out: genome pairs that occur */
+  uint64_t pair_capacity;  /* in: entries `pairs` can hold */
+  swg_breadth_pair* pairs; /* in: caller-owned [pair_capacity] or NULL; written only when n_pairs <= pair_capacity */
+} swg_breadth_counts;
+/* rec: host pointers; seq_genome[rec->n_seq] and status[n] on the host.  all / kept: either may be NULL (kept is ignored when
+ * status is NULL). */
+int swg_breadth_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                        const uint8_t* status, swg_breadth_counts* all, swg_breadth_counts* kept);
+/* The same with the six columns of rec, seq_genome and status in device memory of ctx's GPU; the counts structures and their
+ * arrays stay on the host. */
+int swg_breadth_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                               const uint8_t* status, swg_breadth_counts* all, swg_breadth_counts* kept);
+/* The breadth report of an open PAF under its last-'#' genome map, as text (release it with swg_free): tab-separated, the
+ * header line
+ *   set query_genome target_genome q_bases q_union q_size q_breadth_pct q_depth t_bases t_union t_size t_breadth_pct t_depth
+ * then per set -- `all`, and with status != NULL `kept` -- one row per genome pair in first_record order (only when
+ * `detailed`) and a last row with `*` in both genome columns that holds the sums over the pairs (sizes summed per pair).
+ * Genome names keep their trailing '#'; sizes are those swg_paf_alnstats derives for the set (last-seen lengths, read from the
+ * handle's text); breadth_pct = 100.0 * union / size and depth = bases / union, computed in double and printed "%.4f", `-`
+ * when the divisor is 0.  A PAF without records needs no device (ctx may be NULL then).  A handle whose columns are rebased
+ * (the file has a value >= 2^32): SWG_ERR_UNSUPPORTED.  Errors: text in swg_alnstats_last_error().  .1aln handles keep no
+ * text: the record seams above work on swg_aln_records. */
+int swg_paf_breadth(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int detailed, char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -34,7 +34,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_tree_select_pairs", "swg_tree_select_records", "swg_tree_select_records_device", "swg_filter_subset",
            "swg_filter_subset_device", "swg_filter_subset_multi", "swg_paf_tree_select", "swg_paf_tree_needs_text",
            "swg_aln_tree_select", "swg_paf_num_genomes_two", "swg_paf_genome_two_prefix", "swg_aln_num_genomes_two",
-           "swg_aln_genome_two_prefix"]
+           "swg_aln_genome_two_prefix",
+           "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth"]
 
 
 class SwgError(RuntimeError):
@@ -121,6 +122,15 @@ class SwgAlnstatsCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("total_mappings", "total_bases", "total_matches", "self_mappings", "inter_chromosomal",
                                            "inter_genome", "chr_pair_count", "n_pairs", "pair_capacity")] + \
                [("pairs", C.POINTER(SwgAlnstatsPairCounts)), ("seq_last", C.POINTER(C.c_uint64))]
+
+
+class SwgBreadthPair(C.Structure):
+    _fields_ = [("q_genome", C.c_uint32), ("t_genome", C.c_uint32), ("q_bases", C.c_uint64), ("t_bases", C.c_uint64),
+                ("q_union", C.c_uint64), ("t_union", C.c_uint64), ("first_record", C.c_uint64)]
+
+
+class SwgBreadthCounts(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgBreadthPair))]
 
 
 _lib = None
@@ -298,6 +308,15 @@ def load():
         f = getattr(lib, name)
         f.restype = C.c_char_p
         f.argtypes = [C.c_void_p, C.c_uint32]
+    for name in ("swg_breadth_records", "swg_breadth_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgBreadthCounts),
+                      C.POINTER(SwgBreadthCounts)]
+    lib.swg_paf_breadth.restype = C.c_int
+    lib.swg_paf_breadth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.swg_alnstats_last_error.restype = C.c_char_p
+    lib.swg_alnstats_last_error.argtypes = []
     _lib = lib
     return lib
 

@@ -374,6 +374,51 @@ int swg_alnstats_from_counts(const swg_alnstats_result& r, const std::vector<std
   }
 }
 
+// The --breadth report: tab-separated, one header line, per set (all, then kept) one row per genome pair
+// in first-record order when `detailed`, then the `*` row of the set's sums (sizes summed per pair).  pct = 100.0 * union /
+// size and depth = bases / union in f64, "%.4f", "-" over a zero divisor.
+int swg_breadth_report(const std::vector<std::string>& genome_name, const swg_breadth_result* res, const std::vector<uint64_t>* genome_size,
+                       int n_sets, bool detailed, char** out_text, uint64_t* out_len) {
+  std::string o = "set\tquery_genome\ttarget_genome\tq_bases\tq_union\tq_size\tq_breadth_pct\tq_depth\tt_bases\tt_union\tt_size\tt_breadth_pct\tt_depth\n";
+  auto side = [&o](uint64_t bases, uint64_t uni, uint64_t size) {
+    char buf[400];
+    o += '\t' + std::to_string(bases) + '\t' + std::to_string(uni) + '\t' + std::to_string(size) + '\t';
+    if (size) {
+      std::snprintf(buf, sizeof buf, "%.4f", 100.0 * (double)uni / (double)size);
+      o += buf;
+    } else {
+      o += '-';
+    }
+    o += '\t';
+    if (uni) {
+      std::snprintf(buf, sizeof buf, "%.4f", (double)bases / (double)uni);
+      o += buf;
+    } else {
+      o += '-';
+    }
+  };
+  for (int k = 0; k < n_sets; ++k) {
+    const char* set = k ? "kept" : "all";
+    uint64_t sum[6] = {0, 0, 0, 0, 0, 0};
+    for (const swg_breadth_pair& p : res[k].pairs) {
+      const uint64_t qsz = genome_size[k][p.q_genome], tsz = genome_size[k][p.t_genome];
+      sum[0] += p.q_bases, sum[1] += p.q_union, sum[2] += qsz, sum[3] += p.t_bases, sum[4] += p.t_union, sum[5] += tsz;
+      if (!detailed) continue;
+      o += set;
+      o += '\t' + genome_name[p.q_genome] + '\t' + genome_name[p.t_genome];
+      side(p.q_bases, p.q_union, qsz);
+      side(p.t_bases, p.t_union, tsz);
+      o += '\n';
+    }
+    o += set;
+    o += "\t*\t*";
+    side(sum[0], sum[1], sum[2]);
+    side(sum[3], sum[4], sum[5]);
+    o += '\n';
+  }
+  return hand_over(o, out_text, out_len);
+}
+
 extern "C" {
 
 int swg_alnstats_open_buffer(const char* text, uint64_t len, int threads, swg_alnstats** out) {

@@ -35,8 +35,22 @@ int swg_alnstats_from_counts(const swg_alnstats_result& r, const std::vector<std
 // the text side of swg_paf_alnstats (paf_io.cpp; host code only, so that the host translation units link without the device ones)
 int swg_paf_stats_prepare(const swg_paf* p, swg_records* rec, std::vector<uint32_t>* col10, const uint32_t** seq_genome);
 int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res /* [2]: ALL, KEPT */, swg_alnstats** const* outs /* [2], NULL = not wanted */);
+// the two halves of swg_paf_stats_finish that swg_paf_breadth needs too: genome g's name (trailing '#' kept), and its size in one
+// result set (sum of the last-seen lengths of its sequences, read from the lines the set's seq_last names)
+void swg_paf_stats_genome_names(const swg_paf* p, std::vector<std::string>* genome_name);
+int swg_paf_stats_genome_sizes(const swg_paf* p, const swg_alnstats_result& r, std::vector<uint64_t>* genome_size);
 int swg_alnstats_error(int code, const char* fmt, ...);  // sets swg_alnstats_last_error()
 extern const char* const SWG_ALNSTATS_FIELD_ERR[6];      // "Invalid query length" ... for columns 2, 3, 4, 7, 10, 11
+
+// ---- breadth (swg_breadth.hip: kernels and seams; alnstats.cpp: the report) ----
+struct swg_breadth_result {
+  std::vector<swg_breadth_pair> pairs;  // ascending first_record
+};
+int swg_breadth_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome,
+                    const uint8_t* status, swg_breadth_result* all, swg_breadth_result* kept);
+// the --breadth report of n_sets result sets (ALL, KEPT) with the genome sizes of each set
+int swg_breadth_report(const std::vector<std::string>& genome_name, const swg_breadth_result* res, const std::vector<uint64_t>* genome_size,
+                       int n_sets, bool detailed, char** out_text, uint64_t* out_len);
 
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53

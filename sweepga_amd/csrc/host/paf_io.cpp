@@ -935,27 +935,35 @@ int swg_paf_stats_prepare(const swg_paf* p, swg_records* rec, std::vector<uint32
   return SWG_OK;
 }
 
-int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res, swg_alnstats** const* outs) {
+void swg_paf_stats_genome_names(const swg_paf* p, std::vector<std::string>* genome_name) {
   const uint64_t n = p->rec.n;
-  const uint32_t G = n ? p->rec.n_genome_last : 0;
-  std::vector<std::string> gname(G);
-  for (size_t s = 0; s < p->names.size() && n; ++s) gname[p->g_last[s]] = prefix_last(p->names[s]);
+  genome_name->assign(n ? p->rec.n_genome_last : 0, std::string());
+  for (size_t s = 0; s < p->names.size() && n; ++s) (*genome_name)[p->g_last[s]] = prefix_last(p->names[s]);
+}
+
+int swg_paf_stats_genome_sizes(const swg_paf* p, const swg_alnstats_result& r, std::vector<uint64_t>* genome_size) {
+  genome_size->assign(p->rec.n ? p->rec.n_genome_last : 0, 0);
+  for (size_t s = 0; s < r.seq_last.size(); ++s) {
+    const uint64_t v = r.seq_last[s];
+    if (v == UINT64_MAX) continue;
+    size_t len;
+    const char* b = stats_column(p, v >> 1, (v & 1) ? 6 : 1, &len);
+    uint64_t size;
+    if (!parse_u64(b, len, &size))
+      return swg_alnstats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[(v & 1) ? 3 : 0], (unsigned long long)(p->rank[v >> 1] + 1));
+    (*genome_size)[p->g_last[s]] += size;
+  }
+  return SWG_OK;
+}
+
+int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res, swg_alnstats** const* outs) {
+  std::vector<std::string> gname;
+  swg_paf_stats_genome_names(p, &gname);
   int rc = SWG_OK;
   for (int k = 0; k < 2 && rc == SWG_OK; ++k) {
     if (!outs[k]) continue;
-    std::vector<uint64_t> gsize(G, 0);
-    for (size_t s = 0; s < res[k].seq_last.size(); ++s) {
-      const uint64_t v = res[k].seq_last[s];
-      if (v == UINT64_MAX) continue;
-      size_t len;
-      const char* b = stats_column(p, v >> 1, (v & 1) ? 6 : 1, &len);
-      uint64_t size;
-      if (!parse_u64(b, len, &size)) {
-        rc = swg_alnstats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[(v & 1) ? 3 : 0], (unsigned long long)(p->rank[v >> 1] + 1));
-        break;
-      }
-      gsize[p->g_last[s]] += size;
-    }
+    std::vector<uint64_t> gsize;
+    rc = swg_paf_stats_genome_sizes(p, res[k], &gsize);
     if (rc == SWG_OK) rc = swg_alnstats_from_counts(res[k], gname, gsize, outs[k]);
   }
   if (rc != SWG_OK)  // no half result

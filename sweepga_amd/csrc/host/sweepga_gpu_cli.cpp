@@ -254,6 +254,20 @@ void write_stats_report(const std::string& path, const swg_alnstats* before, con
   if (f == stderr) std::fflush(stderr);
 }
 
+// --breadth: the report of swg_paf_breadth (merged-interval coverage per genome pair, all records and the kept ones).
+// "-" = standard error.
+void write_breadth_report(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, bool detailed) {
+  char* text = nullptr;
+  uint64_t len = 0;
+  if (swg_paf_breadth(ctx, paf, status, detailed ? 1 : 0, &text, &len) != SWG_OK) die(3, std::string("--breadth: ") + swg_alnstats_last_error());
+  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
+  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+  if (f == stderr) std::fflush(stderr);
+  swg_free(text);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -270,6 +284,8 @@ int main(int argc, char** argv) {
   std::vector<std::string> inputs;
   bool joblist = false, threads_given = false, stats_detailed = false;
   std::string stats_path;  // --stats: empty = no report
+  std::string breadth_path;  // --breadth: empty = no report
+  bool breadth_detailed = false;
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -330,6 +346,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--stats") { stats_path = value(); if (stats_path.empty()) die(2, "empty value for --stats"); }
     else if (a == "--stats-detailed") stats_detailed = true;
+    else if (a == "--breadth") { breadth_path = value(); if (breadth_path.empty()) die(2, "empty value for --breadth"); }
+    else if (a == "--breadth-detailed") breadth_detailed = true;
     else if (a == "--joblist") joblist = true;
     else if (a == "--joblist-output-dir") joblist_dir = value();
     else if (a == "--mash-kmer-size") { if (!parse_u64(value(), &mash_k)) die(2, "invalid value for --mash-kmer-size"); }
@@ -340,12 +358,16 @@ int main(int argc, char** argv) {
                 "         [--scaffold-mass N] [--scaffold-filter M] [--scaffold-overlap F] [--scaffold-dist N]\n"
                 "         [--min-scaffold-identity I] [--scaffolds-only] [--ani-method M]\n"
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
-                "         [--stats REPORT|-] [--stats-detailed]\n"
+                "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
                 "                      computed on the device from the records and their status (- = standard error)\n"
                 "  --stats-detailed    with --stats: followed by the two `alnstats <file> -d` reports (input, then output)\n"
+                "  --breadth REPORT    after the filter: per set (all records, kept records) the bases of either side under at least one\n"
+                "                      inter-genome mapping (merged intervals), their share of the genome and the mean depth, as a\n"
+                "                      tab-separated table computed on the device (- = standard error); with --no-filter kept = all\n"
+                "  --breadth-detailed  with --breadth: one row per ordered genome pair ahead of each set's `*` row of sums\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -419,8 +441,9 @@ int main(int argc, char** argv) {
   std::string init_err;
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
-    if (no_filter) return;
+    if (no_filter && breadth_path.empty()) return;  // (--no-filter opens a device only for the breadth report)
     for (int d : devices) {
+      if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
       swg_ctx* c = nullptr;
       const auto c0 = std::chrono::steady_clock::now();
       init_rc = swg_create(d, &c);
@@ -433,6 +456,8 @@ int main(int argc, char** argv) {
       const auto w0 = std::chrono::steady_clock::now();
       // best effort: a failure here (e.g. no room for the speculative reservation) shows up again, with its own message, in
       // the filter call, which sizes itself; SWG_DEBUG prints this one too
+      // (--no-filter --breadth runs no filter: the report's call sizes its own, smaller arena)
+      if (no_filter) continue;
       if (swg_warmup(c, records_hint / devices.size(), 4096, cfg.scaffold_gap != 0) != SWG_OK && getenv("SWG_DEBUG"))
         fprintf(stderr, "[sweepga-gpu] warm-up on device %d failed (ignored): %s\n", d, swg_last_error(c));
       warm_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
@@ -457,6 +482,11 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(2, msg);
   }
+  // --breadth reads 32-bit columns (swg_paf_breadth): refused here, not after a whole filter run and ahead of the output
+  if (!breadth_path.empty() && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {
+    gpu_init.join();
+    die(3, "--breadth: the file has a value >= 2^32, its columns are rebased: breadth of 64-bit columns is not supported");
+  }
   const std::string out_path = output_file.empty() ? "-" : output_file;
   const swg_records* r = swg_paf_records(paf);
   uint64_t n = r->n;
@@ -474,15 +504,22 @@ int main(int argc, char** argv) {
       std::fputc('\n', out);
       pos = end + 1;
     }
-    if (!stats_path.empty()) {  // no device is opened on this path: the host tool's statistics of the same lines, twice
+    if (!stats_path.empty()) {  // no device is needed for this report: the host tool's statistics of the same lines, twice
       std::fflush(out);
       swg_alnstats* sa = nullptr;
       if (swg_alnstats_open_buffer(text, len, threads, &sa) != SWG_OK) die(3, std::string("--stats: ") + swg_alnstats_last_error());
       write_stats_report(stats_path, sa, sa, input, out_path, stats_detailed);
       swg_alnstats_close(sa);
     }
-    swg_paf_close(paf);
     gpu_init.join();
+    if (!breadth_path.empty()) {  // nothing is dropped: the kept rows equal the all rows
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_breadth_report(breadth_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), breadth_detailed);
+    }
+    for (swg_ctx* c : ctxs) swg_destroy(c);
+    swg_paf_close(paf);
     return 0;
   }
   const auto t1 = clk::now();
@@ -580,6 +617,12 @@ int main(int argc, char** argv) {
     }
     swg_alnstats_close(sa);
     swg_alnstats_close(sk);
+  }
+  // ---- --breadth: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (!breadth_path.empty()) {
+    const auto tb = clk::now();
+    write_breadth_report(breadth_path, ctx, paf, status.data(), breadth_detailed);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --breadth: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

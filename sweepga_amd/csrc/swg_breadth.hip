@@ -1,0 +1,552 @@
+// Breadth: per ordered genome pair, the bases of each side that lie under at least one mapping -- the
+// merged-interval coverage that alnstats' summed coverage is mistaken for -- for ALL records and, from the same launches, for
+// the records a filter call KEPT (status != 0).  Only records whose two genomes differ count (alnstats' inter-genome rule).
+//
+// The unit is the filter's sweep segment: one sequence against one genome of the other side.  Per axis:
+//
+//   breadth_keys     key = segment << 32 | start, value = record index (bit 31: KEPT; n < 2^31 leaves it free, so the status
+//                    byte is read once, in input order, and never gathered).  segment = sequence * G + genome of the other side
+//                    while that fits 32 bits, else the slot of an open-addressing set over those products.  Records that do
+//                    not count get the segment `sentinel` (one past the last id): they sort to the end and add nothing.
+//   (sort)           swg_radix_sort_pairs over the 32 + bits(sentinel) key bits.
+//   breadth_gather   tile of 1024 sorted records: end = end_column[record] (the one gather of the axis) written in sorted order,
+//                    and the tile's maximum of P = segment << 32 | end, once over all records and once over the KEPT ones.
+//                    Segments ascend along the sorted order, so the maximum of P over any prefix belongs to the LAST segment
+//                    of the prefix: a plain running maximum of P is the segmented running maximum of the ends.  Also counts
+//                    the segments (query axis), which bound the genome pairs that occur.
+//   (scan)           swg_inclusive_max_scan_u64 over the tile maxima: the carry across work-groups, however far it reaches
+//                    (one long interval over 10^6 short ones is 1000 tiles of carry).
+//   breadth_union    the same tile again: carry-in = scanned maximum of the tile before, running maximum across the threads
+//                    of the work-group (four consecutive records per thread, wavefront scan by shuffles, four wavefronts
+//                    through LDS), contribution = max(0, end - max(start, running maximum before)) with the maximum taken
+//                    as 0 when it belongs to an earlier segment.  ALL and KEPT are two maxima in the same pass.  bases, union
+//                    and the smallest record index go per genome pair through the run / LDS-table / global-table scheme of
+//                    swg_pair_table.h: one atomic per (work-group, pair, quantity).
+//   breadth_collect  the occupied pairs as lists (the host orders them by first record).
+//
+// Why two kernels around the library's scan and not one kernel with a decoupled look-back: a look-back makes work-groups wait
+// for each other inside a launch, and a wait that is wrong hangs a device others share; this form has no wait, its cost is
+// known -- the sorted keys, values and ends are read a second time, 16 bytes per record and axis -- and the scan it leans
+// on runs over n / 1024 values.  tools/breadth_bench.py measures the split; DESIGN.md section 17 records what is known.
+// Integer atomics only; no floating point.
+#include <algorithm>
+#include <cstdlib>
+#include <new>
+
+#include "swg_internal.h"
+#include "swg_pair_table.h"
+#include "host/host_internal.h"
+
+namespace {
+
+using namespace swg_pair_table;  // TB, WAVES, LSLOTS, EMPTY, NONE32, table_slot, lds_slot, run_end, run_sum, wave_sum
+constexpr int ITEMS = 4;                   // consecutive sorted records per thread
+constexpr int TILE = TB * ITEMS;           // ... per work-group
+constexpr uint32_t KEPT_FLAG = 0x80000000u;
+constexpr uint32_t INDEX_MASK = 0x7fffffffu;
+enum { D_BAD = 0, D_SEGMENTS, D_LISTED, D_LISTED_KEPT, D_TOTAL };
+enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // per set
+
+struct BreadthTable {
+  unsigned long long* keys;  // hashed: [mask + 1], EMPTY = free; nullptr = dense (slot = gq * G + gt)
+  unsigned long long* sums;  // [slots][2][Q_COUNT]: ALL, KEPT
+  uint32_t* first;           // [slots][2]: smallest record index ALL, KEPT (NONE32 = none)
+  uint32_t mask;
+  uint64_t slots;
+};
+struct SegMap {  // segment id -> sequence of the axis * G + genome of the other side
+  unsigned long long* set_keys;  // hashed: the set (segment = slot); nullptr = the product itself
+  uint32_t set_mask;
+  uint32_t G;
+  uint32_t sentinel;
+};
+struct PairOut {  // one listed genome pair
+  unsigned long long key, v[Q_COUNT], first;
+};
+
+// ---- keys --------------------------------------------------------------------------------------------------------------
+template <int AXIS>
+__global__ __launch_bounds__(TB) void breadth_keys_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
+                                                          const uint32_t* __restrict__ start, const uint8_t* __restrict__ status,
+                                                          const uint32_t* __restrict__ seq_genome, uint32_t n_seq, SegMap M,
+                                                          uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                          unsigned long long* __restrict__ scalars) {
+  const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t q = q_id[i], t = t_id[i];
+  const uint32_t gq = q < n_seq ? seq_genome[q] : NONE32, gt = t < n_seq ? seq_genome[t] : NONE32;
+  uint64_t key = (uint64_t)M.sentinel << 32;
+  if (gq >= M.G || gt >= M.G) {
+    atomicOr(&scalars[D_BAD], 1ull);
+  } else if (gq != gt) {
+    const unsigned long long product = (unsigned long long)(AXIS ? t : q) * M.G + (AXIS ? gq : gt);
+    const uint32_t seg = M.set_keys ? table_slot(M.set_keys, M.set_mask, product) : (uint32_t)product;
+    key = ((uint64_t)seg << 32) | start[i];
+  }
+  keys[i] = key;
+  vals[i] = (uint32_t)i | (status && status[i] != 0 ? KEPT_FLAG : 0u);
+}
+
+// ---- one tile of the sorted order ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load_tile(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n, uint64_t p0,
+                                          uint64_t (&k)[ITEMS], uint32_t (&v)[ITEMS]) {
+  if (p0 + ITEMS <= n) {  // (arena blocks are 16-byte aligned and p0 is a multiple of 4)
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(keys + p0), b = *reinterpret_cast<const ulonglong2*>(keys + p0 + 2);
+    const uint4 w = *reinterpret_cast<const uint4*>(vals + p0);
+    k[0] = a.x, k[1] = a.y, k[2] = b.x, k[3] = b.y;
+    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+      k[j] = p0 + j < n ? keys[p0 + j] : ~0ull;
+      v[j] = p0 + j < n ? vals[p0 + j] : 0u;
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned long long max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+__global__ __launch_bounds__(TB) void breadth_gather_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                            const uint32_t* __restrict__ end_col, uint32_t sentinel,
+                                                            uint32_t* __restrict__ ends, unsigned long long* __restrict__ tile_max,
+                                                            uint64_t ntiles, unsigned long long* __restrict__ segments) {
+  __shared__ unsigned long long l_max[2][WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
+  uint64_t k[ITEMS];
+  uint32_t v[ITEMS], e[ITEMS];
+  load_tile(keys, vals, n, p0, k, v);
+  uint32_t before = p0 > 0 && p0 <= n ? (uint32_t)(keys[p0 - 1] >> 32) : sentinel;  // (the sentinel is never a head's segment)
+  unsigned long long m_all = 0, m_kept = 0;
+  uint32_t heads = 0;
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    const uint32_t seg = (uint32_t)(k[j] >> 32);
+    const bool counted = p0 + j < n && seg != sentinel;
+    e[j] = counted ? end_col[v[j] & INDEX_MASK] : 0u;  // (values are the indices breadth_keys wrote: < n)
+    if (counted) {
+      const unsigned long long P = ((unsigned long long)seg << 32) | e[j];
+      m_all = max64(m_all, P);
+      if (v[j] & KEPT_FLAG) m_kept = max64(m_kept, P);
+      heads += seg != before || p0 + j == 0;
+    }
+    before = seg;
+  }
+  if (p0 + ITEMS <= n) {
+    *reinterpret_cast<uint4*>(ends + p0) = make_uint4(e[0], e[1], e[2], e[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j)
+      if (p0 + j < n) ends[p0 + j] = e[j];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    m_all = max64(m_all, __shfl_xor(m_all, d));
+    m_kept = max64(m_kept, __shfl_xor(m_kept, d));
+  }
+  if (segments) {
+    const unsigned long long h = wave_sum(heads);
+    if (lane == 0 && h) atomicAdd(segments, h);
+  }
+  if (lane == 0) l_max[0][wave] = m_all, l_max[1][wave] = m_kept;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned long long m = 0;
+    for (int w = 0; w < WAVES; ++w) m = max64(m, l_max[threadIdx.x][w]);
+    tile_max[threadIdx.x * ntiles + blockIdx.x] = m;
+  }
+}
+
+template <int AXIS>
+__device__ __forceinline__ void table_add(const BreadthTable& T, unsigned long long key, const unsigned long long v[4], uint32_t f_all,
+                                          uint32_t f_kept) {
+  const uint64_t s = T.keys ? table_slot(T.keys, T.mask, key) : key;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)  // v: bases ALL, union ALL, bases KEPT, union KEPT
+    if (v[j]) atomicAdd(&T.sums[s * (2 * Q_COUNT) + (j >> 1) * Q_COUNT + AXIS * 2 + (j & 1)], v[j]);
+  if (AXIS == 0) {
+    atomicMin(&T.first[s * 2], f_all);
+    if (f_kept != NONE32) atomicMin(&T.first[s * 2 + 1], f_kept);
+  }
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                           const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
+                                                           uint64_t ntiles, SegMap M, const uint32_t* __restrict__ seq_genome, BreadthTable T) {
+  __shared__ unsigned long long l_key[LSLOTS];
+  __shared__ unsigned long long l_sum[LSLOTS][4];
+  __shared__ uint32_t l_first[LSLOTS][2];
+  __shared__ unsigned long long l_wave[2][WAVES];
+  for (int s = threadIdx.x; s < LSLOTS; s += TB) {
+    l_key[s] = EMPTY;
+    l_sum[s][0] = l_sum[s][1] = l_sum[s][2] = l_sum[s][3] = 0;
+    l_first[s][0] = l_first[s][1] = NONE32;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
+  uint64_t k[ITEMS];
+  uint32_t v[ITEMS], e[ITEMS];
+  load_tile(keys, vals, n, p0, k, v);
+  if (p0 + ITEMS <= n) {
+    const uint4 w = *reinterpret_cast<const uint4*>(ends + p0);
+    e[0] = w.x, e[1] = w.y, e[2] = w.z, e[3] = w.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) e[j] = p0 + j < n ? ends[p0 + j] : 0u;
+  }
+  bool counted[ITEMS];
+  unsigned long long t_all = 0, t_kept = 0;
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    counted[j] = p0 + j < n && (uint32_t)(k[j] >> 32) != M.sentinel;
+    if (counted[j]) {
+      const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
+      t_all = max64(t_all, P);
+      if (v[j] & KEPT_FLAG) t_kept = max64(t_kept, P);
+    }
+  }
+  // running maximum over the threads before this one: wavefront, work-group, tiles before
+  unsigned long long i_all = t_all, i_kept = t_kept;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long a = __shfl_up(i_all, d), b = __shfl_up(i_kept, d);
+    if (lane >= d) i_all = max64(i_all, a), i_kept = max64(i_kept, b);
+  }
+  if (lane == 63) l_wave[0][wave] = i_all, l_wave[1][wave] = i_kept;
+  __syncthreads();  // (also: the LDS table is ready)
+  unsigned long long r_all = __shfl_up(i_all, 1), r_kept = __shfl_up(i_kept, 1);
+  if (lane == 0) r_all = r_kept = 0;
+  for (int w = 0; w < wave; ++w) r_all = max64(r_all, l_wave[0][w]), r_kept = max64(r_kept, l_wave[1][w]);
+  if (blockIdx.x > 0) r_all = max64(r_all, carry[blockIdx.x - 1]), r_kept = max64(r_kept, carry[ntiles + blockIdx.x - 1]);
+  // contributions
+  unsigned long long q[ITEMS][4];  // bases ALL, union ALL, bases KEPT, union KEPT
+  uint32_t f_all[ITEMS], f_kept[ITEMS];
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    q[j][0] = q[j][1] = q[j][2] = q[j][3] = 0;
+    f_all[j] = f_kept[j] = NONE32;
+    if (counted[j]) {
+      const uint32_t seg = (uint32_t)(k[j] >> 32), start = (uint32_t)k[j], idx = v[j] & INDEX_MASK;
+      const bool kept = (v[j] & KEPT_FLAG) != 0;
+      const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
+      const uint32_t len = e[j] > start ? e[j] - start : 0u;
+      const uint32_t m_all = (uint32_t)(r_all >> 32) == seg ? (uint32_t)r_all : 0u;
+      const uint32_t lo_all = start > m_all ? start : m_all;
+      q[j][0] = len;
+      q[j][1] = e[j] > lo_all ? e[j] - lo_all : 0u;
+      f_all[j] = idx;
+      r_all = max64(r_all, P);
+      if (kept) {
+        const uint32_t m_kept = (uint32_t)(r_kept >> 32) == seg ? (uint32_t)r_kept : 0u;
+        const uint32_t lo_kept = start > m_kept ? start : m_kept;
+        q[j][2] = len;
+        q[j][3] = e[j] > lo_kept ? e[j] - lo_kept : 0u;
+        f_kept[j] = idx;
+        r_kept = max64(r_kept, P);
+      }
+    }
+  }
+  // a thread's records of one segment: summed towards the first of them
+  bool head[ITEMS];
+#pragma unroll
+  for (int j = ITEMS - 1; j >= 1; --j) {
+    head[j] = counted[j];
+    if (counted[j] && counted[j - 1] && (k[j] >> 32) == (k[j - 1] >> 32)) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) q[j - 1][c] += q[j][c];
+      f_all[j - 1] = f_all[j - 1] < f_all[j] ? f_all[j - 1] : f_all[j];
+      f_kept[j - 1] = f_kept[j - 1] < f_kept[j] ? f_kept[j - 1] : f_kept[j];
+      head[j] = false;
+    }
+  }
+  head[0] = counted[0];
+  // round j: what the lanes hold at place j, runs of one genome pair along the lanes summed towards the run's first lane
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    if (__ballot(head[j]) == 0) continue;  // wavefront-uniform (rounds 1..3: only where a segment starts inside a thread)
+    unsigned long long key = EMPTY;
+    if (head[j]) {
+      const uint32_t seg = (uint32_t)(k[j] >> 32);
+      uint32_t seq, other;
+      if (M.set_keys) {
+        const unsigned long long product = M.set_keys[seg];
+        seq = (uint32_t)(product / M.G), other = (uint32_t)(product % M.G);
+      } else {
+        seq = seg / M.G, other = seg % M.G;
+      }
+      const uint32_t mine = seq_genome[seq];
+      key = AXIS ? (unsigned long long)other * M.G + mine : (unsigned long long)mine * M.G + other;
+    }
+    const unsigned long long before = __shfl_up(key, 1);
+    const bool first_lane = lane == 0 || key != before;
+    const int end = run_end(__ballot(first_lane), lane);
+    run_sum(q[j], lane, end);
+    uint32_t fa = f_all[j], fk = f_kept[j];
+    if (AXIS == 0) {
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t a = __shfl_down(fa, d), b = __shfl_down(fk, d);
+        if (lane + d < end) fa = fa < a ? fa : a, fk = fk < b ? fk : b;
+      }
+    }
+    if (first_lane && key != EMPTY) {
+      const int h = lds_slot(l_key, key);
+      if (h >= 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (q[j][c]) atomicAdd(&l_sum[h][c], q[j][c]);
+        if (AXIS == 0) {
+          atomicMin(&l_first[h][0], fa);
+          if (fk != NONE32) atomicMin(&l_first[h][1], fk);
+        }
+      } else {
+        table_add<AXIS>(T, key, q[j], fa, fk);  // more pairs in this tile than the LDS table takes
+      }
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < LSLOTS; s += TB)
+    if (l_key[s] != EMPTY) table_add<AXIS>(T, l_key[s], l_sum[s], l_first[s][0], l_first[s][1]);
+}
+
+// ---- the occupied genome pairs as lists ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TB) void breadth_collect_kernel(BreadthTable T, uint64_t cap, PairOut* __restrict__ out_all,
+                                                             PairOut* __restrict__ out_kept, unsigned long long* __restrict__ scalars) {
+  const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool in = s < T.slots;
+  const uint32_t f_all = in ? T.first[s * 2] : NONE32, f_kept = in ? T.first[s * 2 + 1] : NONE32;
+  const unsigned long long key = !in ? 0 : T.keys ? T.keys[s] : s;
+  auto place = [&](bool have, unsigned long long* counter) -> unsigned long long {  // consecutive places, one atomic per wavefront
+    const uint64_t m = __ballot(have);
+    if (!m) return 0;
+    unsigned long long base = 0;
+    if (lane == __builtin_ctzll(m)) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = __shfl(base, __builtin_ctzll(m));
+    return base + __popcll(m & ((1ull << lane) - 1ull));
+  };
+  const unsigned long long* v = T.sums + s * (2 * Q_COUNT);
+  const unsigned long long a = place(f_all != NONE32, &scalars[D_LISTED]);
+  if (f_all != NONE32 && a < cap) out_all[a] = PairOut{key, {v[0], v[1], v[2], v[3]}, f_all};
+  const unsigned long long b = place(f_kept != NONE32, &scalars[D_LISTED_KEPT]);
+  if (f_kept != NONE32 && b < cap) out_kept[b] = PairOut{key, {v[4], v[5], v[6], v[7]}, f_kept};
+}
+
+struct DevCols {
+  const uint32_t *q_id, *t_id, *start[2], *end[2], *seq_genome;
+  const uint8_t* status;
+};
+
+// inside an arena frame
+int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_breadth_result* all, swg_breadth_result* kept) {
+  hipStream_t st = ctx->stream;
+  const char* knob = std::getenv("SWG_BREADTH_HASH");  // test knob: the hashed segment set and pair table at any size
+  const bool force_hash = knob && knob[0] == '1';
+  const uint64_t ntiles = (n + TILE - 1) / TILE;
+  unsigned long long* scalars = swg_alloc<unsigned long long>(ctx, D_TOTAL);
+  uint64_t* keys = swg_alloc<uint64_t>(ctx, n);
+  uint64_t* keys_alt = swg_alloc<uint64_t>(ctx, n);
+  uint32_t* vals = swg_alloc<uint32_t>(ctx, n);
+  uint32_t* vals_alt = swg_alloc<uint32_t>(ctx, n);
+  uint32_t* ends = swg_alloc<uint32_t>(ctx, n);
+  unsigned long long* tile_max = swg_alloc<unsigned long long>(ctx, 2 * ntiles);
+  // segments: the product while it (and the sentinel one past it) fits 32 bits, else slots of a set with room for twice the
+  // segments that can occur -- never more than 2^31 slots, so that slot and sentinel fit too (n < 2^31: a free slot always comes)
+  const uint64_t products = (uint64_t)n_seq * G;
+  SegMap M{};
+  M.G = G;
+  if (products <= 0xffffffffull && !force_hash) {
+    M.sentinel = (uint32_t)products;
+  } else {
+    const uint64_t want = pow2_at_least(2 * (products < n ? products : n));
+    const uint64_t set_cap = want < (uint64_t(1) << 31) ? want : uint64_t(1) << 31;
+    M.set_keys = swg_alloc<unsigned long long>(ctx, set_cap);
+    M.set_mask = (uint32_t)(set_cap - 1);
+    M.sentinel = (uint32_t)set_cap;
+  }
+  SWG_CHECK_ARENA(ctx);
+  SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
+  const int end_bit = 32 + swg_bits_for(M.sentinel);
+  const unsigned grid_n = (unsigned)((n + TB - 1) / TB), grid_t = (unsigned)ntiles;
+  BreadthTable T{};
+  uint64_t cap = 1;
+  PairOut *out_all = nullptr, *out_kept = nullptr;
+  for (int axis = 0; axis < 2; ++axis) {
+    if (M.set_keys) SWG_HIP(ctx, hipMemsetAsync(M.set_keys, 0xff, ((size_t)M.set_mask + 1) * sizeof(unsigned long long), st));
+    if (axis == 0)
+      SWG_LAUNCH(ctx, "breadth_keys", breadth_keys_kernel<0><<<grid_n, TB, 0, st>>>(n, d.q_id, d.t_id, d.start[0], d.status, d.seq_genome,
+                                                                                     n_seq, M, keys, vals, scalars));
+    else
+      SWG_LAUNCH(ctx, "breadth_keys", breadth_keys_kernel<1><<<grid_n, TB, 0, st>>>(n, d.q_id, d.t_id, d.start[1], d.status, d.seq_genome,
+                                                                                     n_seq, M, keys, vals, scalars));
+    SWG_KERNEL_CHECK(ctx);
+    {  // (the profiler sees the axis' sort as one entry too: with swg_profile_select, the sort of this call's pairs on its own)
+      swg_prof_scope sort_scope(ctx, axis == 0 ? "breadth_sort_q" : "breadth_sort_t");
+      SWG_TRY(swg_radix_sort_pairs(ctx, &keys, &vals, &keys_alt, &vals_alt, n, 0, end_bit));
+    }
+    SWG_LAUNCH(ctx, "breadth_gather", breadth_gather_kernel<<<grid_t, TB, 0, st>>>(n, keys, vals, d.end[axis], M.sentinel, ends, tile_max, ntiles,
+                                                                                     axis == 0 ? scalars + D_SEGMENTS : nullptr));
+    SWG_KERNEL_CHECK(ctx);
+    if (axis == 0) {
+      uint64_t h[2];
+      SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, 2));
+      if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: a sequence id >= n_seq or a genome id >= n_genome");
+      // genome pairs that occur <= segments of the query axis (every pair has one)
+      const uint64_t g2 = (uint64_t)G * G;
+      const uint64_t pairs_max = g2 < h[D_SEGMENTS] ? g2 : h[D_SEGMENTS];
+      if (g2 <= DENSE_LIMIT && !force_hash) {
+        T.slots = g2;
+      } else {
+        T.slots = pow2_at_least(2 * pairs_max);
+        T.mask = (uint32_t)(T.slots - 1);
+        T.keys = swg_alloc<unsigned long long>(ctx, T.slots);
+      }
+      T.sums = swg_alloc<unsigned long long>(ctx, T.slots * 2 * Q_COUNT);
+      T.first = swg_alloc<uint32_t>(ctx, T.slots * 2);
+      cap = pairs_max ? pairs_max : 1;
+      out_all = swg_alloc<PairOut>(ctx, cap);
+      out_kept = swg_alloc<PairOut>(ctx, d.status ? cap : 1);
+      SWG_CHECK_ARENA(ctx);
+      if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
+      SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * 2 * Q_COUNT * sizeof(unsigned long long), st));
+      SWG_HIP(ctx, hipMemsetAsync(T.first, 0xff, T.slots * 2 * sizeof(uint32_t), st));
+    }
+    SWG_TRY(swg_inclusive_max_scan_u64(ctx, reinterpret_cast<uint64_t*>(tile_max), reinterpret_cast<uint64_t*>(tile_max), ntiles));
+    if (d.status)
+      SWG_TRY(swg_inclusive_max_scan_u64(ctx, reinterpret_cast<uint64_t*>(tile_max + ntiles), reinterpret_cast<uint64_t*>(tile_max + ntiles), ntiles));
+    if (axis == 0)
+      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<0><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, d.seq_genome, T));
+    else
+      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<1><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, d.seq_genome, T));
+    SWG_KERNEL_CHECK(ctx);
+  }
+  SWG_LAUNCH(ctx, "breadth_collect",
+             breadth_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, cap, out_all, out_kept, scalars));
+  SWG_KERNEL_CHECK(ctx);
+  uint64_t h[D_TOTAL];
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_TOTAL));
+  if (h[D_LISTED] > cap || h[D_LISTED_KEPT] > cap)
+    return swg_set_error(ctx, SWG_ERR_HIP, "breadth: internal: %llu genome pairs listed, %llu expected at most",
+                         (unsigned long long)h[D_LISTED], (unsigned long long)cap);
+  std::vector<PairOut> list[2];
+  list[0].resize(h[D_LISTED]);
+  list[1].resize(d.status ? h[D_LISTED_KEPT] : 0);
+  if (!list[0].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[0].data(), out_all, list[0].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+  if (!list[1].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[1].data(), out_kept, list[1].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
+  SWG_HIP(ctx, hipStreamSynchronize(st));
+  swg_breadth_result* res[2] = {all, d.status ? kept : nullptr};
+  for (int s = 0; s < 2; ++s) {
+    if (!res[s]) continue;
+    std::sort(list[s].begin(), list[s].end(), [](const PairOut& a, const PairOut& b) { return a.first < b.first; });
+    res[s]->pairs.resize(list[s].size());
+    for (size_t k = 0; k < list[s].size(); ++k) {
+      const PairOut& o = list[s][k];
+      res[s]->pairs[k] = swg_breadth_pair{(uint32_t)(o.key / G), (uint32_t)(o.key % G), o.v[Q_BASES], o.v[T_BASES], o.v[Q_UNION], o.v[T_UNION], o.first};
+    }
+  }
+  return SWG_OK;
+}
+
+void hand_over(const swg_breadth_result& r, swg_breadth_counts* c) {
+  if (!c) return;
+  c->n_pairs = r.pairs.size();
+  if (c->pairs && c->n_pairs <= c->pair_capacity) std::copy(r.pairs.begin(), r.pairs.end(), c->pairs);
+}
+
+int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                swg_breadth_counts* all, swg_breadth_counts* kept) {
+  if (!ctx) return SWG_ERR_INVALID;
+  try {
+    swg_breadth_result ra, rk;
+    SWG_TRY(swg_breadth_run(ctx, rec, on_device, seq_genome, n_genome, status, all ? &ra : nullptr, kept && status ? &rk : nullptr));
+    hand_over(ra, all);
+    if (status) hand_over(rk, kept);
+    return SWG_OK;
+  } catch (const std::bad_alloc&) {
+    return swg_set_error(ctx, SWG_ERR_OOM, "out of host memory");
+  }
+}
+
+}  // namespace
+
+int swg_breadth_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome,
+                    const uint8_t* status, swg_breadth_result* all, swg_breadth_result* kept) {
+  if (!ctx) return SWG_ERR_INVALID;
+  if (!rec) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: NULL records");
+  const uint64_t n = rec->n;
+  const uint32_t n_seq = rec->n_seq;
+  if (all) all->pairs.clear();
+  if (kept) kept->pairs.clear();
+  if (n == 0) return SWG_OK;
+  if (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->t_start || !rec->t_end || !seq_genome)
+    return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: NULL column (q_id, t_id, the four coordinates and seq_genome are read)");
+  if (n_seq == 0 || n_genome == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: records without sequences or genomes");
+  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: 2^31 records or more in one call");
+  if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: more than 2^31 sequences");
+  SWG_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (ctx->arena_cap == 0) {
+    const size_t want = (size_t)n * 64 + (size_t(8) << 20), budget = swg_arena_budget(ctx);
+    SWG_TRY(swg_arena_reserve(ctx, want < budget ? want : budget));
+  }
+  return swg_run_with_arena(ctx, [&]() -> int {
+    DevCols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, status};
+    if (!on_device) {
+      uint32_t* col[6];
+      for (auto& c : col) c = swg_alloc<uint32_t>(ctx, n);
+      uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
+      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
+      SWG_CHECK_ARENA(ctx);
+      const uint32_t* src[6] = {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end};
+      for (int k = 0; k < 6; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
+      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, g, s8};
+    }
+    return breadth_device(ctx, n, n_seq, n_genome, d, all, kept);
+  });
+}
+
+extern "C" int swg_breadth_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                   const uint8_t* status, swg_breadth_counts* all, swg_breadth_counts* kept) {
+  return records_abi(ctx, rec, false, seq_genome, n_genome, status, all, kept);
+}
+
+extern "C" int swg_breadth_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                          const uint8_t* status, swg_breadth_counts* all, swg_breadth_counts* kept) {
+  return records_abi(ctx, rec, true, seq_genome, n_genome, status, all, kept);
+}
+
+// The breadth report of an open PAF: records and genome map from the handle, the integers from the device, the genome sizes as
+// swg_paf_alnstats derives them -- the last line per sequence and set comes from the alnstats kernels, its length from the
+// handle's text (host/paf_io.cpp) -- and the text from host/alnstats.cpp.  Errors: swg_alnstats_last_error().
+extern "C" int swg_paf_breadth(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int detailed, char** out_text, uint64_t* out_len) {
+  if (out_text) *out_text = nullptr;
+  if (out_len) *out_len = 0;
+  if (!p || !out_text || !out_len) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_breadth: NULL argument");
+  const uint64_t n = swg_paf_records(p)->n;
+  if (n && !ctx) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_breadth: NULL context");
+  if (swg_paf_seq_offsets(p) || swg_paf_record_offsets(p, 0))
+    return swg_alnstats_error(SWG_ERR_UNSUPPORTED, "swg_paf_breadth: the file has a value >= 2^32, its columns are rebased: breadth of 64-bit columns is not supported");
+  try {
+    swg_records rec;
+    std::vector<uint32_t> col10;
+    const uint32_t* seq_genome = nullptr;
+    SWG_TRY(swg_paf_stats_prepare(p, &rec, &col10, &seq_genome));
+    swg_alnstats_result stats[2];
+    swg_breadth_result res[2];
+    if (n) {
+      int rc = swg_alnstats_run(ctx, &rec, false, seq_genome, rec.n_genome_last, status, &stats[0], status ? &stats[1] : nullptr);
+      if (rc == SWG_OK) rc = swg_breadth_run(ctx, &rec, false, seq_genome, rec.n_genome_last, status, &res[0], status ? &res[1] : nullptr);
+      if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+    }
+    std::vector<std::string> gname;
+    std::vector<uint64_t> gsize[2];
+    swg_paf_stats_genome_names(p, &gname);
+    for (int k = 0; k < (status ? 2 : 1); ++k) SWG_TRY(swg_paf_stats_genome_sizes(p, stats[k], &gsize[k]));
+    return swg_breadth_report(gname, res, gsize, status ? 2 : 1, detailed != 0, out_text, out_len);
+  } catch (const std::bad_alloc&) {
+    return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+  }
+}
