@@ -14,8 +14,9 @@
 //   alnstats_collect   the occupied entries of the genome-pair table as a list (the host orders it by first record).
 //
 // The genome-pair table is keyed by gq * G + gt under ANY sequence -> genome map (a parameter: alnstats' last-'#' rule here,
-// the filter's two-part prefix for whoever needs per-pair sums next): dense G x G while that is small, open addressing over
-// the pairs that occur beyond it -- at most the distinct (q_id, t_id) pairs, which the first kernel has counted by then.
+// the filter's two-part prefix for the tree sparsification): dense G x G while that is small, open addressing over the pairs
+// that occur beyond it -- at most the distinct (q_id, t_id) pairs, which the first kernel has counted by then.  The table, its
+// LDS staging and its listing are swg_pair_table.h's, shared with swg_sparsify.hip and swg_breadth.hip.
 // Integer atomics only; no floating point.
 #include <algorithm>
 #include <new>
@@ -26,36 +27,14 @@
 
 namespace {
 
-using namespace swg_pair_table;  // TB, LSLOTS, EMPTY, hash32, table_slot, lds_slot, run_end, lane_range, run_sum, wave_sum
+using namespace swg_pair_table;  // the genome-pair table, the run and wavefront helpers, the host entry helpers
 constexpr unsigned long long KEPT_BIT = 1ull << 63;
 enum { S_MAPPINGS = 0, S_BASES, S_MATCHES, S_SELF, S_INTER_GENOME, S_INTER_CHR, S_COUNT };
 // device scalars: [set][S_COUNT], then distinct pairs [2], listed genome pairs [2], bad-id flag
 enum { D_DISTINCT = 2 * S_COUNT, D_LISTED = D_DISTINCT + 2, D_BAD = D_LISTED + 2, D_TOTAL };
 
-struct StatTable {
-  unsigned long long* keys;  // hashed: [mask + 1], EMPTY = free; nullptr = dense (slot = key)
-  unsigned long long* sums;  // [slots][4]: bases ALL, matches ALL, bases KEPT, matches KEPT
-  uint32_t* first;           // [slots][2]: smallest record index ALL, KEPT (NONE32 = none)
-  uint32_t mask;
-  uint64_t slots;
-};
-struct PairOut {  // one listed genome pair
-  unsigned long long key, bases, matches, first;
-};
-
-__device__ __forceinline__ uint64_t stat_slot(const StatTable& t, unsigned long long key) {  // inserts when absent
-  return t.keys ? table_slot(t.keys, t.mask, key) : key;
-}
-
-__device__ __forceinline__ void stat_add(const StatTable& t, unsigned long long key, const unsigned long long v[4], uint32_t f_all,
-                                         uint32_t f_kept) {
-  const uint64_t s = stat_slot(t, key);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (v[j]) atomicAdd(&t.sums[s * 4 + j], v[j]);
-  atomicMin(&t.first[s * 2], f_all);
-  if (f_kept != NONE32) atomicMin(&t.first[s * 2 + 1], f_kept);
-}
+using StatTable = PairTable<4, true>;  // sums: bases ALL, matches ALL, bases KEPT, matches KEPT
+using StatList = PairList<4, true>;    // entries: bases, matches, first record of the set
 
 // ---- distinct (q_id, t_id) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TB) void alnstats_seqpair_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
@@ -118,16 +97,10 @@ __global__ __launch_bounds__(TB) void alnstats_reduce_kernel(uint64_t n, uint64_
                                                              uint32_t n_seq, uint32_t n_genome, StatTable T,
                                                              uint32_t* __restrict__ seq_last,  // [2][n_seq]: 2 * record + side + 1, 0 = none
                                                              unsigned long long* __restrict__ scalars) {
-  __shared__ unsigned long long l_key[LSLOTS];
-  __shared__ unsigned long long l_sum[LSLOTS][4];
-  __shared__ uint32_t l_first[LSLOTS][2];
+  __shared__ LdsTable<4, true> l_pairs;
   __shared__ unsigned long long l_red[WAVES][2 * S_COUNT];
   __shared__ uint32_t l_bad;
-  for (int s = threadIdx.x; s < LSLOTS; s += TB) {
-    l_key[s] = EMPTY;
-    l_sum[s][0] = l_sum[s][1] = l_sum[s][2] = l_sum[s][3] = 0;
-    l_first[s][0] = l_first[s][1] = NONE32;
-  }
+  l_pairs.clear();
   if (threadIdx.x == 0) l_bad = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -188,22 +161,13 @@ __global__ __launch_bounds__(TB) void alnstats_reduce_kernel(uint64_t n, uint64_
     if (head && key != EMPTY) {
       const uint64_t kf = keptmask & lane_range(lane, end);
       const uint32_t f_all = (uint32_t)i, f_kept = kf ? (uint32_t)(i - lane + __builtin_ctzll(kf)) : NONE32;
-      const int h = lds_slot(l_key, key);
-      const bool placed = h >= 0;
-      if (placed) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (v[j]) atomicAdd(&l_sum[h][j], v[j]);
-        atomicMin(&l_first[h][0], f_all);
-        if (f_kept != NONE32) atomicMin(&l_first[h][1], f_kept);
-      }
-      if (!placed) stat_add(T, key, v, f_all, f_kept);  // more pairs in this share than the LDS table takes (shuffled input)
+      if (!l_pairs.add(key, v, f_all, f_kept))
+        table_add<4, true>(T, key, v, 0, f_all, f_kept);  // more pairs in this share than the LDS table takes (shuffled input)
     }
   }
   if (bad) l_bad = 1;
   __syncthreads();
-  for (int s = threadIdx.x; s < LSLOTS; s += TB)
-    if (l_key[s] != EMPTY) stat_add(T, l_key[s], l_sum[s], l_first[s][0], l_first[s][1]);
+  l_pairs.flush(T, 0);
 #pragma unroll
   for (int k = 0; k < 2 * S_COUNT; ++k) {
     const unsigned long long s = wave_sum(acc[k / S_COUNT][k % S_COUNT]);
@@ -219,27 +183,7 @@ __global__ __launch_bounds__(TB) void alnstats_reduce_kernel(uint64_t n, uint64_
 }
 
 // ---- the occupied genome pairs as lists ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TB) void alnstats_collect_kernel(StatTable T, uint64_t cap, PairOut* __restrict__ out_all, PairOut* __restrict__ out_kept,
-                                                              unsigned long long* __restrict__ scalars) {
-  const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const bool in = s < T.slots;
-  const uint32_t f_all = in ? T.first[s * 2] : NONE32, f_kept = in ? T.first[s * 2 + 1] : NONE32;
-  const unsigned long long key = !in ? 0 : T.keys ? T.keys[s] : s;
-  // one atomic per wavefront and list: the lanes that hold an entry take consecutive places
-  auto place = [&](bool have, unsigned long long* counter) -> unsigned long long {
-    const uint64_t m = __ballot(have);
-    if (!m) return 0;
-    unsigned long long base = 0;
-    if (lane == __builtin_ctzll(m)) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-    base = __shfl(base, __builtin_ctzll(m));
-    return base + __popcll(m & ((1ull << lane) - 1ull));
-  };
-  const unsigned long long a = place(f_all != NONE32, &scalars[D_LISTED]);
-  if (f_all != NONE32 && a < cap) out_all[a] = PairOut{key, T.sums[s * 4], T.sums[s * 4 + 1], f_all};
-  const unsigned long long k = place(f_kept != NONE32, &scalars[D_LISTED + 1]);
-  if (f_kept != NONE32 && k < cap) out_kept[k] = PairOut{key, T.sums[s * 4 + 2], T.sums[s * 4 + 3], f_kept};
-}
+__global__ __launch_bounds__(TB) void alnstats_collect_kernel(StatTable T, StatList L) { list_slots(T, L); }
 
 struct DevCols {
   const uint32_t *q_id, *t_id, *q_start, *q_end, *matches, *seq_genome;
@@ -260,60 +204,31 @@ int alnstats_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const 
   SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
   SWG_HIP(ctx, hipMemsetAsync(seq_last, 0, 2 * (size_t)n_seq * sizeof(uint32_t), st));
   SWG_HIP(ctx, hipMemsetAsync(set_keys, 0xff, set_cap * sizeof(unsigned long long), st));
-  const uint64_t tiles = (n + TB - 1) / TB;
-  const uint64_t max_groups = (uint64_t)ctx->num_cu * 8;
-  {
-    const unsigned grid = (unsigned)(tiles < max_groups ? tiles : max_groups);
-    SWG_LAUNCH(ctx, "alnstats_seqpair", alnstats_seqpair_kernel<<<grid, TB, 0, st>>>(n, d.q_id, d.t_id, d.status, n_seq, set_keys,
-                                                                                       (uint32_t)(set_cap - 1), scalars));
-    SWG_KERNEL_CHECK(ctx);
-  }
+  SWG_LAUNCH(ctx, "alnstats_seqpair", alnstats_seqpair_kernel<<<grid_for(ctx, n), TB, 0, st>>>(n, d.q_id, d.t_id, d.status, n_seq, set_keys,
+                                                                                                 (uint32_t)(set_cap - 1), scalars));
+  SWG_KERNEL_CHECK(ctx);
   uint64_t distinct[2];
   SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars) + D_DISTINCT, distinct, 2));
   // genome pairs that occur <= distinct sequence pairs
   const uint64_t g2 = (uint64_t)G * G;
   const uint64_t pairs_max = g2 < distinct[0] ? g2 : distinct[0];
-  StatTable T{};
-  if (g2 <= DENSE_LIMIT) {
-    T.slots = g2;
-  } else {
-    T.slots = pow2_at_least(2 * pairs_max);
-    T.mask = (uint32_t)(T.slots - 1);
-    T.keys = swg_alloc<unsigned long long>(ctx, T.slots);
-  }
-  T.sums = swg_alloc<unsigned long long>(ctx, T.slots * 4);
-  T.first = swg_alloc<uint32_t>(ctx, T.slots * 2);
-  const uint64_t cap = pairs_max ? pairs_max : 1;
-  PairOut* out_all = swg_alloc<PairOut>(ctx, cap);
-  PairOut* out_kept = swg_alloc<PairOut>(ctx, d.status ? cap : 1);
-  SWG_CHECK_ARENA(ctx);
-  if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
-  SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * 4 * sizeof(unsigned long long), st));
-  SWG_HIP(ctx, hipMemsetAsync(T.first, 0xff, T.slots * 2 * sizeof(uint32_t), st));
-  {
-    const uint64_t groups = tiles < max_groups ? tiles : max_groups;
-    const uint64_t per_group = (tiles + groups - 1) / groups * TB;
-    const unsigned grid = (unsigned)((n + per_group - 1) / per_group);
-    SWG_LAUNCH(ctx, "alnstats_reduce", alnstats_reduce_kernel<<<grid, TB, 0, st>>>(n, per_group, d.q_id, d.t_id, d.q_start, d.q_end, d.matches,
-                                                                                     d.status, d.seq_genome, n_seq, G, T, seq_last, scalars));
-    SWG_KERNEL_CHECK(ctx);
-  }
-  SWG_LAUNCH(ctx, "alnstats_collect",
-             alnstats_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, cap, out_all, out_kept, scalars));
+  StatTable T;
+  StatList L;
+  SWG_TRY(table_create(ctx, G, pairs_max, false, d.status != nullptr, scalars + D_LISTED, &T, &L));
+  const Share share = share_for(ctx, n);
+  SWG_LAUNCH(ctx, "alnstats_reduce", alnstats_reduce_kernel<<<share.grid, TB, 0, st>>>(n, share.per_group, d.q_id, d.t_id, d.q_start, d.q_end,
+                                                                                         d.matches, d.status, d.seq_genome, n_seq, G, T, seq_last,
+                                                                                         scalars));
+  SWG_KERNEL_CHECK(ctx);
+  SWG_LAUNCH(ctx, "alnstats_collect", alnstats_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, L));
   SWG_KERNEL_CHECK(ctx);
   uint64_t h[D_TOTAL];
   SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_TOTAL));
   if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "alnstats: a sequence id >= n_seq or a genome id >= n_genome");
-  if (h[D_LISTED] > cap || h[D_LISTED + 1] > cap)
-    return swg_set_error(ctx, SWG_ERR_HIP, "alnstats: internal: %llu genome pairs listed, %llu expected at most",
-                         (unsigned long long)h[D_LISTED], (unsigned long long)cap);
+  std::vector<StatList::Entry> list[2];
+  SWG_TRY(list_fetch(ctx, "alnstats", L, h + D_LISTED, list));
   std::vector<uint32_t> last((size_t)2 * n_seq);
-  std::vector<PairOut> list[2];
-  list[0].resize(h[D_LISTED]);
-  list[1].resize(d.status ? h[D_LISTED + 1] : 0);
   SWG_HIP(ctx, hipMemcpyAsync(last.data(), seq_last, last.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (!list[0].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[0].data(), out_all, list[0].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
-  if (!list[1].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[1].data(), out_kept, list[1].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
   SWG_HIP(ctx, hipStreamSynchronize(st));
   swg_alnstats_result* res[2] = {all, d.status ? kept : nullptr};
   for (int s = 0; s < 2; ++s) {
@@ -327,11 +242,10 @@ int alnstats_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const 
     r->inter_genome = c[S_INTER_GENOME];
     r->inter_chromosomal = c[S_INTER_CHR];
     r->chr_pair_count = distinct[s];
-    std::sort(list[s].begin(), list[s].end(), [](const PairOut& a, const PairOut& b) { return a.first < b.first; });
     r->pairs.resize(list[s].size());
     for (size_t k = 0; k < list[s].size(); ++k) {
-      const PairOut& o = list[s][k];
-      r->pairs[k] = swg_alnstats_pair_counts{(uint32_t)(o.key / G), (uint32_t)(o.key % G), o.bases, o.matches, o.first};
+      const StatList::Entry& o = list[s][k];
+      r->pairs[k] = swg_alnstats_pair_counts{(uint32_t)(o.key / G), (uint32_t)(o.key % G), o.v[0], o.v[1], o.first};
     }
     r->seq_last.resize(n_seq);
     for (uint32_t q = 0; q < n_seq; ++q) {
@@ -348,9 +262,8 @@ void clear_result(swg_alnstats_result* r, uint32_t n_seq) {
   r->seq_last.assign(n_seq, UINT64_MAX);
 }
 
-int hand_over(swg_ctx* ctx, const swg_alnstats_result& r, swg_alnstats_counts* c) {
-  (void)ctx;
-  if (!c) return SWG_OK;
+void hand_over(const swg_alnstats_result& r, swg_alnstats_counts* c) {
+  if (!c) return;
   c->total_mappings = r.total_mappings;
   c->total_bases = r.total_bases;
   c->total_matches = r.total_matches;
@@ -361,7 +274,6 @@ int hand_over(swg_ctx* ctx, const swg_alnstats_result& r, swg_alnstats_counts* c
   c->n_pairs = r.pairs.size();
   if (c->pairs && c->n_pairs <= c->pair_capacity) std::copy(r.pairs.begin(), r.pairs.end(), c->pairs);
   if (c->seq_last) std::copy(r.seq_last.begin(), r.seq_last.end(), c->seq_last);
-  return SWG_OK;
 }
 
 int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
@@ -370,8 +282,8 @@ int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   try {
     swg_alnstats_result ra, rk;
     SWG_TRY(swg_alnstats_run(ctx, rec, on_device, seq_genome, n_genome, status, all ? &ra : nullptr, kept && status ? &rk : nullptr));
-    SWG_TRY(hand_over(ctx, ra, all));
-    if (status) SWG_TRY(hand_over(ctx, rk, kept));
+    hand_over(ra, all);
+    if (status) hand_over(rk, kept);
     return SWG_OK;
   } catch (const std::bad_alloc&) {
     return swg_set_error(ctx, SWG_ERR_OOM, "out of host memory");
@@ -395,24 +307,15 @@ int swg_alnstats_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const
   if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "alnstats: 2^31 records or more in one call");
   if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "alnstats: more than 2^31 sequences");
   SWG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  if (ctx->arena_cap == 0) {
-    const size_t want = (size_t)n * 64 + (size_t(8) << 20), budget = swg_arena_budget(ctx);
-    SWG_TRY(swg_arena_reserve(ctx, want < budget ? want : budget));
-  }
+  SWG_TRY(reserve_first(ctx, (size_t)n * 64 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     DevCols d{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches, seq_genome, status};
     if (!on_device) {
-      uint32_t* col[5];
-      for (auto& c : col) c = swg_alloc<uint32_t>(ctx, n);
-      uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
-      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-      SWG_CHECK_ARENA(ctx);
-      const uint32_t* src[5] = {rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches};
-      for (int k = 0; k < 5; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
-      d = DevCols{col[0], col[1], col[2], col[3], col[4], g, s8};
+      const uint32_t* col[5];
+      uint8_t* s8;
+      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches}, seq_genome, status != nullptr, status,
+                            col, &d.seq_genome, &s8));
+      d = DevCols{col[0], col[1], col[2], col[3], col[4], d.seq_genome, s8};
     }
     return alnstats_device(ctx, n, n_seq, n_genome, d, all, kept);
   });

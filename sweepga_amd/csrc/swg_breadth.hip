@@ -39,29 +39,21 @@
 
 namespace {
 
-using namespace swg_pair_table;  // TB, WAVES, LSLOTS, EMPTY, NONE32, table_slot, lds_slot, run_end, run_sum, wave_sum
+using namespace swg_pair_table;  // the genome-pair table, the run and wavefront helpers, the host entry helpers
 constexpr int ITEMS = 4;                   // consecutive sorted records per thread
 constexpr int TILE = TB * ITEMS;           // ... per work-group
 constexpr uint32_t KEPT_FLAG = 0x80000000u;
 constexpr uint32_t INDEX_MASK = 0x7fffffffu;
 enum { D_BAD = 0, D_SEGMENTS, D_LISTED, D_LISTED_KEPT, D_TOTAL };
-enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // per set
+enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // a listed entry's sums
 
-struct BreadthTable {
-  unsigned long long* keys;  // hashed: [mask + 1], EMPTY = free; nullptr = dense (slot = gq * G + gt)
-  unsigned long long* sums;  // [slots][2][Q_COUNT]: ALL, KEPT
-  uint32_t* first;           // [slots][2]: smallest record index ALL, KEPT (NONE32 = none)
-  uint32_t mask;
-  uint64_t slots;
-};
+using BreadthTable = PairTable<2 * Q_COUNT, true>;  // sums: [axis][bases ALL, union ALL, bases KEPT, union KEPT]
+using BreadthList = PairList<2 * Q_COUNT, true>;   // entries: Q_BASES .. T_UNION and the first record of the set
 struct SegMap {  // segment id -> sequence of the axis * G + genome of the other side
   unsigned long long* set_keys;  // hashed: the set (segment = slot); nullptr = the product itself
   uint32_t set_mask;
   uint32_t G;
   uint32_t sentinel;
-};
-struct PairOut {  // one listed genome pair
-  unsigned long long key, v[Q_COUNT], first;
 };
 
 // ---- keys --------------------------------------------------------------------------------------------------------------
@@ -158,31 +150,12 @@ __global__ __launch_bounds__(TB) void breadth_gather_kernel(uint64_t n, const ui
 }
 
 template <int AXIS>
-__device__ __forceinline__ void table_add(const BreadthTable& T, unsigned long long key, const unsigned long long v[4], uint32_t f_all,
-                                          uint32_t f_kept) {
-  const uint64_t s = T.keys ? table_slot(T.keys, T.mask, key) : key;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)  // v: bases ALL, union ALL, bases KEPT, union KEPT
-    if (v[j]) atomicAdd(&T.sums[s * (2 * Q_COUNT) + (j >> 1) * Q_COUNT + AXIS * 2 + (j & 1)], v[j]);
-  if (AXIS == 0) {
-    atomicMin(&T.first[s * 2], f_all);
-    if (f_kept != NONE32) atomicMin(&T.first[s * 2 + 1], f_kept);
-  }
-}
-
-template <int AXIS>
 __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                            const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
                                                            uint64_t ntiles, SegMap M, const uint32_t* __restrict__ seq_genome, BreadthTable T) {
-  __shared__ unsigned long long l_key[LSLOTS];
-  __shared__ unsigned long long l_sum[LSLOTS][4];
-  __shared__ uint32_t l_first[LSLOTS][2];
+  __shared__ LdsTable<4, AXIS == 0> l_pairs;  // (first records: the query axis writes them, the target axis leaves them alone)
   __shared__ unsigned long long l_wave[2][WAVES];
-  for (int s = threadIdx.x; s < LSLOTS; s += TB) {
-    l_key[s] = EMPTY;
-    l_sum[s][0] = l_sum[s][1] = l_sum[s][2] = l_sum[s][3] = 0;
-    l_first[s][0] = l_first[s][1] = NONE32;
-  }
+  l_pairs.clear();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
   uint64_t k[ITEMS];
@@ -291,47 +264,16 @@ __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uin
       }
     }
     if (first_lane && key != EMPTY) {
-      const int h = lds_slot(l_key, key);
-      if (h >= 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (q[j][c]) atomicAdd(&l_sum[h][c], q[j][c]);
-        if (AXIS == 0) {
-          atomicMin(&l_first[h][0], fa);
-          if (fk != NONE32) atomicMin(&l_first[h][1], fk);
-        }
-      } else {
-        table_add<AXIS>(T, key, q[j], fa, fk);  // more pairs in this tile than the LDS table takes
-      }
+      if (!l_pairs.add(key, q[j], fa, fk))
+        table_add<4, AXIS == 0>(T, key, q[j], 4 * AXIS, fa, fk);  // more pairs in this tile than the LDS table takes
     }
   }
   __syncthreads();
-  for (int s = threadIdx.x; s < LSLOTS; s += TB)
-    if (l_key[s] != EMPTY) table_add<AXIS>(T, l_key[s], l_sum[s], l_first[s][0], l_first[s][1]);
+  l_pairs.flush(T, 4 * AXIS);
 }
 
 // ---- the occupied genome pairs as lists ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TB) void breadth_collect_kernel(BreadthTable T, uint64_t cap, PairOut* __restrict__ out_all,
-                                                             PairOut* __restrict__ out_kept, unsigned long long* __restrict__ scalars) {
-  const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const bool in = s < T.slots;
-  const uint32_t f_all = in ? T.first[s * 2] : NONE32, f_kept = in ? T.first[s * 2 + 1] : NONE32;
-  const unsigned long long key = !in ? 0 : T.keys ? T.keys[s] : s;
-  auto place = [&](bool have, unsigned long long* counter) -> unsigned long long {  // consecutive places, one atomic per wavefront
-    const uint64_t m = __ballot(have);
-    if (!m) return 0;
-    unsigned long long base = 0;
-    if (lane == __builtin_ctzll(m)) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-    base = __shfl(base, __builtin_ctzll(m));
-    return base + __popcll(m & ((1ull << lane) - 1ull));
-  };
-  const unsigned long long* v = T.sums + s * (2 * Q_COUNT);
-  const unsigned long long a = place(f_all != NONE32, &scalars[D_LISTED]);
-  if (f_all != NONE32 && a < cap) out_all[a] = PairOut{key, {v[0], v[1], v[2], v[3]}, f_all};
-  const unsigned long long b = place(f_kept != NONE32, &scalars[D_LISTED_KEPT]);
-  if (f_kept != NONE32 && b < cap) out_kept[b] = PairOut{key, {v[4], v[5], v[6], v[7]}, f_kept};
-}
+__global__ __launch_bounds__(TB) void breadth_collect_kernel(BreadthTable T, BreadthList L) { list_slots(T, L); }
 
 struct DevCols {
   const uint32_t *q_id, *t_id, *start[2], *end[2], *seq_genome;
@@ -370,8 +312,7 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
   const int end_bit = 32 + swg_bits_for(M.sentinel);
   const unsigned grid_n = (unsigned)((n + TB - 1) / TB), grid_t = (unsigned)ntiles;
   BreadthTable T{};
-  uint64_t cap = 1;
-  PairOut *out_all = nullptr, *out_kept = nullptr;
+  BreadthList L{};
   for (int axis = 0; axis < 2; ++axis) {
     if (M.set_keys) SWG_HIP(ctx, hipMemsetAsync(M.set_keys, 0xff, ((size_t)M.set_mask + 1) * sizeof(unsigned long long), st));
     if (axis == 0)
@@ -394,23 +335,7 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
       if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: a sequence id >= n_seq or a genome id >= n_genome");
       // genome pairs that occur <= segments of the query axis (every pair has one)
       const uint64_t g2 = (uint64_t)G * G;
-      const uint64_t pairs_max = g2 < h[D_SEGMENTS] ? g2 : h[D_SEGMENTS];
-      if (g2 <= DENSE_LIMIT && !force_hash) {
-        T.slots = g2;
-      } else {
-        T.slots = pow2_at_least(2 * pairs_max);
-        T.mask = (uint32_t)(T.slots - 1);
-        T.keys = swg_alloc<unsigned long long>(ctx, T.slots);
-      }
-      T.sums = swg_alloc<unsigned long long>(ctx, T.slots * 2 * Q_COUNT);
-      T.first = swg_alloc<uint32_t>(ctx, T.slots * 2);
-      cap = pairs_max ? pairs_max : 1;
-      out_all = swg_alloc<PairOut>(ctx, cap);
-      out_kept = swg_alloc<PairOut>(ctx, d.status ? cap : 1);
-      SWG_CHECK_ARENA(ctx);
-      if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
-      SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * 2 * Q_COUNT * sizeof(unsigned long long), st));
-      SWG_HIP(ctx, hipMemsetAsync(T.first, 0xff, T.slots * 2 * sizeof(uint32_t), st));
+      SWG_TRY(table_create(ctx, G, g2 < h[D_SEGMENTS] ? g2 : h[D_SEGMENTS], force_hash, d.status != nullptr, scalars + D_LISTED, &T, &L));
     }
     SWG_TRY(swg_inclusive_max_scan_u64(ctx, reinterpret_cast<uint64_t*>(tile_max), reinterpret_cast<uint64_t*>(tile_max), ntiles));
     if (d.status)
@@ -421,27 +346,18 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
       SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<1><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, d.seq_genome, T));
     SWG_KERNEL_CHECK(ctx);
   }
-  SWG_LAUNCH(ctx, "breadth_collect",
-             breadth_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, cap, out_all, out_kept, scalars));
+  SWG_LAUNCH(ctx, "breadth_collect", breadth_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, L));
   SWG_KERNEL_CHECK(ctx);
   uint64_t h[D_TOTAL];
   SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_TOTAL));
-  if (h[D_LISTED] > cap || h[D_LISTED_KEPT] > cap)
-    return swg_set_error(ctx, SWG_ERR_HIP, "breadth: internal: %llu genome pairs listed, %llu expected at most",
-                         (unsigned long long)h[D_LISTED], (unsigned long long)cap);
-  std::vector<PairOut> list[2];
-  list[0].resize(h[D_LISTED]);
-  list[1].resize(d.status ? h[D_LISTED_KEPT] : 0);
-  if (!list[0].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[0].data(), out_all, list[0].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
-  if (!list[1].empty()) SWG_HIP(ctx, hipMemcpyAsync(list[1].data(), out_kept, list[1].size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
-  SWG_HIP(ctx, hipStreamSynchronize(st));
+  std::vector<BreadthList::Entry> list[2];
+  SWG_TRY(list_fetch(ctx, "breadth", L, h + D_LISTED, list));
   swg_breadth_result* res[2] = {all, d.status ? kept : nullptr};
   for (int s = 0; s < 2; ++s) {
     if (!res[s]) continue;
-    std::sort(list[s].begin(), list[s].end(), [](const PairOut& a, const PairOut& b) { return a.first < b.first; });
     res[s]->pairs.resize(list[s].size());
     for (size_t k = 0; k < list[s].size(); ++k) {
-      const PairOut& o = list[s][k];
+      const BreadthList::Entry& o = list[s][k];
       res[s]->pairs[k] = swg_breadth_pair{(uint32_t)(o.key / G), (uint32_t)(o.key % G), o.v[Q_BASES], o.v[T_BASES], o.v[Q_UNION], o.v[T_UNION], o.first};
     }
   }
@@ -485,24 +401,15 @@ int swg_breadth_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const 
   if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: 2^31 records or more in one call");
   if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: more than 2^31 sequences");
   SWG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  if (ctx->arena_cap == 0) {
-    const size_t want = (size_t)n * 64 + (size_t(8) << 20), budget = swg_arena_budget(ctx);
-    SWG_TRY(swg_arena_reserve(ctx, want < budget ? want : budget));
-  }
+  SWG_TRY(reserve_first(ctx, (size_t)n * 64 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     DevCols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, status};
     if (!on_device) {
-      uint32_t* col[6];
-      for (auto& c : col) c = swg_alloc<uint32_t>(ctx, n);
-      uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
-      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-      SWG_CHECK_ARENA(ctx);
-      const uint32_t* src[6] = {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end};
-      for (int k = 0; k < 6; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
-      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, g, s8};
+      const uint32_t* col[6];
+      uint8_t* s8;
+      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end}, seq_genome,
+                            status != nullptr, status, col, &d.seq_genome, &s8));
+      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, d.seq_genome, s8};
     }
     return breadth_device(ctx, n, n_seq, n_genome, d, all, kept);
   });

@@ -3,8 +3,8 @@
 //
 //   sparsify_pairsum   per unordered pair of DIFFERENT genomes (key = smaller id * G + larger id) sum(matches), sum(block_len)
 //                      and the record count, u64: runs of one pair along a wavefront summed towards the run's first lane, a small
-//                      LDS table per work-group, one atomic per (work-group, pair, quantity) -- the structure of alnstats_reduce,
-//                      shared through swg_pair_table.h.  Dense G x G table up to 2^20 entries, open addressing beyond.
+//                      LDS table per work-group, one atomic per (work-group, pair, quantity), dense G x G table up to 2^20 entries,
+//                      open addressing beyond: the scheme of swg_pair_table.h.
 //   sparsify_collect   the pairs that occur as a list.  The host turns it into (pair sums, prefixes) and runs THE selection
 //                      (swg_tree_select, host/tree_filter.cpp): the strings decide the canonical order of a pair, the tie order and
 //                      the hash, the device never sees one.
@@ -30,39 +30,21 @@
 
 namespace {
 
-using namespace swg_pair_table;
+using namespace swg_pair_table;  // the genome-pair table, the run and wavefront helpers, the host entry helpers
 
 enum { D_LISTED = 0, D_BAD, D_KEPT, D_TOTAL };
 
-struct SumTable {
-  unsigned long long* keys;  // hashed: [mask + 1], EMPTY = free; nullptr = dense (slot = key)
-  unsigned long long* sums;  // [slots][3]: matches, block length, records
-  uint32_t mask;
-  uint64_t slots;
-};
-struct PairOut {  // one listed genome pair
-  unsigned long long key, matches, block, count;
-};
-
-__device__ __forceinline__ void sum_add(const SumTable& t, unsigned long long key, const unsigned long long v[3]) {
-  const uint64_t s = t.keys ? table_slot(t.keys, t.mask, key) : key;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    if (v[j]) atomicAdd(&t.sums[s * 3 + j], v[j]);
-}
+using SumTable = PairTable<3, false>;  // sums, and the entries of the one list: matches, block length, records
+using SumList = PairList<3, false>;
 
 __global__ __launch_bounds__(TB) void sparsify_pairsum_kernel(uint64_t n, uint64_t per_group, const uint32_t* __restrict__ q_id,
                                                               const uint32_t* __restrict__ t_id, const uint32_t* __restrict__ matches,
                                                               const uint32_t* __restrict__ block_len, const uint32_t* __restrict__ seq_genome,
                                                               uint32_t n_seq, uint32_t n_genome, SumTable T,
                                                               unsigned long long* __restrict__ scalars) {
-  __shared__ unsigned long long l_key[LSLOTS];
-  __shared__ unsigned long long l_sum[LSLOTS][3];
+  __shared__ LdsTable<3, false> l_pairs;
   __shared__ uint32_t l_bad;
-  for (int s = threadIdx.x; s < LSLOTS; s += TB) {
-    l_key[s] = EMPTY;
-    l_sum[s][0] = l_sum[s][1] = l_sum[s][2] = 0;
-  }
+  l_pairs.clear();
   if (threadIdx.x == 0) l_bad = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -92,37 +74,16 @@ __global__ __launch_bounds__(TB) void sparsify_pairsum_kernel(uint64_t n, uint64
     if (__ballot(key != EMPTY) == 0) continue;  // wavefront-uniform
     run_sum(v, lane, run_end(heads, lane));
     if (head && key != EMPTY) {
-      const int h = lds_slot(l_key, key);
-      if (h >= 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (v[j]) atomicAdd(&l_sum[h][j], v[j]);
-      } else {
-        sum_add(T, key, v);  // more pairs in this share than the LDS table takes (shuffled input)
-      }
+      if (!l_pairs.add(key, v)) table_add<3, false>(T, key, v, 0);  // more pairs in this share than the LDS table takes (shuffled input)
     }
   }
   if (bad) l_bad = 1;
   __syncthreads();
-  for (int s = threadIdx.x; s < LSLOTS; s += TB)
-    if (l_key[s] != EMPTY) sum_add(T, l_key[s], l_sum[s]);
+  l_pairs.flush(T, 0);
   if (threadIdx.x == 0 && l_bad) atomicOr(&scalars[D_BAD], 1ull);
 }
 
-__global__ __launch_bounds__(TB) void sparsify_collect_kernel(SumTable T, uint64_t cap, PairOut* __restrict__ out,
-                                                              unsigned long long* __restrict__ scalars) {
-  const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const unsigned long long count = s < T.slots ? T.sums[s * 3 + 2] : 0;
-  // one atomic per wavefront: the lanes that hold an entry take consecutive places
-  const uint64_t m = __ballot(count != 0);
-  if (!m) return;
-  unsigned long long base = 0;
-  if (lane == __builtin_ctzll(m)) base = atomicAdd(&scalars[D_LISTED], (unsigned long long)__popcll(m));
-  base = __shfl(base, __builtin_ctzll(m));
-  const unsigned long long at = base + __popcll(m & ((1ull << lane) - 1ull));
-  if (count != 0 && at < cap) out[at] = PairOut{T.keys ? T.keys[s] : s, T.sums[s * 3], T.sums[s * 3 + 1], count};
-}
+__global__ __launch_bounds__(TB) void sparsify_collect_kernel(SumTable T, SumList L) { list_slots(T, L); }
 
 // bitmap != nullptr: bit `key` of it; else the open-addressing set (set_keys, set_mask) the host built with hash32
 __global__ __launch_bounds__(TB) void sparsify_mark_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
@@ -195,11 +156,6 @@ __global__ __launch_bounds__(TB) void sparsify_scatter_kernel(uint64_t m, const 
   }
 }
 
-unsigned grid_for(const swg_ctx* ctx, uint64_t items) {  // several times the resident work-groups, never more than the work
-  const uint64_t tiles = (items + TB - 1) / TB, max_groups = (uint64_t)ctx->num_cu * 8;
-  return (unsigned)std::max<uint64_t>(1, std::min(tiles, max_groups));
-}
-
 // ---- the mask --------------------------------------------------------------------------------------------------------------
 struct SelCols {
   const uint32_t *q_id, *t_id, *matches, *block_len, *seq_genome;
@@ -211,54 +167,34 @@ int select_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const Se
   hipStream_t st = ctx->stream;
   *too_big = false;
   unsigned long long* scalars = swg_alloc<unsigned long long>(ctx, D_TOTAL);
-  const uint64_t g2 = (uint64_t)G * G;
   const uint64_t all_pairs = (uint64_t)G * (G - 1) / 2;
   const uint64_t pairs_max = std::max<uint64_t>(1, std::min(all_pairs, n));
-  SumTable T{};
-  if (g2 <= DENSE_LIMIT) {
-    T.slots = g2;
-  } else {
-    T.slots = pow2_at_least(2 * pairs_max);
-    T.mask = (uint32_t)(T.slots - 1);
-    T.keys = swg_alloc<unsigned long long>(ctx, T.slots);
-  }
-  T.sums = swg_alloc<unsigned long long>(ctx, T.slots * 3);
-  PairOut* out = swg_alloc<PairOut>(ctx, pairs_max);
-  SWG_CHECK_ARENA(ctx);
+  SumTable T;
+  SumList L;
+  SWG_TRY(table_create(ctx, G, pairs_max, false, false, scalars + D_LISTED, &T, &L));
   SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
-  if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
-  SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * 3 * sizeof(unsigned long long), st));
-  {
-    const uint64_t tiles = (n + TB - 1) / TB, groups = grid_for(ctx, n);
-    const uint64_t per_group = (tiles + groups - 1) / groups * TB;
-    const unsigned grid = (unsigned)((n + per_group - 1) / per_group);
-    SWG_LAUNCH(ctx, "sparsify_pairsum", sparsify_pairsum_kernel<<<grid, TB, 0, st>>>(n, per_group, d.q_id, d.t_id, d.matches, d.block_len,
-                                                                                       d.seq_genome, n_seq, G, T, scalars));
-    SWG_KERNEL_CHECK(ctx);
-  }
-  SWG_LAUNCH(ctx, "sparsify_collect", sparsify_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, pairs_max, out, scalars));
+  const Share share = share_for(ctx, n);
+  SWG_LAUNCH(ctx, "sparsify_pairsum", sparsify_pairsum_kernel<<<share.grid, TB, 0, st>>>(n, share.per_group, d.q_id, d.t_id, d.matches, d.block_len,
+                                                                                           d.seq_genome, n_seq, G, T, scalars));
+  SWG_KERNEL_CHECK(ctx);
+  SWG_LAUNCH(ctx, "sparsify_collect", sparsify_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, L));
   SWG_KERNEL_CHECK(ctx);
   uint64_t h[D_TOTAL];
   SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_TOTAL));
   if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "tree select: a sequence id >= n_seq or a genome id >= n_genome");
-  if (h[D_LISTED] > pairs_max)
-    return swg_set_error(ctx, SWG_ERR_HIP, "tree select: internal: %llu genome pairs listed, %llu expected at most",
-                         (unsigned long long)h[D_LISTED], (unsigned long long)pairs_max);
-  std::vector<PairOut> list(h[D_LISTED]);
-  if (!list.empty()) {
-    SWG_HIP(ctx, hipMemcpyAsync(list.data(), out, list.size() * sizeof(PairOut), hipMemcpyDeviceToHost, st));
-    SWG_HIP(ctx, hipStreamSynchronize(st));
-  }
+  std::vector<SumList::Entry> lists[1];
+  SWG_TRY(list_fetch(ctx, "tree select", L, h + D_LISTED, lists));
+  const std::vector<SumList::Entry>& list = lists[0];
   // the listing order is whatever the atomics made it: the selection does not depend on it (a total order per genome, one hash per pair)
   std::vector<swg_tree_pair> pairs(list.size());
   for (size_t k = 0; k < list.size(); ++k) {
-    if (list[k].matches >= SWG_TREE_SUM_LIMIT || list[k].block >= SWG_TREE_SUM_LIMIT) {
+    if (list[k].v[0] >= SWG_TREE_SUM_LIMIT || list[k].v[1] >= SWG_TREE_SUM_LIMIT) {
       *too_big = true;
       return SWG_OK;
     }
     uint32_t a = (uint32_t)(list[k].key / G), b = (uint32_t)(list[k].key % G);
     if (prefix[b] < prefix[a]) std::swap(a, b);
-    pairs[k] = swg_tree_pair{a, b, (double)list[k].matches, (double)list[k].block};
+    pairs[k] = swg_tree_pair{a, b, (double)list[k].v[0], (double)list[k].v[1]};
   }
   std::vector<uint8_t> selected;
   swg_tree_select(prefix, pairs, k_nearest, k_farthest, random_fraction, &selected);
@@ -268,8 +204,8 @@ int select_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const Se
   uint32_t* d_bits = nullptr;
   unsigned long long* d_set = nullptr;
   uint32_t set_mask = 0;
-  if (g2 <= DENSE_LIMIT) {
-    bits.assign((g2 + 31) / 32, 0);
+  if (!T.keys) {  // (dense: slots = G x G)
+    bits.assign((T.slots + 31) / 32, 0);
     for (size_t k = 0; k < list.size(); ++k)
       if (selected[k]) bits[list[k].key >> 5] |= 1u << (list[k].key & 31);
     d_bits = swg_alloc<uint32_t>(ctx, bits.size());
@@ -317,23 +253,15 @@ int select_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint3
   if (!(random_fraction >= 0.0) && !(random_fraction < 0.0)) return swg_set_error(ctx, SWG_ERR_INVALID, "tree select: random_fraction is NaN");
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (ctx->arena_cap == 0) {
-    const size_t want = (size_t)n * 24 + (size_t(32) << 20), budget = swg_arena_budget(ctx);
-    SWG_TRY(swg_arena_reserve(ctx, want < budget ? want : budget));
-  }
+  SWG_TRY(reserve_first(ctx, (size_t)n * 24 + (size_t(32) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     SelCols d{rec->q_id, rec->t_id, rec->matches, rec->block_len, seq_genome};
     uint8_t* d_keep = keep;
     if (!on_device) {
-      uint32_t* col[4];
-      for (auto& c : col) c = swg_alloc<uint32_t>(ctx, n);
-      uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
-      d_keep = swg_alloc<uint8_t>(ctx, n);
-      SWG_CHECK_ARENA(ctx);
-      const uint32_t* src[4] = {rec->q_id, rec->t_id, rec->matches, rec->block_len};
-      for (int k = 0; k < 4; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      d = SelCols{col[0], col[1], col[2], col[3], g};
+      const uint32_t* col[4];
+      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->matches, rec->block_len}, seq_genome, true, nullptr, col, &d.seq_genome,
+                            &d_keep));
+      d = SelCols{col[0], col[1], col[2], col[3], d.seq_genome};
     }
     SWG_TRY(select_device(ctx, n, n_seq, n_genome, d, prefix, k_nearest, k_farthest, random_fraction, d_keep, n_kept, too_big));
     if (!on_device && !*too_big) {
@@ -393,7 +321,7 @@ int subset_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* keep, con
   if (!rec->q_id || !rec->t_id || !status_full || !chain_full) return swg_set_error(ctx, SWG_ERR_INVALID, "subset filter: NULL column");
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (ctx->arena_cap == 0) SWG_TRY(swg_arena_reserve(ctx, std::min<size_t>(size_t(8) << 20, swg_arena_budget(ctx))));
+  SWG_TRY(reserve_first(ctx, size_t(8) << 20));
   const Cols in{{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->t_start, rec->t_end, rec->matches, rec->block_len}, rec->identity, rec->strand};
   uint64_t m = 0;
   uint32_t* kept_index = nullptr;

@@ -317,7 +317,7 @@ def test_record_seams_host_and_device_agree_with_numpy(sw):
     ctx = sw.default_context()
     rng = np.random.default_rng(31)
     for n, n_seq, per_genome, order in ((1, 2, 1, "shuffled"), (70_000, 40, 4, "pair_major"), (70_000, 3_000, 1, "shuffled"),
-                                        (50_000, 12, 12, "shuffled")):
+                                        (50_000, 12, 12, "shuffled"), (1 << 20, 64, 1, "shuffled")):
         cols, seq_genome = synth_columns(rng, n, n_seq, per_genome, order)
         G = int(seq_genome.max()) + 1
         status = (rng.random(n) < 0.4).astype(np.uint8) * rng.integers(1, 4, n).astype(np.uint8)

@@ -66,15 +66,17 @@ def shape_texts():
         "one_hash": named_text(3, 4_000, ["g%d#chr%d" % (g, c) for g in range(6) for c in range(3)]),
         "three_hashes": named_text(4, 4_000, ["s%d#%d#x%d#chr%d" % (g, g % 2, g % 3, c) for g in range(7) for c in range(3)]),
         "no_hash_20000_contigs": named_text(5, 60_000, ["ctg%05d" % i for i in range(20_000)]),
+        # 64 genomes of one contig, dense pair table: a sorted tile of 1024 records holds more pairs than the LDS table takes
+        "no_hash_64_contigs": named_text(6, 8_192, ["ctg%02d" % i for i in range(64)]),
     }
 
 
-SHAPE_NAMES = ("no_hash_20000_contigs", "one_hash", "pansn", "pansn_selfheavy", "three_hashes")
+SHAPE_NAMES = ("no_hash_20000_contigs", "no_hash_64_contigs", "one_hash", "pansn", "pansn_selfheavy", "three_hashes")
 
 
 @pytest.fixture(scope="module")
 def shapes():
-    """The five texts, built once when the first test asks for them: nothing at collection."""
+    """The texts, built once when the first test asks for them: nothing at collection."""
     texts = shape_texts()
     assert sorted(texts) == list(SHAPE_NAMES)
     return texts
