@@ -576,6 +576,61 @@ int swg_breadth_records_device(swg_ctx* ctx, const swg_records* rec, const uint3
  * text: the record seams above work on swg_aln_records. */
 int swg_paf_breadth(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int detailed, char** out_text, uint64_t* out_len);
 
+/* ---- blocks: one row per scaffold chain that a filter call kept, on the device -----------------------
+ * A pure function of the record columns plus status[n] and chain[n] as swg_filter* writes them (the MergedChain of
+ * src/paf_filter.rs:139-155, which the reference drops after numbering).  A record takes part when status != 0 and chain != 0; a
+ * block exists for every chain number that at least one such record carries.  All records of one chain share (q_id, t_id).  The
+ * SWG_ST_SCAFFOLD records of a chain are its members; on a '+' chain they include the '-' records that inversion capture added,
+ * so strand = '+' if any SCAFFOLD record of the chain is '+', else '-'.  core = the SCAFFOLD records on the block's strand,
+ * inverted = the SCAFFOLD '-' records of a '+' block, rescued = the SWG_ST_RESCUED records.  (A record with any other non-zero
+ * status and a chain number -- no filter writes one -- adds to the sums and covers only.)
+ *   q_start .. t_end    minimum of the starts and maximum of the ends over the core records: MergedChain's span
+ *   matches, block_len  sums over all records of the chain
+ *   q_bases, t_bases    sum(end - start) over all records of the chain
+ *   q_cover, t_cover    |union of [start, end)| over all records of the chain, per axis: half-open, zero-length intervals add
+ *                       nothing, touching ones join (breadth's rules with the chain as the unit)
+ *   first_record        smallest index of a core record
+ * Rows come in ascending chain number; a number that no record carries gives no row.  Every value is an integer and does not
+ * depend on the order of the records.  q_id, t_id, the four coordinates, strand, matches and block_len are read (32-bit
+ * layout; start <= end is assumed).  Capacity protocol of swg_breadth_counts: n_blocks > block_capacity still returns SWG_OK
+ * and leaves `blocks` alone.  Errors: a chain whose records name two (q_id, t_id) pairs, a chain without a SCAFFOLD record, a
+ * sequence id >= n_seq, a NULL context (there is no CPU path): SWG_ERR_INVALID; n >= 2^31 records or a chain number of
+ * 2^32 - 1: SWG_ERR_RANGE.  Scratch comes from the context's arena, SWG_ERR_OOM when the memory limit does not hold it: 28 bytes
+ * per record (two 8-byte key buffers, two 4-byte value buffers, one 4-byte buffer of ends; both axes use the same ones) plus
+ * the radix sort's histograms, 120 bytes per chain NUMBER (the table is dense in the chain number: its largest value sizes it)
+ * and 104 bytes per block.  swg_blocks_records stages its host columns there too: 38 more bytes per record. */
+typedef struct swg_block {
+  uint32_t chain;        /* N of ch:Z:chain_N */
+  uint32_t q_id, t_id;
+  uint32_t strand;       /* 0 = '+', 1 = '-' */
+  uint32_t q_start, q_end, t_start, t_end;
+  uint32_t n_core, n_inverted, n_rescued;
+  uint32_t reserved;     /* 0 */
+  uint64_t matches, block_len;
+  uint64_t q_bases, t_bases;
+  uint64_t q_cover, t_cover;
+  uint64_t first_record;
+} swg_block;
+typedef struct swg_block_table {
+  uint64_t n_blocks;       /* out: chains that occur */
+  uint64_t block_capacity; /* in: entries `blocks` can hold */
+  swg_block* blocks;       /* in: caller-owned [block_capacity] or NULL; written only when n_blocks <= block_capacity */
+} swg_block_table;
+/* rec: host pointers; status[n] and chain[n] on the host. */
+int swg_blocks_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const uint32_t* chain, swg_block_table* table);
+/* The same with the nine columns of rec, status and chain in device memory of ctx's GPU (as swg_filter_device leaves them: no
+ * copy in between); the table structure and its array stay on the host. */
+int swg_blocks_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const uint32_t* chain, swg_block_table* table);
+/* The blocks of an open PAF as PAF text (release it with swg_free), one line per block in chain order, tab-separated:
+ *   qname qlen q_start q_end strand tname tlen t_start t_end matches block_len 255
+ *   ch:Z:chain_N nc:i:<n_core> ni:i:<n_inverted> nr:i:<n_rescued> qc:i:<q_cover> tc:i:<t_cover> id:f:<identity>
+ * qname, qlen, tname and tlen are copied as text from the line of the block's first_record; identity = matches /
+ * max(block_len, 1) in double, printed "%.6f".  matches is the handle's column (RecordMeta.matches).  A PAF without records, or
+ * a status and chain without a chain, gives empty text and needs no device (ctx may be NULL then).  A handle whose columns are
+ * rebased (the file has a value >= 2^32): SWG_ERR_UNSUPPORTED.  Errors: text in swg_alnstats_last_error().  .1aln handles keep
+ * no text: the record seams above work on swg_aln_records. */
+int swg_paf_blocks(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const uint32_t* chain, char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -10,6 +10,7 @@ from .filter import (ChainStatus, FilterConfig, FilterMode, PafFilter, PlaneSwee
 from .paf import PafFile  # noqa: F401
 from .aln import AlnRecords  # noqa: F401
 from .alnstats import AlnStats  # noqa: F401
+from .blocks import BLOCK_DTYPE, Blocks, blocks_records, blocks_records_device  # noqa: F401
 from .breadth import BREADTH_PAIR_DTYPE, Breadth, breadth_records, breadth_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401
                   parse_identity_value)

@@ -35,7 +35,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_filter_subset_device", "swg_filter_subset_multi", "swg_paf_tree_select", "swg_paf_tree_needs_text",
            "swg_aln_tree_select", "swg_paf_num_genomes_two", "swg_paf_genome_two_prefix", "swg_aln_num_genomes_two",
            "swg_aln_genome_two_prefix",
-           "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth"]
+           "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth",
+           "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks"]
 
 
 class SwgError(RuntimeError):
@@ -131,6 +132,16 @@ class SwgBreadthPair(C.Structure):
 
 class SwgBreadthCounts(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgBreadthPair))]
+
+
+class SwgBlock(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("chain", "q_id", "t_id", "strand", "q_start", "q_end", "t_start", "t_end", "n_core",
+                                           "n_inverted", "n_rescued", "reserved")] + \
+               [(k, C.c_uint64) for k in ("matches", "block_len", "q_bases", "t_bases", "q_cover", "t_cover", "first_record")]
+
+
+class SwgBlockTable(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("block_capacity", C.c_uint64), ("blocks", C.POINTER(SwgBlock))]
 
 
 _lib = None
@@ -313,6 +324,12 @@ def load():
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgBreadthCounts),
                       C.POINTER(SwgBreadthCounts)]
+    for name in ("swg_blocks_records", "swg_blocks_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.POINTER(SwgBlockTable)]
+    lib.swg_paf_blocks.restype = C.c_int
+    lib.swg_paf_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_breadth.restype = C.c_int
     lib.swg_paf_breadth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p

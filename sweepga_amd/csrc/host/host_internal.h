@@ -52,6 +52,14 @@ int swg_breadth_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const 
 int swg_breadth_report(const std::vector<std::string>& genome_name, const swg_breadth_result* res, const std::vector<uint64_t>* genome_size,
                        int n_sets, bool detailed, char** out_text, uint64_t* out_len);
 
+// ---- blocks (swg_blocks.hip: kernels and seams; paf_io.cpp: the text) ----
+struct swg_blocks_result {
+  std::vector<swg_block> blocks;  // ascending chain number
+};
+int swg_blocks_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const uint32_t* chain, swg_blocks_result* res);
+// the --blocks text: names and lengths from the line of each block's first record
+int swg_paf_blocks_text(const swg_paf* p, const std::vector<swg_block>& blocks, char** out_text, uint64_t* out_len);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

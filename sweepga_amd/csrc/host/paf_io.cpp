@@ -956,6 +956,33 @@ int swg_paf_stats_genome_sizes(const swg_paf* p, const swg_alnstats_result& r, s
   return SWG_OK;
 }
 
+// The --blocks text: one PAF line per block; columns 1, 2, 6 and 7 are the bytes of the first record's line.
+int swg_paf_blocks_text(const swg_paf* p, const std::vector<swg_block>& blocks, char** out_text, uint64_t* out_len) {
+  std::string o;
+  char buf[64];
+  for (const swg_block& b : blocks) {
+    size_t len[4];
+    const char* col[4];
+    static const int COL[4] = {0, 1, 5, 6};
+    for (int j = 0; j < 4; ++j) col[j] = stats_column(p, b.first_record, COL[j], &len[j]);
+    o.append(col[0], len[0]).append(1, '\t').append(col[1], len[1]);
+    o += '\t' + std::to_string(b.q_start) + '\t' + std::to_string(b.q_end) + '\t' + (b.strand ? '-' : '+') + '\t';
+    o.append(col[2], len[2]).append(1, '\t').append(col[3], len[3]);
+    o += '\t' + std::to_string(b.t_start) + '\t' + std::to_string(b.t_end) + '\t' + std::to_string(b.matches) + '\t' + std::to_string(b.block_len);
+    o += "\t255\tch:Z:chain_" + std::to_string(b.chain) + "\tnc:i:" + std::to_string(b.n_core) + "\tni:i:" + std::to_string(b.n_inverted) +
+         "\tnr:i:" + std::to_string(b.n_rescued) + "\tqc:i:" + std::to_string(b.q_cover) + "\ttc:i:" + std::to_string(b.t_cover);
+    std::snprintf(buf, sizeof buf, "\tid:f:%.6f\n", (double)b.matches / (double)(b.block_len ? b.block_len : 1));
+    o += buf;
+  }
+  char* t = static_cast<char*>(std::malloc(o.size() + 1));
+  if (!t) return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+  std::memcpy(t, o.data(), o.size());
+  t[o.size()] = 0;
+  *out_text = t;
+  *out_len = o.size();
+  return SWG_OK;
+}
+
 int swg_paf_stats_finish(const swg_paf* p, const swg_alnstats_result* res, swg_alnstats** const* outs) {
   std::vector<std::string> gname;
   swg_paf_stats_genome_names(p, &gname);

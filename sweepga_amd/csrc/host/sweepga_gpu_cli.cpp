@@ -268,6 +268,20 @@ void write_breadth_report(const std::string& path, swg_ctx* ctx, const swg_paf* 
   swg_free(text);
 }
 
+// --blocks: the text of swg_paf_blocks (one PAF line per kept scaffold chain).  "-" = standard error.  status == NULL: no filter
+// ran, there are no chains, the file is written empty.
+void write_blocks(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const uint32_t* chain) {
+  char* text = nullptr;
+  uint64_t len = 0;
+  if (status && swg_paf_blocks(ctx, paf, status, chain, &text, &len) != SWG_OK) die(3, std::string("--blocks: ") + swg_alnstats_last_error());
+  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
+  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+  if (f == stderr) std::fflush(stderr);
+  swg_free(text);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -286,6 +300,7 @@ int main(int argc, char** argv) {
   std::string stats_path;  // --stats: empty = no report
   std::string breadth_path;  // --breadth: empty = no report
   bool breadth_detailed = false;
+  std::string blocks_path;  // --blocks: empty = no file
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -348,6 +363,7 @@ int main(int argc, char** argv) {
     else if (a == "--stats-detailed") stats_detailed = true;
     else if (a == "--breadth") { breadth_path = value(); if (breadth_path.empty()) die(2, "empty value for --breadth"); }
     else if (a == "--breadth-detailed") breadth_detailed = true;
+    else if (a == "--blocks") { blocks_path = value(); if (blocks_path.empty()) die(2, "empty value for --blocks"); }
     else if (a == "--joblist") joblist = true;
     else if (a == "--joblist-output-dir") joblist_dir = value();
     else if (a == "--mash-kmer-size") { if (!parse_u64(value(), &mash_k)) die(2, "invalid value for --mash-kmer-size"); }
@@ -359,6 +375,7 @@ int main(int argc, char** argv) {
                 "         [--min-scaffold-identity I] [--scaffolds-only] [--ani-method M]\n"
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
                 "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
+                "         [--blocks FILE|-]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -368,6 +385,10 @@ int main(int argc, char** argv) {
                 "                      inter-genome mapping (merged intervals), their share of the genome and the mean depth, as a\n"
                 "                      tab-separated table computed on the device (- = standard error); with --no-filter kept = all\n"
                 "  --breadth-detailed  with --breadth: one row per ordered genome pair ahead of each set's `*` row of sums\n"
+                "  --blocks FILE       after the filter: one PAF line per scaffold chain that was kept -- its span on both sequences, summed\n"
+                "                      matches and block length, and the tags ch:Z: nc:i: ni:i: nr:i: (core, inverted, rescued mappings)\n"
+                "                      qc:i: tc:i: (bases under at least one of them) id:f: -- built on the device (- = standard error);\n"
+                "                      empty with --no-filter or --scaffold-jump 0, which make no chains\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -487,6 +508,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--breadth: the file has a value >= 2^32, its columns are rebased: breadth of 64-bit columns is not supported");
   }
+  if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
+  }
   const std::string out_path = output_file.empty() ? "-" : output_file;
   const swg_records* r = swg_paf_records(paf);
   uint64_t n = r->n;
@@ -517,6 +542,10 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_breadth_report(breadth_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), breadth_detailed);
+    }
+    if (!blocks_path.empty()) {  // no filter, no chains
+      std::fflush(out);
+      write_blocks(blocks_path, nullptr, paf, nullptr, nullptr);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -623,6 +652,13 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_breadth_report(breadth_path, ctx, paf, status.data(), breadth_detailed);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --breadth: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --blocks: on the first context, from the (merged) status and chain the filter left; records that a sparsification dropped
+  // carry chain 0 and take no part
+  if (!blocks_path.empty()) {
+    const auto tb = clk::now();
+    write_blocks(blocks_path, ctx, paf, status.data(), chain.data());
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --blocks: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

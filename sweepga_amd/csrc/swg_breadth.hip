@@ -35,15 +35,13 @@
 
 #include "swg_internal.h"
 #include "swg_pair_table.h"
+#include "swg_union_tiles.h"
 #include "host/host_internal.h"
 
 namespace {
 
-using namespace swg_pair_table;  // the genome-pair table, the run and wavefront helpers, the host entry helpers
-constexpr int ITEMS = 4;                   // consecutive sorted records per thread
-constexpr int TILE = TB * ITEMS;           // ... per work-group
-constexpr uint32_t KEPT_FLAG = 0x80000000u;
-constexpr uint32_t INDEX_MASK = 0x7fffffffu;
+using namespace swg_pair_table;   // the genome-pair table, the run and wavefront helpers, the host entry helpers
+using namespace swg_union_tiles;  // the tile of the sorted order and its first pass
 enum { D_BAD = 0, D_SEGMENTS, D_LISTED, D_LISTED_KEPT, D_TOTAL };
 enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // a listed entry's sums
 
@@ -79,74 +77,12 @@ __global__ __launch_bounds__(TB) void breadth_keys_kernel(uint64_t n, const uint
   vals[i] = (uint32_t)i | (status && status[i] != 0 ? KEPT_FLAG : 0u);
 }
 
-// ---- one tile of the sorted order ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load_tile(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n, uint64_t p0,
-                                          uint64_t (&k)[ITEMS], uint32_t (&v)[ITEMS]) {
-  if (p0 + ITEMS <= n) {  // (arena blocks are 16-byte aligned and p0 is a multiple of 4)
-    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(keys + p0), b = *reinterpret_cast<const ulonglong2*>(keys + p0 + 2);
-    const uint4 w = *reinterpret_cast<const uint4*>(vals + p0);
-    k[0] = a.x, k[1] = a.y, k[2] = b.x, k[3] = b.y;
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      k[j] = p0 + j < n ? keys[p0 + j] : ~0ull;
-      v[j] = p0 + j < n ? vals[p0 + j] : 0u;
-    }
-  }
-}
-
-__device__ __forceinline__ unsigned long long max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
+// ---- one tile of the sorted order (load_tile, gather_tile: swg_union_tiles.h) ---------------------------------------------
 __global__ __launch_bounds__(TB) void breadth_gather_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             const uint32_t* __restrict__ end_col, uint32_t sentinel,
                                                             uint32_t* __restrict__ ends, unsigned long long* __restrict__ tile_max,
                                                             uint64_t ntiles, unsigned long long* __restrict__ segments) {
-  __shared__ unsigned long long l_max[2][WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
-  uint64_t k[ITEMS];
-  uint32_t v[ITEMS], e[ITEMS];
-  load_tile(keys, vals, n, p0, k, v);
-  uint32_t before = p0 > 0 && p0 <= n ? (uint32_t)(keys[p0 - 1] >> 32) : sentinel;  // (the sentinel is never a head's segment)
-  unsigned long long m_all = 0, m_kept = 0;
-  uint32_t heads = 0;
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const uint32_t seg = (uint32_t)(k[j] >> 32);
-    const bool counted = p0 + j < n && seg != sentinel;
-    e[j] = counted ? end_col[v[j] & INDEX_MASK] : 0u;  // (values are the indices breadth_keys wrote: < n)
-    if (counted) {
-      const unsigned long long P = ((unsigned long long)seg << 32) | e[j];
-      m_all = max64(m_all, P);
-      if (v[j] & KEPT_FLAG) m_kept = max64(m_kept, P);
-      heads += seg != before || p0 + j == 0;
-    }
-    before = seg;
-  }
-  if (p0 + ITEMS <= n) {
-    *reinterpret_cast<uint4*>(ends + p0) = make_uint4(e[0], e[1], e[2], e[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j)
-      if (p0 + j < n) ends[p0 + j] = e[j];
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    m_all = max64(m_all, __shfl_xor(m_all, d));
-    m_kept = max64(m_kept, __shfl_xor(m_kept, d));
-  }
-  if (segments) {
-    const unsigned long long h = wave_sum(heads);
-    if (lane == 0 && h) atomicAdd(segments, h);
-  }
-  if (lane == 0) l_max[0][wave] = m_all, l_max[1][wave] = m_kept;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned long long m = 0;
-    for (int w = 0; w < WAVES; ++w) m = max64(m, l_max[threadIdx.x][w]);
-    tile_max[threadIdx.x * ntiles + blockIdx.x] = m;
-  }
+  gather_tile<true>(n, keys, vals, end_col, sentinel, ends, tile_max, ntiles, segments);
 }
 
 template <int AXIS>
@@ -161,13 +97,7 @@ __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uin
   uint64_t k[ITEMS];
   uint32_t v[ITEMS], e[ITEMS];
   load_tile(keys, vals, n, p0, k, v);
-  if (p0 + ITEMS <= n) {
-    const uint4 w = *reinterpret_cast<const uint4*>(ends + p0);
-    e[0] = w.x, e[1] = w.y, e[2] = w.z, e[3] = w.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) e[j] = p0 + j < n ? ends[p0 + j] : 0u;
-  }
+  load_ends(ends, n, p0, e);
   bool counted[ITEMS];
   unsigned long long t_all = 0, t_kept = 0;
 #pragma unroll

@@ -12,7 +12,8 @@
 //
 // A kernel keeps its own per-record loop and its own __global__ entry for the listing (the profile's launch labels are kernel
 // names); everything it does to a table goes through here.  Integer atomics only.  Below the scheme: what the host entries of
-// the three users share (grid_for, share_for, reserve_first, stage_columns).
+// the three users share (grid_for, share_for, reserve_first, stage_columns).  swg_blocks.hip reduces per chain into a dense table
+// of its own and borrows the run and wavefront helpers only.
 #pragma once
 #include <algorithm>
 #include <vector>
