@@ -7,6 +7,7 @@
 // pair after pair, so a pair is one run of the input -- and its few thousand records fit the LDS of one work-group:
 //
 //   pair_boundary / pair_runs   the runs of equal (q_id, t_id), checked to be one per pair (else: the global-sort path)
+//   pair_order   the lists of the two largest size classes, longest pairs first (what a per-pair launch starts first)
 //   pair_sort    one work-group per pair: step-1 retain (paf_filter.rs:384-388), members bucket-sorted in LDS by
 //                (strand, q_start, index) (:777), the other columns transposed through LDS into that order (coalesced reads,
 //                coalesced writes: no gather), unit cuts and the chunk list of the walk
@@ -266,6 +267,64 @@ __global__ __launch_bounds__(256) void pair_runs_kernel(uint32_t n, uint32_t cap
     for (int w2 = 0; w2 < wv; ++w2) o += s_cnt[w2][cls];
     const unsigned long long m = cls == 0 ? mk[0] : (cls == 1 ? mk[1] : (cls == 2 ? mk[2] : mk[3]));
     class_list[(size_t)cls * cap + o + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = k;
+  }
+}
+
+// The two largest classes' lists, longest pairs first: a launch lasts as long as its last long pair, and pair_runs_kernel files
+// the pairs in whatever order its work-groups reach the class counters.  One work-group per class sorts its list by counting
+// over ORDER_BINS length bins (the longest lengths in bin 0; inside a bin the order is what the LDS atomics make it).  The order
+// of a list carries no meaning -- a pair's chunk slots follow from its place in the input, the numbering from its keys -- so
+// every kernel that takes its pairs from these lists (pair_sort_big, pair_chains, pair_finish, pair_out) starts its longest
+// pairs first without knowing.  tmp: room for cap_tmp entries per class (a class-2 pair has more than PAIR_M_MAX records).
+constexpr int ORDER_NT = 1024, ORDER_BINS = 256;
+__global__ __launch_bounds__(ORDER_NT) void pair_order_kernel(const PairRun* __restrict__ runs, uint32_t* __restrict__ class_list, uint32_t cap,
+                                                              uint32_t* __restrict__ tmp, uint32_t cap_tmp,
+                                                              const PairCounters* __restrict__ C) {
+  __shared__ uint32_t bin_at[ORDER_BINS];
+  const int tid = threadIdx.x, cls = 2 + (int)blockIdx.x;
+  if (C->flags) return;  // (pair_plan gives the path up: the lists are not read)
+  const uint32_t cnt = C->n_class[cls];
+  if (cnt < 2u || cnt > cap_tmp || cnt > cap) return;
+  const uint32_t lo = cls == 2 ? PAIR_M_MAX : PAIR_L_MAX, width = (cls == 2 ? PAIR_L_MAX : PAIR_XL_MAX) - lo;  // lengths in (lo, lo + width]
+  uint32_t* const list = class_list + (size_t)cls * cap;
+  uint32_t* const t = tmp + (size_t)blockIdx.x * cap_tmp;
+  auto bin_of = [&](uint32_t len) -> uint32_t {
+    const uint32_t b = (uint32_t)(((uint64_t)(len - lo - 1u) * ORDER_BINS) / width);
+    return (uint32_t)ORDER_BINS - 1u - (b < (uint32_t)ORDER_BINS ? b : (uint32_t)ORDER_BINS - 1u);
+  };
+  for (int b = tid; b < ORDER_BINS; b += ORDER_NT) bin_at[b] = 0u;
+  __syncthreads();
+  for (uint32_t i = tid; i < cnt; i += ORDER_NT) {
+    const uint32_t k = list[i];
+    t[i] = k;
+    atomicAdd(&bin_at[bin_of(runs[k].n)], 1u);
+  }
+  __syncthreads();
+  if (tid < 64) {  // exclusive prefix sums of the bins: four bins per lane
+    constexpr int PER = ORDER_BINS / 64;
+    uint32_t v[PER], s = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      v[j] = bin_at[tid * PER + j];
+      s += v[j];
+    }
+    uint32_t inc = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t x = __shfl_up(inc, d, 64);
+      if (tid >= d) inc += x;
+    }
+    uint32_t o = inc - s;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      bin_at[tid * PER + j] = o;
+      o += v[j];
+    }
+  }
+  __syncthreads();  // (every read of the list is done; a thread reads back the entries of tmp it wrote itself)
+  for (uint32_t i = tid; i < cnt; i += ORDER_NT) {
+    const uint32_t k = t[i];
+    list[atomicAdd(&bin_at[bin_of(runs[k].n)], 1u)] = k;
   }
 }
 
@@ -1539,6 +1598,8 @@ __global__ void pair_gate_kernel(PairCounters* __restrict__ C) {
 struct PairFinishArgs {
   const PairRun* runs;
   const uint32_t* list;
+  const uint32_t* list_xl;  // the largest class's launch: its first n_xl work-groups take their pairs from the list of the
+  uint32_t n_xl;            //   very long pairs (pair_sort_big_kernel's order), the others from `list`
   const PairInfo* info;
   PairSum* sum;
   const uint32_t *s_qs, *s_qe, *s_ts, *s_te, *s_idx, *hd;
@@ -1572,6 +1633,8 @@ constexpr uint32_t NEVER = 0xfffffffeu;  // a member of a chain that passed the 
 struct PairChainArgs {
   const PairRun* runs;
   const uint32_t* list;
+  const uint32_t* list_xl;  // (as PairFinishArgs: the very long pairs open the largest class's launch)
+  uint32_t n_xl;
   const PairInfo* info;
   const uint8_t* ok_head;
   const HeadRec* rec;
@@ -1594,7 +1657,7 @@ __global__ __launch_bounds__(NT) void pair_chains_kernel(PairChainArgs A) {
   __shared__ uint32_t sh_base;
   const int tid = threadIdx.x;
   if (A.C->flags & PF_FALLBACK) return;
-  const uint32_t rk = A.list[blockIdx.x];
+  const uint32_t rk = blockIdx.x < A.n_xl ? A.list_xl[blockIdx.x] : A.list[blockIdx.x - A.n_xl];
   const PairRun run = A.runs[rk];
   const PairInfo pi = A.info[rk];
   const uint32_t a = run.a, m = pi.m, m_plus = pi.m_plus;
@@ -1724,7 +1787,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
   // a pair_sort work-group gave the call up (a pair too dense for the LDS batches ...): nothing written from here on is used
   // (the host sees the same flag and runs the global-sort stage)
   if (A.C->flags & PF_FALLBACK) return;
-  const uint32_t rk = A.list[blockIdx.x];
+  const uint32_t rk = blockIdx.x < A.n_xl ? A.list_xl[blockIdx.x] : A.list[blockIdx.x - A.n_xl];
   const PairRun run = A.runs[rk];
   const PairInfo pi = A.info[rk];
   const uint32_t a = run.a, m = pi.m, m_plus = pi.m_plus, M = pi.M;
@@ -2270,35 +2333,79 @@ __global__ __launch_bounds__(EW) void pair_base_kernel(uint32_t n_runs, const ui
   const uint32_t r = blockIdx.x * EW + threadIdx.x;
   if (r < n_runs) sum[order[r]].base = bases[r];
 }
-// A moderate number of pairs: the same by counting, one wavefront per pair (its lanes stride over the keys; O(pairs^2)
-// compares, no sort: 10^4 pairs are 10^8 compares).
-__global__ __launch_bounds__(EW) void pair_rank_count_kernel(uint32_t n_runs, const uint64_t* __restrict__ key, const PairInfo* __restrict__ info,
-                                                             const uint32_t* __restrict__ seq_genome_two, PairTable gp2_first,
-                                                             uint32_t* __restrict__ rank1) {
-  const uint32_t k = blockIdx.x * (EW / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (k >= n_runs) return;
+// A moderate number of pairs (up to NUMBER_COUNT_MAX): the same by counting, O(pairs^2) compares and no sort: 10^4 pairs are
+// 10^8 compares.  Every work-group stages all keys (and, for the bases, the pairs' kept counts as a plain array) in LDS once;
+// a wavefront then counts for NUMBER_T pairs at a time, its lanes striding over the staged keys -- one LDS read serves
+// NUMBER_T compares.  (Streaming the keys from L2 once per wavefront and pair took 0.066 + 0.100 ms at 9,900 pairs.)
+constexpr uint32_t NUMBER_COUNT_MAX = 12288;
+constexpr int NUMBER_NT = 1024, NUMBER_T = 4;
+static_assert(NUMBER_COUNT_MAX * 12 + 64 <= 160 * 1024, "LDS of a CU");
+__global__ __launch_bounds__(NUMBER_NT) void pair_rank_count_kernel(uint32_t n_runs, const uint64_t* __restrict__ key, const PairInfo* __restrict__ info,
+                                                                    const uint32_t* __restrict__ seq_genome_two, PairTable gp2_first,
+                                                                    uint32_t* __restrict__ rank1) {
+  __shared__ uint64_t l_key[NUMBER_COUNT_MAX];
+  for (uint32_t j = threadIdx.x; j < n_runs; j += NUMBER_NT) l_key[j] = key[j];
+  __syncthreads();
   const int lane = threadIdx.x & 63;
-  const uint64_t mine = key[k];
-  uint32_t r = 0;
-  if (mine != ~0ull)
-    for (uint32_t j = lane; j < n_runs; j += 64) r += key[j] < mine ? 1u : 0u;
+  const uint32_t wave = blockIdx.x * (NUMBER_NT / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (uint32_t k0 = wave * NUMBER_T; k0 < n_runs; k0 += gridDim.x * (NUMBER_NT / 64) * NUMBER_T) {
+    uint64_t mine[NUMBER_T];
+    uint32_t r[NUMBER_T];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
-  if (lane) return;
-  rank1[k] = r;
-  if (mine != ~0ull) atomicMin(pair_slot(gp2_first, seq_genome_two[info[k].q], seq_genome_two[info[k].t]), r);
+    for (int t = 0; t < NUMBER_T; ++t) {
+      mine[t] = k0 + t < n_runs ? l_key[k0 + t] : ~0ull;
+      r[t] = 0;
+    }
+    for (uint32_t j = lane; j < n_runs; j += 64) {
+      const uint64_t x = l_key[j];
+#pragma unroll
+      for (int t = 0; t < NUMBER_T; ++t) r[t] += x < mine[t] ? 1u : 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < NUMBER_T; ++t) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) r[t] += __shfl_xor(r[t], o, 64);
+      const uint32_t k = k0 + t;
+      if (lane == 0 && k < n_runs) {
+        const bool has = mine[t] != ~0ull;  // (a pair without a passing chain: no rank, as no key)
+        rank1[k] = has ? r[t] : 0u;
+        if (has) atomicMin(pair_slot(gp2_first, seq_genome_two[info[k].q], seq_genome_two[info[k].t]), r[t]);
+      }
+    }
+  }
 }
-__global__ __launch_bounds__(EW) void pair_base_count_kernel(uint32_t n_runs, const uint64_t* __restrict__ key, PairSum* sum) {
-  const uint32_t k = blockIdx.x * (EW / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (k >= n_runs) return;
+__global__ __launch_bounds__(NUMBER_NT) void pair_base_count_kernel(uint32_t n_runs, const uint64_t* __restrict__ key, PairSum* sum) {
+  __shared__ uint64_t l_key[NUMBER_COUNT_MAX];
+  __shared__ uint32_t l_kept[NUMBER_COUNT_MAX];
+  for (uint32_t j = threadIdx.x; j < n_runs; j += NUMBER_NT) {
+    l_key[j] = key[j];
+    l_kept[j] = sum[j].n_kept;  // (a word of its own: the other work-groups write `base`)
+  }
+  __syncthreads();
   const int lane = threadIdx.x & 63;
-  const uint64_t mine = key[k];
-  uint32_t b = 0;
-  if (mine != ~0ull)
-    for (uint32_t j = lane; j < n_runs; j += 64) b += key[j] < mine ? sum[j].n_kept : 0u;
+  const uint32_t wave = blockIdx.x * (NUMBER_NT / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (uint32_t k0 = wave * NUMBER_T; k0 < n_runs; k0 += gridDim.x * (NUMBER_NT / 64) * NUMBER_T) {
+    uint64_t mine[NUMBER_T];
+    uint32_t b[NUMBER_T];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) b += __shfl_xor(b, o, 64);
-  if (lane == 0) sum[k].base = b;  // (a word of its own: the other wavefronts read n_kept)
+    for (int t = 0; t < NUMBER_T; ++t) {
+      mine[t] = k0 + t < n_runs ? l_key[k0 + t] : ~0ull;
+      b[t] = 0;
+    }
+    for (uint32_t j = lane; j < n_runs; j += 64) {
+      const uint64_t x = l_key[j];
+      const uint32_t kept = l_kept[j];
+#pragma unroll
+      for (int t = 0; t < NUMBER_T; ++t) b[t] += x < mine[t] ? kept : 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < NUMBER_T; ++t) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) b[t] += __shfl_xor(b[t], o, 64);
+      const uint32_t k = k0 + t;
+      if (lane == 0 && k < n_runs) sum[k].base = mine[t] != ~0ull ? b[t] : 0u;
+    }
+  }
 }
 // Few pairs (the usual case for a small input): no sort at all -- a pair's place among the keys is a count, and its base is
 // the sum of the kept chains of the pairs whose key is smaller; one work-group, O(pairs^2) compares from LDS.
@@ -2642,6 +2749,10 @@ int pair_plan(swg_ctx* ctx, const swg_records* r, const swg_config* cfg, PairPla
     uint32_t* starts = swg_alloc<uint32_t>(ctx, (size_t)cap + 2);
     unsigned long long* table = swg_alloc<unsigned long long>(ctx, tsize);
     uint64_t* d_nr = swg_alloc<uint64_t>(ctx, 1);
+    // SWG_PAIR_ORDER=0: the lists stay in the order pair_runs_kernel filed them (experiments)
+    static const bool order_knob = !(getenv("SWG_PAIR_ORDER") && atoi(getenv("SWG_PAIR_ORDER")) == 0);
+    const uint32_t cap_tmp = n / PAIR_M_MAX + 1u < cap ? n / PAIR_M_MAX + 1u : cap;
+    uint32_t* order_tmp = order_knob ? swg_alloc<uint32_t>(ctx, (size_t)2 * cap_tmp) : nullptr;
     SWG_CHECK_ARENA(ctx);
     SWG_HIP(ctx, hipMemsetAsync(C, 0, sizeof(PairCounters), st));
     SWG_HIP(ctx, hipMemsetAsync(table, 0xff, (size_t)tsize * 8, st));
@@ -2652,6 +2763,10 @@ int pair_plan(swg_ctx* ctx, const swg_records* r, const swg_config* cfg, PairPla
     SWG_KERNEL_CHECK(ctx);
     SWG_LAUNCH(ctx, "pair_runs", pair_runs_kernel<<<(cap + 255) / 256, 256, 0, st>>>(n, cap, d_nr, starts, r->q_id, r->t_id, table, tsize - 1, runs, class_list, C));
     SWG_KERNEL_CHECK(ctx);
+    if (order_knob && n > PAIR_M_MAX) {  // (no pair of the two largest classes otherwise)
+      SWG_LAUNCH(ctx, "pair_order", pair_order_kernel<<<2, ORDER_NT, 0, st>>>(runs, class_list, cap, order_tmp, cap_tmp, C));
+      SWG_KERNEL_CHECK(ctx);
+    }
   }
   uint64_t h[4];
   static_assert(sizeof(PairCounters) >= 32, "the first four words are read back");
@@ -2895,20 +3010,25 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
     SWG_HIP(ctx, hipMemsetAsync(CA.cnt, 0, (size_t)n_runs * sizeof(uint32_t), st));   // (a call given up on the device leaves them unwritten)
     SWG_HIP(ctx, hipMemsetAsync(CA.has, 0, (size_t)n_runs * sizeof(uint32_t), st));
     for (int phase = 0; phase < 2; ++phase) {
-      for (int c = 0; c < 4; ++c) {
-        if (!ncls[c]) continue;
+      // the two largest classes in one launch, the very long pairs first (as pair_sort_big_kernel): on their own they keep a
+      // few dozen CUs busy while the rest of the chip waits for the last of them
+      for (int c = 0; c < 3; ++c) {
+        const uint32_t nb = c == 2 ? ncls[2] + ncls[3] : ncls[c];
+        if (!nb) continue;
         CA.list = class_list + (size_t)c * cap;
+        CA.list_xl = c == 2 ? class_list + (size_t)3 * cap : nullptr;
+        CA.n_xl = c == 2 ? ncls[3] : 0u;
         if (phase == 0) {
           switch (c) {
-            case 0: SWG_LAUNCH(ctx, "pair_chains_s", pair_chains_kernel<64, 0><<<ncls[c], 64, 0, st>>>(CA)); break;
-            case 1: SWG_LAUNCH(ctx, "pair_chains_m", pair_chains_kernel<256, 0><<<ncls[c], 256, 0, st>>>(CA)); break;
-            default: SWG_LAUNCH(ctx, "pair_chains", pair_chains_kernel<512, 0><<<ncls[c], 512, 0, st>>>(CA)); break;
+            case 0: SWG_LAUNCH(ctx, "pair_chains_s", pair_chains_kernel<64, 0><<<nb, 64, 0, st>>>(CA)); break;
+            case 1: SWG_LAUNCH(ctx, "pair_chains_m", pair_chains_kernel<256, 0><<<nb, 256, 0, st>>>(CA)); break;
+            default: SWG_LAUNCH(ctx, "pair_chains", pair_chains_kernel<512, 0><<<nb, 512, 0, st>>>(CA)); break;
           }
         } else {
           switch (c) {
-            case 0: SWG_LAUNCH(ctx, "pair_chains_s", pair_chains_kernel<64, 1><<<ncls[c], 64, 0, st>>>(CA)); break;
-            case 1: SWG_LAUNCH(ctx, "pair_chains_m", pair_chains_kernel<256, 1><<<ncls[c], 256, 0, st>>>(CA)); break;
-            default: SWG_LAUNCH(ctx, "pair_chains", pair_chains_kernel<512, 1><<<ncls[c], 512, 0, st>>>(CA)); break;
+            case 0: SWG_LAUNCH(ctx, "pair_chains_s", pair_chains_kernel<64, 1><<<nb, 64, 0, st>>>(CA)); break;
+            case 1: SWG_LAUNCH(ctx, "pair_chains_m", pair_chains_kernel<256, 1><<<nb, 256, 0, st>>>(CA)); break;
+            default: SWG_LAUNCH(ctx, "pair_chains", pair_chains_kernel<512, 1><<<nb, 512, 0, st>>>(CA)); break;
           }
         }
         SWG_KERNEL_CHECK(ctx);
@@ -2939,13 +3059,16 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   FA.anum = anum;
   FA.n_out_pair = n_out_pair;
   FA.fin = fin;
-  for (int c = 0; c < 4; ++c) {
-    if (!ncls[c]) continue;
+  for (int c = 0; c < 3; ++c) {  // (the two largest classes in one launch, the very long pairs first, as pair_chains above)
+    const uint32_t nb = c == 2 ? ncls[2] + ncls[3] : ncls[c];
+    if (!nb) continue;
     FA.list = class_list + (size_t)c * cap;
+    FA.list_xl = c == 2 ? class_list + (size_t)3 * cap : nullptr;
+    FA.n_xl = c == 2 ? ncls[3] : 0u;
     switch (c) {
-      case 0: SWG_LAUNCH(ctx, "pair_finish_s", pair_finish_kernel<64, 256><<<ncls[c], 64, 0, st>>>(FA)); break;
-      case 1: SWG_LAUNCH(ctx, "pair_finish_m", pair_finish_kernel<256, 1024><<<ncls[c], 256, 0, st>>>(FA)); break;
-      default: SWG_LAUNCH(ctx, "pair_finish", pair_finish_kernel<512, 4096><<<ncls[c], 512, 0, st>>>(FA)); break;
+      case 0: SWG_LAUNCH(ctx, "pair_finish_s", pair_finish_kernel<64, 256><<<nb, 64, 0, st>>>(FA)); break;
+      case 1: SWG_LAUNCH(ctx, "pair_finish_m", pair_finish_kernel<256, 1024><<<nb, 256, 0, st>>>(FA)); break;
+      default: SWG_LAUNCH(ctx, "pair_finish", pair_finish_kernel<512, 4096><<<nb, 512, 0, st>>>(FA)); break;
     }
     SWG_KERNEL_CHECK(ctx);
   }
@@ -2954,16 +3077,17 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
     SWG_LAUNCH(ctx, "pair_number", pair_number_small_kernel<<<1, 512, 0, st>>>(n_runs, info, sum, gl_first, r->seq_genome_last, gp2_first,
                                                                      r->seq_genome_two, C));
     SWG_KERNEL_CHECK(ctx);
-  } else if (n_runs <= 12288u) {  // (a wavefront per key counts the smaller keys: quadratic -- 0.19 ms at 9,900 pairs, 1.45 at 32,000)
+  } else if (n_runs <= NUMBER_COUNT_MAX) {  // (every key against every other, from LDS: quadratic)
     uint64_t* key = swg_alloc<uint64_t>(ctx, n_runs);
     uint32_t* val = swg_alloc<uint32_t>(ctx, n_runs);
     uint32_t* rank1 = swg_alloc<uint32_t>(ctx, n_runs);
     SWG_CHECK_ARENA(ctx);
-    const unsigned rb = nblk(n_runs), wb = (n_runs + EW / 64 - 1) / (EW / 64);
+    constexpr uint32_t per_wg = (NUMBER_NT / 64) * NUMBER_T;  // pairs a work-group counts for in one round
+    const unsigned rb = nblk(n_runs), wb = (n_runs + per_wg - 1) / per_wg < (unsigned)ctx->num_cu ? (n_runs + per_wg - 1) / per_wg : (unsigned)ctx->num_cu;
     SWG_LAUNCH(ctx, "pair_number", pair_key1_kernel<<<rb, EW, 0, st>>>(n_runs, info, sum, gl_first, r->seq_genome_last, key, val, C));
-    SWG_LAUNCH(ctx, "pair_number", pair_rank_count_kernel<<<wb, EW, 0, st>>>(n_runs, key, info, r->seq_genome_two, gp2_first, rank1));
+    SWG_LAUNCH(ctx, "pair_number", pair_rank_count_kernel<<<wb, NUMBER_NT, 0, st>>>(n_runs, key, info, r->seq_genome_two, gp2_first, rank1));
     SWG_LAUNCH(ctx, "pair_number", pair_key2_kernel<<<rb, EW, 0, st>>>(n_runs, info, sum, rank1, r->seq_genome_two, gp2_first, key, val, C));
-    SWG_LAUNCH(ctx, "pair_number", pair_base_count_kernel<<<wb, EW, 0, st>>>(n_runs, key, sum));
+    SWG_LAUNCH(ctx, "pair_number", pair_base_count_kernel<<<wb, NUMBER_NT, 0, st>>>(n_runs, key, sum));
     SWG_KERNEL_CHECK(ctx);
   } else {
     uint64_t* key = swg_alloc<uint64_t>(ctx, n_runs);
