@@ -631,6 +631,79 @@ int swg_blocks_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_
  * no text: the record seams above work on swg_aln_records. */
 int swg_paf_blocks(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const uint32_t* chain, char** out_text, uint64_t* out_len);
 
+/* ---- components: which sequences belong together under the kept mappings, on the device ------------
+ * A pure function of q_id, t_id and the four coordinates (32-bit layout; start <= end is assumed), status[n], seq_len[n_seq]
+ * and two parameters; all integers, independent of record order and grid shape.
+ *   nodes       every sequence id < n_seq
+ *   links       a record takes part when status != 0 (the rule of swg_paf_write; status == NULL: every record) and
+ *               q_id != t_id.  Every unordered pair {a, b}, a < b, that such a record names is a link: a_bases / b_bases =
+ *               sum(end - start) on the axis where a / b lies, over the pair's records of BOTH orientations; n_records their
+ *               number; first_record the smallest record index.  These are plain SUMS, not unions: overlapping mappings count
+ *               once each (a pile of repeats over one locus adds up; breadth, section 17, is the union).
+ *   joined      with need(s) = ceil(min_share_ppm * seq_len[s] / 10^6):  max(a_bases, b_bases) >= min_bases  and
+ *               (a_bases >= need(a) or b_bases >= need(b)).  A contig that aligns mostly to a chromosome joins it, two
+ *               chromosomes tied by a short translocation do not.  The defaults 0, 0 join every link: plain connected components.
+ *   components  connected sets of sequences over the joined links, numbered 1..C in ascending order of their smallest member
+ *               (first_seq); a sequence without a joined link is a component of its own.  length = sum of seq_len; n_links,
+ *               n_records and bases = sum(a_bases + b_bases) run over the links whose two ends lie in the component, joined or
+ *               not.  cross_links, cross_records, cross_bases: the same three sums over the links whose ends lie in different
+ *               components.
+ * `links` comes in ascending (a, b), `components` in ascending id; seq_component[s] is the id of s's component.  Capacity
+ * protocol of swg_breadth_counts, per array: a count above its capacity still returns SWG_OK and leaves that array alone.
+ * n == 0 gives n_seq singleton components and no links.  Errors: a NULL context (there is no CPU path), a sequence id >=
+ * n_seq, min_share_ppm > 10^6, reserved != 0: SWG_ERR_INVALID; n >= 2^31 records: SWG_ERR_RANGE.  Scratch comes from the
+ * context's arena, SWG_ERR_OOM when the memory limit does not hold it: nothing per record on the device seam (the host seam
+ * stages its columns there: 25 bytes per record), 32 bytes per slot of the sequence-pair table (n_seq^2 slots while that is at
+ * most 2^20, else 40 bytes per slot of an open-addressing table of at least twice the pairs that can occur -- the smaller of
+ * n_seq (n_seq - 1) / 2 and the runs of one pair in input order), 40 bytes per link, 16 bytes per sequence (20 on the host
+ * seam) and 40 per component. */
+typedef struct swg_component_params {
+  uint64_t min_bases;
+  uint32_t min_share_ppm; /* <= 1000000 */
+  uint32_t reserved;      /* 0 */
+} swg_component_params;
+typedef struct swg_link {
+  uint32_t a, b; /* a < b */
+  uint32_t n_records;
+  uint32_t joined; /* 0 or 1 */
+  uint64_t a_bases, b_bases;
+  uint64_t first_record;
+} swg_link; /* 40 bytes */
+typedef struct swg_component {
+  uint32_t id, first_seq, n_seq, n_links;
+  uint64_t length, n_records, bases;
+} swg_component; /* 40 bytes */
+typedef struct swg_component_table {
+  uint64_t n_components;       /* out */
+  uint64_t component_capacity; /* in: entries `components` can hold */
+  swg_component* components;   /* in: caller-owned [component_capacity] or NULL; written only when n_components <= component_capacity */
+  uint64_t n_links;            /* out */
+  uint64_t link_capacity;      /* in */
+  swg_link* links;             /* in: caller-owned [link_capacity] or NULL; written only when n_links <= link_capacity */
+  uint32_t* seq_component;     /* in: caller-owned [n_seq] or NULL */
+  uint64_t cross_links, cross_records, cross_bases; /* out */
+} swg_component_table;
+/* rec: host pointers; seq_len[n_seq] and status[n] (or NULL) on the host; params NULL = the defaults 0, 0. */
+int swg_components_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint8_t* status,
+                           const swg_component_params* params, swg_component_table* table);
+/* The same with the six columns of rec, seq_len and status in device memory of ctx's GPU (status as swg_filter_device leaves
+ * it: no copy in between); params, the table structure and its three arrays stay on the host. */
+int swg_components_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint8_t* status,
+                                  const swg_component_params* params, swg_component_table* table);
+/* The components of an open PAF as text (release it with swg_free), tab-separated, a header line
+ *   sequence length component component_sequences component_length links records bases
+ * and one row per sequence in sequence-id order: length = the sequence's last-seen length (the line that mentions it last has
+ * the last word, its target column after its query column: the rule of swg_paf_alnstats' genome sizes, read from the handle's
+ * text -- which is also seq_len of the call); links, records, bases = the sums n_links, n_records, a_bases + b_bases over the
+ * sequence's own links.  With `detailed` a line `#links` follows and per link, in ascending (a, b), by name:
+ *   a b records a_bases b_bases joined
+ * A last line `#cross <links> <records> <bases>` closes the text.  A PAF without records gives the header and `#cross 0 0 0`
+ * (and `#links`) and needs no device (ctx may be NULL then).  A handle whose columns are rebased (the file has a value >=
+ * 2^32): SWG_ERR_UNSUPPORTED.  Errors: text in swg_alnstats_last_error().  .1aln handles keep no text: the record seams above
+ * work on swg_aln_records. */
+int swg_paf_components(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_component_params* params, int detailed,
+                       char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

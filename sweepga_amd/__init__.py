@@ -11,6 +11,8 @@ from .paf import PafFile  # noqa: F401
 from .aln import AlnRecords  # noqa: F401
 from .alnstats import AlnStats  # noqa: F401
 from .blocks import BLOCK_DTYPE, Blocks, blocks_records, blocks_records_device  # noqa: F401
+from .components import (COMPONENT_DTYPE, LINK_DTYPE, Components, components_records,  # noqa: F401
+                         components_records_device)
 from .breadth import BREADTH_PAIR_DTYPE, Breadth, breadth_records, breadth_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401
                   parse_identity_value)

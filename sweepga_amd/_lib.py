@@ -36,7 +36,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_aln_tree_select", "swg_paf_num_genomes_two", "swg_paf_genome_two_prefix", "swg_aln_num_genomes_two",
            "swg_aln_genome_two_prefix",
            "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth",
-           "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks"]
+           "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks",
+           "swg_components_records", "swg_components_records_device", "swg_paf_components"]
 
 
 class SwgError(RuntimeError):
@@ -142,6 +143,27 @@ class SwgBlock(C.Structure):
 
 class SwgBlockTable(C.Structure):
     _fields_ = [("n_blocks", C.c_uint64), ("block_capacity", C.c_uint64), ("blocks", C.POINTER(SwgBlock))]
+
+
+class SwgComponentParams(C.Structure):
+    _fields_ = [("min_bases", C.c_uint64), ("min_share_ppm", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SwgLink(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("a", "b", "n_records", "joined")] + \
+               [(k, C.c_uint64) for k in ("a_bases", "b_bases", "first_record")]
+
+
+class SwgComponent(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("id", "first_seq", "n_seq", "n_links")] + \
+               [(k, C.c_uint64) for k in ("length", "n_records", "bases")]
+
+
+class SwgComponentTable(C.Structure):
+    _fields_ = [("n_components", C.c_uint64), ("component_capacity", C.c_uint64), ("components", C.POINTER(SwgComponent)),
+                ("n_links", C.c_uint64), ("link_capacity", C.c_uint64), ("links", C.POINTER(SwgLink)),
+                ("seq_component", C.POINTER(C.c_uint32)),
+                ("cross_links", C.c_uint64), ("cross_records", C.c_uint64), ("cross_bases", C.c_uint64)]
 
 
 _lib = None
@@ -328,6 +350,13 @@ def load():
         f = getattr(lib, name)
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.POINTER(SwgBlockTable)]
+    for name in ("swg_components_records", "swg_components_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.POINTER(SwgComponentParams), C.POINTER(SwgComponentTable)]
+    lib.swg_paf_components.restype = C.c_int
+    lib.swg_paf_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgComponentParams), C.c_int, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_uint64)]
     lib.swg_paf_blocks.restype = C.c_int
     lib.swg_paf_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_breadth.restype = C.c_int

@@ -60,6 +60,19 @@ int swg_blocks_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const u
 // the --blocks text: names and lengths from the line of each block's first record
 int swg_paf_blocks_text(const swg_paf* p, const std::vector<swg_block>& blocks, char** out_text, uint64_t* out_len);
 
+// ---- components (swg_components.hip: kernels, seams and the text; paf_io.cpp: the lengths) ----
+struct swg_components_result {
+  std::vector<swg_component> components;  // ascending id
+  std::vector<swg_link> links;            // ascending (a, b)
+  std::vector<uint32_t> seq_component;    // [n_seq]
+  uint64_t cross_links = 0, cross_records = 0, cross_bases = 0;
+};
+// want_links / want_seq: whether the two long arrays are copied back at all (the counts always are)
+int swg_components_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_len, const uint8_t* status,
+                       const swg_component_params* params, bool want_links, bool want_seq, swg_components_result* res);
+// per sequence of the handle, the length on the line that mentions it last (target column after query column)
+int swg_paf_seq_last_lengths(const swg_paf* p, std::vector<uint32_t>* seq_len);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

@@ -956,6 +956,31 @@ int swg_paf_stats_genome_sizes(const swg_paf* p, const swg_alnstats_result& r, s
   return SWG_OK;
 }
 
+// seq_len of swg_paf_components: the rule of the genome sizes above with every record in the set -- the
+// last record that names a sequence has the last word, its target column after its query column.
+int swg_paf_seq_last_lengths(const swg_paf* p, std::vector<uint32_t>* seq_len) {
+  const uint64_t n = p->rec.n;
+  std::vector<uint64_t> last(p->names.size(), UINT64_MAX);
+  for (uint64_t r = 0; r < n; ++r) {
+    last[p->rec.q_id[r]] = 2 * r;
+    last[p->rec.t_id[r]] = 2 * r + 1;
+  }
+  seq_len->assign(last.size(), 0);
+  for (size_t s = 0; s < last.size(); ++s) {
+    const uint64_t v = last[s];
+    if (v == UINT64_MAX) continue;
+    size_t len;
+    const char* b = stats_column(p, v >> 1, (v & 1) ? 6 : 1, &len);
+    uint64_t size;
+    if (!parse_u64(b, len, &size))
+      return swg_alnstats_error(SWG_ERR_INVALID, "%s (line %llu)", SWG_ALNSTATS_FIELD_ERR[(v & 1) ? 3 : 0], (unsigned long long)(p->rank[v >> 1] + 1));
+    if (size > 0xffffffffull)
+      return swg_alnstats_error(SWG_ERR_RANGE, "sequence length >= 2^32 on line %llu", (unsigned long long)(p->rank[v >> 1] + 1));
+    (*seq_len)[s] = (uint32_t)size;
+  }
+  return SWG_OK;
+}
+
 // The --blocks text: one PAF line per block; columns 1, 2, 6 and 7 are the bytes of the first record's line.
 int swg_paf_blocks_text(const swg_paf* p, const std::vector<swg_block>& blocks, char** out_text, uint64_t* out_len) {
   std::string o;

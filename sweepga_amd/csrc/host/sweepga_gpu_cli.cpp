@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <string_view>
@@ -282,6 +283,21 @@ void write_blocks(const std::string& path, swg_ctx* ctx, const swg_paf* paf, con
   swg_free(text);
 }
 
+// --components: the report of swg_paf_components (each sequence's component under the kept mappings).  "-" = standard error.
+void write_components(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const swg_component_params& par,
+                      bool detailed) {
+  char* text = nullptr;
+  uint64_t len = 0;
+  if (swg_paf_components(ctx, paf, status, &par, detailed ? 1 : 0, &text, &len) != SWG_OK)
+    die(3, std::string("--components: ") + swg_alnstats_last_error());
+  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
+  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+  if (f == stderr) std::fflush(stderr);
+  swg_free(text);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -301,6 +317,9 @@ int main(int argc, char** argv) {
   std::string breadth_path;  // --breadth: empty = no report
   bool breadth_detailed = false;
   std::string blocks_path;  // --blocks: empty = no file
+  std::string components_path;  // --components: empty = no report
+  bool components_detailed = false, component_flag = false;  // (component_flag: one of the two threshold flags was given)
+  swg_component_params component_par{0, 0, 0};
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -364,6 +383,18 @@ int main(int argc, char** argv) {
     else if (a == "--breadth") { breadth_path = value(); if (breadth_path.empty()) die(2, "empty value for --breadth"); }
     else if (a == "--breadth-detailed") breadth_detailed = true;
     else if (a == "--blocks") { blocks_path = value(); if (blocks_path.empty()) die(2, "empty value for --blocks"); }
+    else if (a == "--components") { components_path = value(); if (components_path.empty()) die(2, "empty value for --components"); }
+    else if (a == "--components-detailed") components_detailed = true;
+    else if (a == "--component-min-bases") {
+      if (!parse_metric_number(value(), &component_par.min_bases)) die(2, "bad --component-min-bases");
+      component_flag = true;
+    }
+    else if (a == "--component-min-share") {
+      double share = 0.0;
+      if (!parse_f64(value(), &share) || !(share >= 0.0 && share <= 1.0)) die(2, "invalid value for --component-min-share: a share in [0, 1]");
+      component_par.min_share_ppm = (uint32_t)std::llround(share * 1e6);
+      component_flag = true;
+    }
     else if (a == "--joblist") joblist = true;
     else if (a == "--joblist-output-dir") joblist_dir = value();
     else if (a == "--mash-kmer-size") { if (!parse_u64(value(), &mash_k)) die(2, "invalid value for --mash-kmer-size"); }
@@ -376,6 +407,7 @@ int main(int argc, char** argv) {
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
                 "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
                 "         [--blocks FILE|-]\n"
+                "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -389,6 +421,13 @@ int main(int argc, char** argv) {
                 "                      matches and block length, and the tags ch:Z: nc:i: ni:i: nr:i: (core, inverted, rescued mappings)\n"
                 "                      qc:i: tc:i: (bases under at least one of them) id:f: -- built on the device (- = standard error);\n"
                 "                      empty with --no-filter or --scaffold-jump 0, which make no chains\n"
+                "  --components REPORT after the filter: per sequence its component -- the connected sets of sequences over the links\n"
+                "                      between sequence pairs that the kept mappings make -- with the component's sequences and length\n"
+                "                      and the sequence's own links, records and bases, as a tab-separated table computed on the device\n"
+                "                      (- = standard error); with --no-filter every record takes part\n"
+                "  --components-detailed  with --components: one row per link (a b records a_bases b_bases joined) after `#links`\n"
+                "  --component-min-bases N  with --components: a link joins only if the bases on one of its ends reach N (k/m/g)\n"
+                "  --component-min-share F  with --components: ... and cover the share F in [0, 1] of one end's length\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -399,6 +438,8 @@ int main(int argc, char** argv) {
   }
   if (joblist) return run_joblist(inputs, sparsify, mash_k, mash_s, threads_given ? (uint64_t)threads : 8, block_length, joblist_dir,
                                   output_file, device);
+  if (components_path.empty() && (components_detailed || component_flag))
+    die(2, "--components-detailed, --component-min-bases and --component-min-share need --components");
   if (input.empty()) die(2, "usage: sweepga-gpu <in.paf> [--output-file out.paf] [filter flags]   (--help)");
 
   if (!no_filter && !bad_sparsify.empty()) die(1, "--sparsify '" + bad_sparsify + "' is not valid for post-alignment PAF/1aln filtering");
@@ -462,7 +503,7 @@ int main(int argc, char** argv) {
   std::string init_err;
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
-    if (no_filter && breadth_path.empty()) return;  // (--no-filter opens a device only for the breadth report)
+    if (no_filter && breadth_path.empty() && components_path.empty()) return;  // (--no-filter opens a device only for these two reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
       swg_ctx* c = nullptr;
@@ -508,6 +549,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--breadth: the file has a value >= 2^32, its columns are rebased: breadth of 64-bit columns is not supported");
   }
+  if (!components_path.empty() && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--components: the file has a value >= 2^32, its columns are rebased: components of 64-bit columns are not supported");
+  }
   if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
@@ -546,6 +591,11 @@ int main(int argc, char** argv) {
     if (!blocks_path.empty()) {  // no filter, no chains
       std::fflush(out);
       write_blocks(blocks_path, nullptr, paf, nullptr, nullptr);
+    }
+    if (!components_path.empty()) {  // nothing is dropped: every record takes part
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      write_components(components_path, ctxs.empty() ? nullptr : ctxs[0], paf, nullptr, component_par, components_detailed);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -659,6 +709,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_blocks(blocks_path, ctx, paf, status.data(), chain.data());
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --blocks: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --components: on the first context, from the (merged) status the filter left
+  if (!components_path.empty()) {
+    const auto tb = clk::now();
+    write_components(components_path, ctx, paf, status.data(), component_par, components_detailed);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --components: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

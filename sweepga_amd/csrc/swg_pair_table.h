@@ -13,7 +13,8 @@
 // A kernel keeps its own per-record loop and its own __global__ entry for the listing (the profile's launch labels are kernel
 // names); everything it does to a table goes through here.  Integer atomics only.  Below the scheme: what the host entries of
 // the three users share (grid_for, share_for, reserve_first, stage_columns).  swg_blocks.hip reduces per chain into a dense table
-// of its own and borrows the run and wavefront helpers only.
+// of its own and borrows the run and wavefront helpers only.  swg_components.hip keys the same table by SEQUENCE pair: three
+// sums (bases of either end, records) and the ALL first record; it lists the slots itself, as swg_link (table_alloc, table_clear).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -69,13 +70,11 @@ struct PairList {
   uint64_t cap;
 };
 
-// Sizes the table for G genomes of which at most pairs_max pairs occur (hashed: twice the slots of the keys that can occur),
-// takes it and its lists from the running arena frame and clears it on the context's stream.
+// Sizes the table for G key halves (genomes; sequences for swg_components.hip, whose key is a * n_seq + b) of which at most
+// pairs_max pairs occur (hashed: twice the slots of the keys that can occur) and takes it from the running arena frame;
+// table_clear, behind the caller's SWG_CHECK_ARENA, clears it on the context's stream.
 template <int Q, bool FIRST>
-int table_create(swg_ctx* ctx, uint32_t G, uint64_t pairs_max, bool force_hash, bool kept_list, unsigned long long* count,
-                 PairTable<Q, FIRST>* T, PairList<Q, FIRST>* L) {
-  using Entry = typename PairList<Q, FIRST>::Entry;
-  hipStream_t st = ctx->stream;
+void table_alloc(swg_ctx* ctx, uint32_t G, uint64_t pairs_max, bool force_hash, PairTable<Q, FIRST>* T) {
   const uint64_t g2 = (uint64_t)G * G;
   *T = PairTable<Q, FIRST>{};
   if (g2 <= DENSE_LIMIT && !force_hash) {
@@ -87,15 +86,28 @@ int table_create(swg_ctx* ctx, uint32_t G, uint64_t pairs_max, bool force_hash, 
   }
   T->sums = swg_alloc<unsigned long long>(ctx, T->slots * Q);
   if (FIRST) T->first = swg_alloc<uint32_t>(ctx, T->slots * 2);
+}
+template <int Q, bool FIRST>
+int table_clear(swg_ctx* ctx, const PairTable<Q, FIRST>& T) {
+  hipStream_t st = ctx->stream;
+  if (T.keys) SWG_HIP(ctx, hipMemsetAsync(T.keys, 0xff, T.slots * sizeof(unsigned long long), st));
+  SWG_HIP(ctx, hipMemsetAsync(T.sums, 0, T.slots * Q * sizeof(unsigned long long), st));
+  if (FIRST) SWG_HIP(ctx, hipMemsetAsync(T.first, 0xff, T.slots * 2 * sizeof(uint32_t), st));
+  return SWG_OK;
+}
+
+// The table with its lists: the genome-pair users' entry.
+template <int Q, bool FIRST>
+int table_create(swg_ctx* ctx, uint32_t G, uint64_t pairs_max, bool force_hash, bool kept_list, unsigned long long* count,
+                 PairTable<Q, FIRST>* T, PairList<Q, FIRST>* L) {
+  using Entry = typename PairList<Q, FIRST>::Entry;
+  table_alloc(ctx, G, pairs_max, force_hash, T);
   L->cap = pairs_max ? pairs_max : 1;
   L->count = count;
   L->out[0] = swg_alloc<Entry>(ctx, L->cap);
   if (FIRST) L->out[FIRST] = swg_alloc<Entry>(ctx, kept_list ? L->cap : 1);
   SWG_CHECK_ARENA(ctx);
-  if (T->keys) SWG_HIP(ctx, hipMemsetAsync(T->keys, 0xff, T->slots * sizeof(unsigned long long), st));
-  SWG_HIP(ctx, hipMemsetAsync(T->sums, 0, T->slots * Q * sizeof(unsigned long long), st));
-  if (FIRST) SWG_HIP(ctx, hipMemsetAsync(T->first, 0xff, T->slots * 2 * sizeof(uint32_t), st));
-  return SWG_OK;
+  return table_clear(ctx, *T);
 }
 
 // The lists of a table after its listing kernel: `listed` is the host's copy of L.count.  `what` names the caller in the error.
