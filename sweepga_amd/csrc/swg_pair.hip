@@ -595,9 +595,13 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
                    O_WS64 = lds_align_up(O_CELL + (size_t)NCELL * 4, 8), O_WS = O_WS64 + (size_t)(NT / 64 + 1) * 8,
                    O_SH = O_WS + (size_t)(NT / 64 + 1) * 4;
   static_assert(O_SH + 13 * 4 <= pair_sort_lds_bytes<NT, ES, ER, NBK, NBIN, PERM>(), "LDS block of the work-group");
+  // the two column buffers of the output phase: B0 is K, B1 lies over I and RR (dead by then)
+  static_assert(O_CNT - O_I >= (size_t)CAP * 4 && O_I % 16 == 0, "B1 holds CAP words, read 16 bytes at a time");
   uint32_t* const K = reinterpret_cast<uint32_t*>(lds_raw + O_K);
   IT* const I = reinterpret_cast<IT*>(lds_raw + O_I);
   uint16_t* const RR = reinterpret_cast<uint16_t*>(lds_raw + O_RR);
+  uint32_t* const B0 = K;
+  uint32_t* const B1 = reinterpret_cast<uint32_t*>(lds_raw + O_I);
   uint32_t* const cnt = reinterpret_cast<uint32_t*>(lds_raw + O_CNT);
   uint32_t* const bins = reinterpret_cast<uint32_t*>(lds_raw + O_BINS);
   uint32_t* const b_lo = reinterpret_cast<uint32_t*>(lds_raw + O_BLO);
@@ -1057,8 +1061,6 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
         o_pred[base + p] = NONE;
       }
     }
-    uint32_t qs_r[ES];  // the thread's own ES consecutive positions, for the unit cuts
-    read_block<ES>(K, qs_r);
 #pragma unroll
     for (int j = 0; j < ER / 2; ++j) {
       const uint32_t w = slotw[j];
@@ -1069,13 +1071,29 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
     lds_barrier();
     PT_STAMP(6);
     // ---- the other columns, transposed through LDS: coalesced reads in input order land at their sorted position, coalesced
-    // writes follow
-    auto put_group = [&](int g, const uint32_t (&v)[H]) {
+    // writes follow.  Two buffers take the columns in turn -- B0 is K, B1 the block of I and RR, which nothing reads once the
+    // barrier above has closed the key / index output -- so that a column's two halves overlap with its neighbours': the loads
+    // of column c are requested, column c - 1 is written out of its buffer while they are under way, column c is dropped
+    // into the other buffer, and ONE barrier closes the step.  The buffer of column c - 1 is next written by column c + 1,
+    // behind that barrier.  (Of a thread's records the first H ride across the stores and the next H are requested behind
+    // them, under way while the first are dropped; with 2 * H across the stores the large class needs more scratch than before.
+    // A pair of more than NT * 2 * H records takes its further groups one after the other as before.)
+    auto put_group = [&](uint32_t* buf, int g, const uint32_t (&v)[H]) {
 #pragma unroll
       for (int e = 0; e < H; ++e)
-        if ((batch_mask >> (g + e)) & 1u) K[(slotw[(g + e) / 2] >> (16 * ((g + e) & 1))) & 0xffffu] = v[e];
+        if ((batch_mask >> (g + e)) & 1u) buf[(slotw[(g + e) / 2] >> (16 * ((g + e) & 1))) & 0xffffu] = v[e];
     };
-    auto column = [&](const uint32_t* src, uint32_t* dst) {
+    auto store_column = [&](const uint32_t* buf, uint32_t* dst) {
+      const uint32_t t_st = fresh_tid();
+#pragma unroll
+      for (int e = 0; e < ES; ++e) {
+        const uint32_t p = t_st + (uint32_t)e * NT;
+        if (p < mb) dst[base + p] = buf[p];
+      }
+    };
+    // column `src` into `buf`; before that -- behind the requests of its first loads -- the previous column out of `pbuf` to
+    // `pdst` (has_prev).  The caller closes the step with a barrier.
+    auto column = [&](const uint32_t* src, uint32_t* buf, auto has_prev, const uint32_t* pbuf, uint32_t* pdst) {
       tid_v = fresh_tid();
 #pragma unroll
       for (int g = 0; g < ER; g += 2 * H) {
@@ -1083,54 +1101,62 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
         uint32_t v[H], w[H];
 #pragma unroll
         for (int e = 0; e < H; ++e) v[e] = src[rec_index(g + e)];
+        if constexpr (decltype(has_prev)::value) {
+          if (g == 0) {  // (the first group always runs: a pair has a record)
+            asm volatile("" ::: "memory");  // (the loads are requested first: the stores must not wait in front of them)
+            store_column(pbuf, pdst);
+          }
+        }
         if (g + H < ER) {
 #pragma unroll
           for (int e = 0; e < H; ++e) w[e] = src[rec_index(g + H + e)];
         }
-        put_group(g, v);
-        if (g + H < ER) put_group(g + H, w);
+        put_group(buf, g, v);
+        if (g + H < ER) put_group(buf, g + H, w);
         asm volatile("" ::: "memory");
       }
-      lds_barrier();
-      const uint32_t t_st = fresh_tid();
-#pragma unroll
-      for (int e = 0; e < ES; ++e) {
-        const uint32_t p = t_st + (uint32_t)e * NT;
-        if (p < mb) dst[base + p] = K[p];
-      }
     };
-    column(c_qe, o_qe);
-    {
-      uint32_t qe_r[ES];
-      read_block<ES>(K, qe_r);
+    constexpr std::true_type after_prev{};
+    column(c_qe, B1, std::false_type{}, nullptr, nullptr);
+    lds_barrier();
+    {  // the unit cuts, from the thread's own ES consecutive positions: B0 still holds the sorted q_start -- the next column goes
+      // there behind the barriers of unit_starts' scan, or, in a work-group of one wavefront, behind these reads in program order
+      // (before the step's loads are requested, not under them: registers)
+      uint32_t qs_r[ES], qe_r[ES];
+      read_block<ES>(B0, qs_r);
+      read_block<ES>(B1, qe_r);
 #pragma unroll
       for (int e = 0; e < ES; ++e) degenerate |= (uint32_t)tid * ES + e < mb && qs_r[e] >= qe_r[e];
-      unit_starts<NT, ES>(qs_r, qe_r, mb, base, m_plus, A.max_gap, ws64, cellmin, &carry_max);  // (its barriers also close the column)
+      unit_starts<NT, ES>(qs_r, qe_r, mb, base, m_plus, A.max_gap, ws64, cellmin, &carry_max);
     }
+    column(c_ts, B0, after_prev, B1, o_qe);
     lds_barrier();
     PT_STAMP(7);
-    column(c_ts, o_ts);
+    column(c_te, B1, after_prev, B0, o_ts);
     uint32_t ts_r[ES];
-    read_block<ES>(K, ts_r);
+    read_block<ES>(B0, ts_r);
     lds_barrier();
     PT_STAMP(8);
-    column(c_te, o_te);
+    if (A.s_m) {  // (nullptr: nobody asks for the chains' weighted identities -- no identity floor, no scaffold filter with limits)
+      column(c_m, B0, after_prev, B1, o_te);
+    } else {
+      store_column(B1, o_te);
+    }
     {
       uint32_t te_r[ES];
-      read_block<ES>(K, te_r);
+      read_block<ES>(B1, te_r);
 #pragma unroll
       for (int e = 0; e < ES; ++e) degenerate |= (uint32_t)tid * ES + e < mb && ts_r[e] >= te_r[e];
     }
-    lds_barrier();
     PT_STAMP(9);
-    if (A.s_m) {  // (nullptr: nobody asks for the chains' weighted identities -- no identity floor, no scaffold filter with limits)
-      column(c_m, o_m);
+    if (A.s_m) {
+      lds_barrier();
+      column(c_b, B1, after_prev, B0, o_m);
       lds_barrier();
       PT_STAMP(10);
-      column(c_b, o_b);
+      store_column(B1, o_b);
     }
-    base += mb;
-    lds_barrier();
+    base += mb;  // (no barrier here: the next batch passes several before it writes K, I or RR)
     PT_STAMP(11);
   }
   if (A.check_degenerate && __any(degenerate) && (tid & 63) == 0) atomicOr(&A.C->flags, PF_FALLBACK);
