@@ -704,6 +704,67 @@ int swg_components_records_device(swg_ctx* ctx, const swg_records* rec, const ui
 int swg_paf_components(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_component_params* params, int detailed,
                        char** out_text, uint64_t* out_len);
 
+/* ---- intervals: WHERE the coverage lies, as merged intervals, on the device ---------------------------
+ * Breadth (above) says how many bases of a sequence lie under at least one mapping; this says which.  Units and the counting
+ * rule are breadth's: only records whose two genomes differ under the caller's seq_genome map count; on the query axis (0) the
+ * unit is (query sequence, genome of the target) over [q_start, q_end), on the target axis (1) it is (target sequence, genome of
+ * the query) over [t_start, t_end).  Intervals are half-open, zero-length records add nothing, touching intervals join, the
+ * intervals of one sequence against two genomes are never merged with each other, start <= end is assumed.  Per unit:
+ *   SWG_IV_ALL   the maximal intervals of the union over all counted records
+ *   SWG_IV_KEPT  the same over the records with status != 0 (the rule of swg_paf_write)
+ *   SWG_IV_LOST  the maximal intervals of ALL minus KEPT: covered by a mapping before the filter, by none after it.  Every KEPT
+ *                interval lies inside one ALL interval, so LOST is, inside every ALL interval, the gaps its KEPT intervals leave.
+ * A list is ordered by (seq, other_genome, start), ascending; that order and every value are independent of the order of the
+ * records.  q_id, t_id and the four coordinate columns are read (32-bit layout).  `want` selects the lists: bit (set * 2 +
+ * axis); a list whose bit is clear is left untouched, and the device passes only it would need are not launched (LOST needs the
+ * rows of ALL and KEPT of its axis on the device, not on the host).  For every wanted list n and bases = sum(end - start) are
+ * always written.  Capacity protocol of swg_breadth_counts, per list: n > capacity still returns SWG_OK and leaves `rows` alone
+ * (call once with capacity 0, then with the n that came back).  Errors: a NULL context (there is no CPU path), reserved != 0,
+ * want == 0 or a bit beyond the six, a KEPT or LOST bit with status == NULL, a sequence id >= n_seq or a genome id >=
+ * n_genome: SWG_ERR_INVALID; n >= 2^31 records: SWG_ERR_RANGE.  Scratch comes from the context's arena, SWG_ERR_OOM when the
+ * memory limit does not hold it: 28 bytes per record (two 8-byte key buffers, two 4-byte value buffers, one 4-byte buffer of
+ * ends; both axes use the same ones) plus the radix sort's histograms and the segment set, and per axis, while it runs, 16
+ * bytes per ALL / KEPT / LOST interval whose list is wanted or that LOST needs -- with LOST 16 more per ALL and KEPT interval
+ * (its sort key, a flag, a link).  swg_intervals_records stages its host columns there too: 25 more bytes per record. */
+typedef struct swg_interval {
+  uint32_t seq;          /* the sequence of the axis */
+  uint32_t other_genome; /* the genome on the other side */
+  uint32_t start, end;   /* half-open */
+} swg_interval; /* 16 bytes */
+typedef struct swg_interval_list {
+  uint64_t n;         /* out: intervals of this list */
+  uint64_t bases;     /* out: sum(end - start) over them */
+  uint64_t capacity;  /* in: entries `rows` can hold */
+  swg_interval* rows; /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+} swg_interval_list;
+#define SWG_IV_ALL 0
+#define SWG_IV_KEPT 1
+#define SWG_IV_LOST 2
+typedef struct swg_interval_request {
+  uint32_t want;     /* bit (set * 2 + axis), axis 0 = query, 1 = target; a clear bit leaves that list untouched */
+  uint32_t reserved; /* 0 */
+  swg_interval_list list[3][2]; /* [set][axis] */
+} swg_interval_request;
+/* rec: host pointers; seq_genome[rec->n_seq] and status[n] (NULL: only ALL lists) on the host. */
+int swg_intervals_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                          const uint8_t* status, swg_interval_request* req);
+/* The same with the six columns of rec, seq_genome and status in device memory of ctx's GPU (status as swg_filter_device leaves
+ * it: no copy in between); the request and its row arrays stay on the host. */
+int swg_intervals_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                                 const uint8_t* status, swg_interval_request* req);
+/* One set of an open PAF under its last-'#' genome map (that of swg_paf_breadth) as BED-like text (release it with swg_free),
+ * one line per interval, tab-separated:
+ *   sequence_name start end other_genome_name q|t
+ * the query-axis list first, then the target-axis list, each in list order.  Sequence names are the handle's, genome names keep
+ * their trailing '#'.  set: SWG_IV_ALL, SWG_IV_KEPT or SWG_IV_LOST, anything else SWG_ERR_INVALID; KEPT or LOST with status ==
+ * NULL: SWG_ERR_INVALID.  A PAF without records gives empty text and needs no device (ctx may be NULL then).  A handle whose
+ * columns are rebased (the file has a value >= 2^32): SWG_ERR_UNSUPPORTED.  Errors: text in swg_alnstats_last_error().  .1aln
+ * handles keep no names: the record seams above work on swg_aln_records. */
+int swg_paf_intervals(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int set, char** out_text, uint64_t* out_len);
+/* Several sets from ONE device call: bit s of `sets` asks for set s (at least one, none beyond bit 2); out_text[s] and
+ * out_len[s] of [3] arrays are written for those sets only, each text as swg_paf_intervals gives it and released with swg_free. */
+int swg_paf_interval_texts(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t sets, char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -14,6 +14,7 @@ from .blocks import BLOCK_DTYPE, Blocks, blocks_records, blocks_records_device  
 from .components import (COMPONENT_DTYPE, LINK_DTYPE, Components, components_records,  # noqa: F401
                          components_records_device)
 from .breadth import BREADTH_PAIR_DTYPE, Breadth, breadth_records, breadth_records_device  # noqa: F401
+from .intervals import INTERVAL_DTYPE, Intervals, intervals_records, intervals_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401
                   parse_identity_value)
 

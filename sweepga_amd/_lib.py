@@ -37,7 +37,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_aln_genome_two_prefix",
            "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth",
            "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks",
-           "swg_components_records", "swg_components_records_device", "swg_paf_components"]
+           "swg_components_records", "swg_components_records_device", "swg_paf_components",
+           "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts"]
 
 
 class SwgError(RuntimeError):
@@ -164,6 +165,18 @@ class SwgComponentTable(C.Structure):
                 ("n_links", C.c_uint64), ("link_capacity", C.c_uint64), ("links", C.POINTER(SwgLink)),
                 ("seq_component", C.POINTER(C.c_uint32)),
                 ("cross_links", C.c_uint64), ("cross_records", C.c_uint64), ("cross_bases", C.c_uint64)]
+
+
+class SwgInterval(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("seq", "other_genome", "start", "end")]
+
+
+class SwgIntervalList(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bases", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgInterval))]
+
+
+class SwgIntervalRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("list", (SwgIntervalList * 2) * 3)]   # list[set][axis]
 
 
 _lib = None
@@ -361,6 +374,14 @@ def load():
     lib.swg_paf_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_breadth.restype = C.c_int
     lib.swg_paf_breadth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_intervals_records", "swg_intervals_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgIntervalRequest)]
+    lib.swg_paf_intervals.restype = C.c_int
+    lib.swg_paf_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.swg_paf_interval_texts.restype = C.c_int
+    lib.swg_paf_interval_texts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p
     lib.swg_alnstats_last_error.argtypes = []
     _lib = lib

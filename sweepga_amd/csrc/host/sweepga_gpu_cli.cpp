@@ -298,6 +298,25 @@ void write_components(const std::string& path, swg_ctx* ctx, const swg_paf* paf,
   swg_free(text);
 }
 
+// --lost / --covered: the LOST and KEPT texts of swg_paf_interval_texts (where coverage went, where it stayed), both from one
+// device call when both are asked for.  "-" = standard error.
+void write_intervals(const std::string& lost_path, const std::string& covered_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status) {
+  char* text[3] = {nullptr, nullptr, nullptr};
+  uint64_t len[3] = {0, 0, 0};
+  const uint32_t sets = (lost_path.empty() ? 0u : 1u << SWG_IV_LOST) | (covered_path.empty() ? 0u : 1u << SWG_IV_KEPT);
+  if (swg_paf_interval_texts(ctx, paf, status, sets, text, len) != SWG_OK) die(3, std::string("--lost / --covered: ") + swg_alnstats_last_error());
+  for (int set : {SWG_IV_LOST, SWG_IV_KEPT}) {
+    const std::string& path = set == SWG_IV_LOST ? lost_path : covered_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[set] && std::fwrite(text[set], 1, len[set], f) != len[set]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[set]);
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -320,6 +339,7 @@ int main(int argc, char** argv) {
   std::string components_path;  // --components: empty = no report
   bool components_detailed = false, component_flag = false;  // (component_flag: one of the two threshold flags was given)
   swg_component_params component_par{0, 0, 0};
+  std::string lost_path, covered_path;  // --lost, --covered: empty = no file
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -385,6 +405,8 @@ int main(int argc, char** argv) {
     else if (a == "--blocks") { blocks_path = value(); if (blocks_path.empty()) die(2, "empty value for --blocks"); }
     else if (a == "--components") { components_path = value(); if (components_path.empty()) die(2, "empty value for --components"); }
     else if (a == "--components-detailed") components_detailed = true;
+    else if (a == "--lost") { lost_path = value(); if (lost_path.empty()) die(2, "empty value for --lost"); }
+    else if (a == "--covered") { covered_path = value(); if (covered_path.empty()) die(2, "empty value for --covered"); }
     else if (a == "--component-min-bases") {
       if (!parse_metric_number(value(), &component_par.min_bases)) die(2, "bad --component-min-bases");
       component_flag = true;
@@ -408,6 +430,7 @@ int main(int argc, char** argv) {
                 "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
                 "         [--blocks FILE|-]\n"
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
+                "         [--lost FILE|-] [--covered FILE|-]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -428,6 +451,12 @@ int main(int argc, char** argv) {
                 "  --components-detailed  with --components: one row per link (a b records a_bases b_bases joined) after `#links`\n"
                 "  --component-min-bases N  with --components: a link joins only if the bases on one of its ends reach N (k/m/g)\n"
                 "  --component-min-share F  with --components: ... and cover the share F in [0, 1] of one end's length\n"
+                "  --lost FILE         after the filter: the stretches that lay under at least one inter-genome mapping before the filter\n"
+                "                      and under none after it, as merged intervals per sequence and genome of the other side, one line\n"
+                "                      `sequence start end other_genome q|t` each, built on the device (- = standard error); empty with\n"
+                "                      --no-filter\n"
+                "  --covered FILE      after the filter: the same lines for the stretches the kept mappings still cover (with --no-filter:\n"
+                "                      those of all mappings); with --lost, both come from one device call\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -503,7 +532,8 @@ int main(int argc, char** argv) {
   std::string init_err;
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
-    if (no_filter && breadth_path.empty() && components_path.empty()) return;  // (--no-filter opens a device only for these two reports)
+    if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty())
+      return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
       swg_ctx* c = nullptr;
@@ -553,6 +583,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--components: the file has a value >= 2^32, its columns are rebased: components of 64-bit columns are not supported");
   }
+  if ((!lost_path.empty() || !covered_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--lost / --covered: the file has a value >= 2^32, its columns are rebased: intervals of 64-bit columns are not supported");
+  }
   if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
@@ -596,6 +630,12 @@ int main(int argc, char** argv) {
       std::fflush(out);
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       write_components(components_path, ctxs.empty() ? nullptr : ctxs[0], paf, nullptr, component_par, components_detailed);
+    }
+    if (!lost_path.empty() || !covered_path.empty()) {  // nothing is dropped: nothing is lost, what is covered is what all records cover
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_intervals(lost_path, covered_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data());
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -715,6 +755,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_components(components_path, ctx, paf, status.data(), component_par, components_detailed);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --components: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --lost / --covered: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (!lost_path.empty() || !covered_path.empty()) {
+    const auto tb = clk::now();
+    write_intervals(lost_path, covered_path, ctx, paf, status.data());
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lost / --covered: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

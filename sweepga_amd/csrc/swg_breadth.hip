@@ -41,19 +41,12 @@
 namespace {
 
 using namespace swg_pair_table;   // the genome-pair table, the run and wavefront helpers, the host entry helpers
-using namespace swg_union_tiles;  // the tile of the sorted order and its first pass
+using namespace swg_union_tiles;  // the tile of the sorted order and its first pass, the segment map and its keys
 enum { D_BAD = 0, D_SEGMENTS, D_LISTED, D_LISTED_KEPT, D_TOTAL };
 enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // a listed entry's sums
 
 using BreadthTable = PairTable<2 * Q_COUNT, true>;  // sums: [axis][bases ALL, union ALL, bases KEPT, union KEPT]
 using BreadthList = PairList<2 * Q_COUNT, true>;   // entries: Q_BASES .. T_UNION and the first record of the set
-struct SegMap {  // segment id -> sequence of the axis * G + genome of the other side
-  unsigned long long* set_keys;  // hashed: the set (segment = slot); nullptr = the product itself
-  uint32_t set_mask;
-  uint32_t G;
-  uint32_t sentinel;
-};
-
 // ---- keys --------------------------------------------------------------------------------------------------------------
 template <int AXIS>
 __global__ __launch_bounds__(TB) void breadth_keys_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
@@ -61,20 +54,7 @@ __global__ __launch_bounds__(TB) void breadth_keys_kernel(uint64_t n, const uint
                                                           const uint32_t* __restrict__ seq_genome, uint32_t n_seq, SegMap M,
                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                           unsigned long long* __restrict__ scalars) {
-  const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t q = q_id[i], t = t_id[i];
-  const uint32_t gq = q < n_seq ? seq_genome[q] : NONE32, gt = t < n_seq ? seq_genome[t] : NONE32;
-  uint64_t key = (uint64_t)M.sentinel << 32;
-  if (gq >= M.G || gt >= M.G) {
-    atomicOr(&scalars[D_BAD], 1ull);
-  } else if (gq != gt) {
-    const unsigned long long product = (unsigned long long)(AXIS ? t : q) * M.G + (AXIS ? gq : gt);
-    const uint32_t seg = M.set_keys ? table_slot(M.set_keys, M.set_mask, product) : (uint32_t)product;
-    key = ((uint64_t)seg << 32) | start[i];
-  }
-  keys[i] = key;
-  vals[i] = (uint32_t)i | (status && status[i] != 0 ? KEPT_FLAG : 0u);
+  segment_keys<AXIS>(n, q_id, t_id, start, status, seq_genome, n_seq, M, keys, vals, &scalars[D_BAD]);
 }
 
 // ---- one tile of the sorted order (load_tile, gather_tile: swg_union_tiles.h) ---------------------------------------------
@@ -213,8 +193,7 @@ struct DevCols {
 // inside an arena frame
 int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_breadth_result* all, swg_breadth_result* kept) {
   hipStream_t st = ctx->stream;
-  const char* knob = std::getenv("SWG_BREADTH_HASH");  // test knob: the hashed segment set and pair table at any size
-  const bool force_hash = knob && knob[0] == '1';
+  const bool force_hash = segmap_forced();  // test knob: the hashed segment set and pair table at any size
   const uint64_t ntiles = (n + TILE - 1) / TILE;
   unsigned long long* scalars = swg_alloc<unsigned long long>(ctx, D_TOTAL);
   uint64_t* keys = swg_alloc<uint64_t>(ctx, n);
@@ -223,20 +202,8 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
   uint32_t* vals_alt = swg_alloc<uint32_t>(ctx, n);
   uint32_t* ends = swg_alloc<uint32_t>(ctx, n);
   unsigned long long* tile_max = swg_alloc<unsigned long long>(ctx, 2 * ntiles);
-  // segments: the product while it (and the sentinel one past it) fits 32 bits, else slots of a set with room for twice the
-  // segments that can occur -- never more than 2^31 slots, so that slot and sentinel fit too (n < 2^31: a free slot always comes)
-  const uint64_t products = (uint64_t)n_seq * G;
-  SegMap M{};
-  M.G = G;
-  if (products <= 0xffffffffull && !force_hash) {
-    M.sentinel = (uint32_t)products;
-  } else {
-    const uint64_t want = pow2_at_least(2 * (products < n ? products : n));
-    const uint64_t set_cap = want < (uint64_t(1) << 31) ? want : uint64_t(1) << 31;
-    M.set_keys = swg_alloc<unsigned long long>(ctx, set_cap);
-    M.set_mask = (uint32_t)(set_cap - 1);
-    M.sentinel = (uint32_t)set_cap;
-  }
+  SegMap M;
+  segmap_alloc(ctx, n, n_seq, G, force_hash, &M);  // (swg_union_tiles.h)
   SWG_CHECK_ARENA(ctx);
   SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
   const int end_bit = 32 + swg_bits_for(M.sentinel);

@@ -4,13 +4,20 @@
 //
 //   load_tile / load_ends   a thread's ITEMS keys, values and (second pass) ends, 16-byte loads inside the array
 //   gather_tile             first pass: end = end_column[record] written in sorted order, and the tile's maximum of
-//                           P = unit << 32 | end -- over all records and, with KEPT, over those whose value carries KEPT_FLAG.
+//                           P = unit << 32 | end -- over all records and, with KEPT, over those whose value carries KEPT_FLAG
+//                           (with SKIP_EMPTY: over the records of non-zero length only -- swg_intervals.hip, which has to say
+//                           where an interval begins, needs a maximum that no empty record has raised).
 //                           Units ascend along the sorted order, so the maximum of P over any prefix belongs to the LAST unit of
 //                           the prefix: a plain running maximum of P is the segmented running maximum of the ends.  The carry
 //                           across work-groups is swg_inclusive_max_scan_u64 over these maxima; no work-group waits for another.
 //
+// The segment as a unit is shared by swg_breadth.hip and swg_intervals.hip: SegMap, segmap_alloc (the product or the hashed set)
+// and segment_keys (the body of a keys kernel).
+//
 // A kernel keeps its own __global__ entry (the profile's launch labels are kernel names) and its own second pass.
 #pragma once
+#include <cstdlib>
+
 #include "swg_pair_table.h"
 
 namespace swg_union_tiles {
@@ -22,7 +29,60 @@ constexpr int TILE = TB * ITEMS;           // ... per work-group
 constexpr uint32_t KEPT_FLAG = 0x80000000u;  // bit 31 of a value (n < 2^31 leaves it free)
 constexpr uint32_t INDEX_MASK = 0x7fffffffu;
 
+struct SegMap {  // segment id -> sequence of the axis * G + genome of the other side
+  unsigned long long* set_keys;  // hashed: the set (segment = slot); nullptr = the product itself
+  uint32_t set_mask;
+  uint32_t G;
+  uint32_t sentinel;
+};
+
+inline bool segmap_forced() {  // test knob: the hashed segment set (and breadth's hashed pair table) at any size
+  const char* knob = std::getenv("SWG_BREADTH_HASH");
+  return knob && knob[0] == '1';
+}
+
+// segments: the product while it (and the sentinel one past it) fits 32 bits, else slots of a set with room for twice the
+// segments that can occur -- never more than 2^31 slots, so that slot and sentinel fit too (n < 2^31: a free slot always comes).
+// The set comes from the running arena frame; the caller clears it (0xff) ahead of every axis' keys kernel.
+inline void segmap_alloc(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, bool force_hash, SegMap* M) {
+  const uint64_t products = (uint64_t)n_seq * G;
+  *M = SegMap{};
+  M->G = G;
+  if (products <= 0xffffffffull && !force_hash) {
+    M->sentinel = (uint32_t)products;
+  } else {
+    const uint64_t want = swg_pair_table::pow2_at_least(2 * (products < n ? products : n));
+    const uint64_t set_cap = want < (uint64_t(1) << 31) ? want : uint64_t(1) << 31;
+    M->set_keys = swg_alloc<unsigned long long>(ctx, set_cap);
+    M->set_mask = (uint32_t)(set_cap - 1);
+    M->sentinel = (uint32_t)set_cap;
+  }
+}
+
 #ifdef __HIPCC__
+// The body of a keys kernel, one thread per record, launched over n in work-groups of TB: key = segment << 32 | start, value =
+// record index | KEPT_FLAG.  Records that do not count get the segment `sentinel`; an id out of range sets *bad.
+template <int AXIS>
+__device__ __forceinline__ void segment_keys(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
+                                             const uint32_t* __restrict__ start, const uint8_t* __restrict__ status,
+                                             const uint32_t* __restrict__ seq_genome, uint32_t n_seq, const SegMap& M,
+                                             uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, unsigned long long* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t q = q_id[i], t = t_id[i];
+  const uint32_t gq = q < n_seq ? seq_genome[q] : swg_pair_table::NONE32, gt = t < n_seq ? seq_genome[t] : swg_pair_table::NONE32;
+  uint64_t key = (uint64_t)M.sentinel << 32;
+  if (gq >= M.G || gt >= M.G) {
+    atomicOr(bad, 1ull);
+  } else if (gq != gt) {
+    const unsigned long long product = (unsigned long long)(AXIS ? t : q) * M.G + (AXIS ? gq : gt);
+    const uint32_t seg = M.set_keys ? swg_pair_table::table_slot(M.set_keys, M.set_mask, product) : (uint32_t)product;
+    key = ((uint64_t)seg << 32) | start[i];
+  }
+  keys[i] = key;
+  vals[i] = (uint32_t)i | (status && status[i] != 0 ? KEPT_FLAG : 0u);
+}
+
 __device__ __forceinline__ void load_tile(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n, uint64_t p0,
                                           uint64_t (&k)[ITEMS], uint32_t (&v)[ITEMS]) {
   if (p0 + ITEMS <= n) {  // (arena blocks are 16-byte aligned and p0 is a multiple of 4)
@@ -54,7 +114,7 @@ __device__ __forceinline__ unsigned long long max64(unsigned long long a, unsign
 // The body of a gather kernel, launched over the tiles in work-groups of TB.  tile_max: [ntiles] maxima over all records and,
 // with KEPT, [ntiles] more over the flagged ones.  `sentinel`: the unit of the records that do not count (sorted to the end).
 // `heads` (optional): the number of units that occur is added to it.
-template <bool KEPT>
+template <bool KEPT, bool SKIP_EMPTY = false>
 __device__ __forceinline__ void gather_tile(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                             const uint32_t* __restrict__ end_col, uint32_t sentinel, uint32_t* __restrict__ ends,
                                             unsigned long long* __restrict__ tile_max, uint64_t ntiles, unsigned long long* __restrict__ heads_out) {
@@ -74,8 +134,10 @@ __device__ __forceinline__ void gather_tile(uint64_t n, const uint64_t* __restri
     e[j] = counted ? end_col[v[j] & INDEX_MASK] : 0u;  // (values are the indices the keys kernel wrote: < n)
     if (counted) {
       const unsigned long long P = ((unsigned long long)seg << 32) | e[j];
-      m_all = max64(m_all, P);
-      if (KEPT && (v[j] & KEPT_FLAG)) m_kept = max64(m_kept, P);
+      if (!SKIP_EMPTY || e[j] > (uint32_t)k[j]) {
+        m_all = max64(m_all, P);
+        if (KEPT && (v[j] & KEPT_FLAG)) m_kept = max64(m_kept, P);
+      }
       heads += seg != before || p0 + j == 0;
     }
     before = seg;
