@@ -765,6 +765,73 @@ int swg_paf_intervals(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int
  * out_len[s] of [3] arrays are written for those sets only, each text as swg_paf_intervals gives it and released with swg_free. */
 int swg_paf_interval_texts(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t sets, char** out_text, uint64_t* out_len);
 
+/* ---- sharing: how many genomes cover each base, on the device ----------------------------------------
+ * Breadth and intervals (above) work per (sequence, other genome) unit; this counts ACROSS genomes.  The counting rule is
+ * breadth's: only records whose two genomes differ under the caller's seq_genome map count, intervals are half-open, zero-length
+ * records add nothing, start <= end is assumed, a record is KEPT when status != 0.  cover(s, g), g != genome(s), is the union of
+ * [q_start, q_end) over the counted records with q_id == s and genome(t_id) == g AND of [t_start, t_end) over those with t_id ==
+ * s and genome(q_id) == g: both axes in one union, so a base that a genome covers from both sides counts once.  depth(s, x) is
+ * the number of genomes g with x in cover(s, g), 0 .. n_genome - 1.  Per set (0 = all counted records, 1 = the kept ones):
+ *   runs      the maximal half-open intervals of a sequence with one depth >= 1, ordered by (seq, start); two touching stretches
+ *             of equal depth are one run, also where one genome's cover ends exactly where another's begins; depth 0 is not
+ *             listed.  bases = sum(end - start).
+ *   spectrum  spectrum[g * n_genome + d] = bases of the sequences of genome g at depth d.  With seq_len, d = 0 is the sum of
+ *             seq_len over the sequences of g minus the rest of the row (and then a genome id >= n_genome anywhere in seq_genome,
+ *             or a counted record that ends beyond seq_len of its sequence, is SWG_ERR_INVALID); with seq_len == NULL column 0
+ *             stays 0.
+ * Order and values are independent of the order of the records.  `want`: bit 0 = runs of ALL, bit 1 = runs of KEPT, bit 2 =
+ * spectrum of ALL, bit 3 = spectrum of KEPT; only the device passes the bits need are launched.  A runs bit writes n and bases of
+ * its list and, under the capacity protocol of swg_breadth_counts, its rows (n > capacity still returns SWG_OK and leaves `rows`
+ * alone); a spectrum bit writes all n_genome * n_genome entries of the caller's array and reads back no rows.  Errors: a NULL
+ * context (there is no CPU path), reserved != 0, want == 0 or a bit beyond the four, a KEPT bit with status == NULL, a spectrum
+ * bit with a NULL spectrum, a sequence id >= n_seq or a genome id >= n_genome: SWG_ERR_INVALID; n >= 2^30 records, or a spectrum
+ * bit with n_genome > 4096: SWG_ERR_RANGE.  Scratch comes from the context's arena, SWG_ERR_OOM when the memory limit does not
+ * hold it: 56 bytes per record (every record is sorted twice, once per axis) and, while a set's depth sweep runs, 66 bytes per
+ * merged interval of the set, 17 per breakpoint, 20 per run and 8 * n_genome^2 for a spectrum (DESIGN.md section 21 has the
+ * formula).  swg_sharing_records stages its host columns there too: 25 more bytes per record. */
+typedef struct swg_depth_run {
+  uint32_t seq;
+  uint32_t start, end; /* half-open */
+  uint32_t depth;      /* >= 1 */
+} swg_depth_run; /* 16 bytes */
+typedef struct swg_depth_list {
+  uint64_t n;          /* out (runs bit): runs of this set */
+  uint64_t bases;      /* out (runs bit): sum(end - start) over them */
+  uint64_t capacity;   /* in: entries `rows` can hold */
+  swg_depth_run* rows; /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+  uint64_t* spectrum;  /* in (spectrum bit): caller-owned [n_genome * n_genome], fully written */
+} swg_depth_list; /* 40 bytes */
+#define SWG_SHARING_RUNS_ALL 1u
+#define SWG_SHARING_RUNS_KEPT 2u
+#define SWG_SHARING_SPECTRUM_ALL 4u
+#define SWG_SHARING_SPECTRUM_KEPT 8u
+typedef struct swg_sharing_request {
+  uint32_t want;     /* the four bits above; a set neither of whose bits is given is left untouched */
+  uint32_t reserved; /* 0 */
+  swg_depth_list set[2]; /* 0 = ALL, 1 = KEPT */
+} swg_sharing_request; /* 88 bytes */
+/* rec: host pointers; seq_genome[rec->n_seq], seq_len[rec->n_seq] (or NULL) and status[n] (NULL: only the ALL bits) on the host. */
+int swg_sharing_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint32_t* seq_len,
+                        const uint8_t* status, swg_sharing_request* req);
+/* The same with the six columns of rec, seq_genome, seq_len and status in device memory of ctx's GPU; the request and its arrays
+ * stay on the host. */
+int swg_sharing_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome,
+                               const uint32_t* seq_len, const uint8_t* status, swg_sharing_request* req);
+/* Both texts of an open PAF under its last-'#' genome map from ONE device call: out_text[0] receives the table, out_text[1] the
+ * BED (release each with swg_free).  The caller marks the texts it wants on entry: an entry whose out_text[k] is NULL on entry is
+ * skipped (it stays NULL, out_len[k] = 0, and the device passes only it needs are not launched); any other value asks for text k
+ * and is replaced by it (it is never dereferenced).  Tab-separated:
+ *   table  header `genome length private_all shared_all core_all private_kept shared_kept core_kept`, one row per genome in
+ *          genome-id order (names keep their trailing '#'; length = sum of the last-seen lengths of swg_paf_components; private
+ *          = depth 0, core = depth n_genome - 1, shared = everything between; one genome: all private), then a `#total` row;
+ *          with `detailed` a `#spectrum` line and `genome all|kept depth bases` for every non-zero entry in (genome, set, depth)
+ *          order.
+ *   BED    `sequence start end n_all n_kept`: the maximal stretches of constant (n_all, n_kept) with n_all >= 1, ordered by
+ *          (sequence id, start), merged on the host from the two run lists.
+ * status is needed (SWG_ERR_INVALID without).  A PAF without records gives the header-only table and an empty BED and needs no
+ * device (ctx may be NULL then).  A handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+int swg_paf_sharing(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int detailed, char* out_text[2], uint64_t out_len[2]);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

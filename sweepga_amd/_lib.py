@@ -38,7 +38,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_breadth_records", "swg_breadth_records_device", "swg_paf_breadth",
            "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks",
            "swg_components_records", "swg_components_records_device", "swg_paf_components",
-           "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts"]
+           "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts",
+           "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing"]
 
 
 class SwgError(RuntimeError):
@@ -180,6 +181,19 @@ class SwgIntervalRequest(C.Structure):
 
 
 _lib = None
+
+
+class SwgDepthRun(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("depth", C.c_uint32)]
+
+
+class SwgDepthList(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bases", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgDepthRun)),
+                ("spectrum", C.POINTER(C.c_uint64))]
+
+
+class SwgSharingRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("set", SwgDepthList * 2)]   # set[ALL, KEPT]
 
 
 def load():
@@ -380,6 +394,12 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgIntervalRequest)]
     lib.swg_paf_intervals.restype = C.c_int
     lib.swg_paf_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_sharing_records", "swg_sharing_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(SwgSharingRequest)]
+    lib.swg_paf_sharing.restype = C.c_int
+    lib.swg_paf_sharing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_interval_texts.restype = C.c_int
     lib.swg_paf_interval_texts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p

@@ -317,6 +317,25 @@ void write_intervals(const std::string& lost_path, const std::string& covered_pa
   }
 }
 
+// --sharing / --sharing-bed: the table and the BED of swg_paf_sharing (how many genomes cover each base), both from one device call
+// when both are asked for.  "-" = standard error.
+void write_sharing(const std::string& table_path, const std::string& bed_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, bool detailed) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {table_path.empty() ? nullptr : &marker, bed_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_sharing(ctx, paf, status, detailed ? 1 : 0, text, len) != SWG_OK) die(3, std::string("--sharing: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? table_path : bed_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -340,6 +359,8 @@ int main(int argc, char** argv) {
   bool components_detailed = false, component_flag = false;  // (component_flag: one of the two threshold flags was given)
   swg_component_params component_par{0, 0, 0};
   std::string lost_path, covered_path;  // --lost, --covered: empty = no file
+  std::string sharing_path, sharing_bed_path;  // --sharing, --sharing-bed: empty = no file
+  bool sharing_detailed = false;
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -407,6 +428,9 @@ int main(int argc, char** argv) {
     else if (a == "--components-detailed") components_detailed = true;
     else if (a == "--lost") { lost_path = value(); if (lost_path.empty()) die(2, "empty value for --lost"); }
     else if (a == "--covered") { covered_path = value(); if (covered_path.empty()) die(2, "empty value for --covered"); }
+    else if (a == "--sharing") { sharing_path = value(); if (sharing_path.empty()) die(2, "empty value for --sharing"); }
+    else if (a == "--sharing-detailed") sharing_detailed = true;
+    else if (a == "--sharing-bed") { sharing_bed_path = value(); if (sharing_bed_path.empty()) die(2, "empty value for --sharing-bed"); }
     else if (a == "--component-min-bases") {
       if (!parse_metric_number(value(), &component_par.min_bases)) die(2, "bad --component-min-bases");
       component_flag = true;
@@ -431,6 +455,7 @@ int main(int argc, char** argv) {
                 "         [--blocks FILE|-]\n"
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
+                "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -457,6 +482,13 @@ int main(int argc, char** argv) {
                 "                      --no-filter\n"
                 "  --covered FILE      after the filter: the same lines for the stretches the kept mappings still cover (with --no-filter:\n"
                 "                      those of all mappings); with --lost, both come from one device call\n"
+                "  --sharing REPORT    after the filter: per genome the bases that no other genome covers (private), that every other\n"
+                "                      genome covers (core) and the rest (shared), over all records and over the kept ones, as a\n"
+                "                      tab-separated table; a genome covers a base when an inter-genome mapping to it lies over the base,\n"
+                "                      from either side.  Built on the device (- = standard error); with --no-filter kept = all\n"
+                "  --sharing-detailed  with --sharing: after `#spectrum`, `genome all|kept depth bases` for every depth that occurs\n"
+                "  --sharing-bed FILE  after the filter: `sequence start end n_all n_kept`, the stretches covered by a constant number\n"
+                "                      of genomes before (n_all >= 1) and after the filter; with --sharing, both come from one device call\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -469,6 +501,7 @@ int main(int argc, char** argv) {
                                   output_file, device);
   if (components_path.empty() && (components_detailed || component_flag))
     die(2, "--components-detailed, --component-min-bases and --component-min-share need --components");
+  if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
   if (input.empty()) die(2, "usage: sweepga-gpu <in.paf> [--output-file out.paf] [filter flags]   (--help)");
 
   if (!no_filter && !bad_sparsify.empty()) die(1, "--sparsify '" + bad_sparsify + "' is not valid for post-alignment PAF/1aln filtering");
@@ -532,7 +565,8 @@ int main(int argc, char** argv) {
   std::string init_err;
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
-    if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty())
+    if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
+        sharing_bed_path.empty())
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -587,6 +621,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--lost / --covered: the file has a value >= 2^32, its columns are rebased: intervals of 64-bit columns are not supported");
   }
+  if ((!sharing_path.empty() || !sharing_bed_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--sharing: the file has a value >= 2^32, its columns are rebased: sharing of 64-bit columns is not supported");
+  }
   if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
@@ -636,6 +674,12 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_intervals(lost_path, covered_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data());
+    }
+    if (!sharing_path.empty() || !sharing_bed_path.empty()) {  // nothing is dropped: the kept columns equal the all columns
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_sharing(sharing_path, sharing_bed_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), sharing_detailed);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -761,6 +805,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_intervals(lost_path, covered_path, ctx, paf, status.data());
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lost / --covered: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --sharing / --sharing-bed: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (!sharing_path.empty() || !sharing_bed_path.empty()) {
+    const auto tb = clk::now();
+    write_sharing(sharing_path, sharing_bed_path, ctx, paf, status.data(), sharing_detailed);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --sharing: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

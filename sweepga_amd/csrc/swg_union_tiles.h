@@ -6,7 +6,8 @@
 //   gather_tile             first pass: end = end_column[record] written in sorted order, and the tile's maximum of
 //                           P = unit << 32 | end -- over all records and, with KEPT, over those whose value carries KEPT_FLAG
 //                           (with SKIP_EMPTY: over the records of non-zero length only -- swg_intervals.hip, which has to say
-//                           where an interval begins, needs a maximum that no empty record has raised).
+//                           where an interval begins, needs a maximum that no empty record has raised; with TWO_AXES: the
+//                           value's AXIS_FLAG picks the end column -- swg_sharing.hip sorts both axes of a record together).
 //                           Units ascend along the sorted order, so the maximum of P over any prefix belongs to the LAST unit of
 //                           the prefix: a plain running maximum of P is the segmented running maximum of the ends.  The carry
 //                           across work-groups is swg_inclusive_max_scan_u64 over these maxima; no work-group waits for another.
@@ -28,6 +29,7 @@ constexpr int ITEMS = 4;                   // consecutive sorted records per thr
 constexpr int TILE = TB * ITEMS;           // ... per work-group
 constexpr uint32_t KEPT_FLAG = 0x80000000u;  // bit 31 of a value (n < 2^31 leaves it free)
 constexpr uint32_t INDEX_MASK = 0x7fffffffu;
+constexpr uint32_t AXIS_FLAG = 0x40000000u;  // TWO_AXES: bit 30 of a value, the entry is the record's target side (n < 2^30)
 
 struct SegMap {  // segment id -> sequence of the axis * G + genome of the other side
   unsigned long long* set_keys;  // hashed: the set (segment = slot); nullptr = the product itself
@@ -113,11 +115,13 @@ __device__ __forceinline__ unsigned long long max64(unsigned long long a, unsign
 
 // The body of a gather kernel, launched over the tiles in work-groups of TB.  tile_max: [ntiles] maxima over all records and,
 // with KEPT, [ntiles] more over the flagged ones.  `sentinel`: the unit of the records that do not count (sorted to the end).
-// `heads` (optional): the number of units that occur is added to it.
-template <bool KEPT, bool SKIP_EMPTY = false>
+// `heads` (optional): the number of units that occur is added to it.  TWO_AXES: end_col is the query end column, end_col_t the
+// target one.
+template <bool KEPT, bool SKIP_EMPTY = false, bool TWO_AXES = false>
 __device__ __forceinline__ void gather_tile(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                             const uint32_t* __restrict__ end_col, uint32_t sentinel, uint32_t* __restrict__ ends,
-                                            unsigned long long* __restrict__ tile_max, uint64_t ntiles, unsigned long long* __restrict__ heads_out) {
+                                            unsigned long long* __restrict__ tile_max, uint64_t ntiles, unsigned long long* __restrict__ heads_out,
+                                            const uint32_t* __restrict__ end_col_t = nullptr) {
   __shared__ unsigned long long l_max[2][WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
@@ -131,7 +135,10 @@ __device__ __forceinline__ void gather_tile(uint64_t n, const uint64_t* __restri
   for (int j = 0; j < ITEMS; ++j) {
     const uint32_t seg = (uint32_t)(k[j] >> 32);
     const bool counted = p0 + j < n && seg != sentinel;
-    e[j] = counted ? end_col[v[j] & INDEX_MASK] : 0u;  // (values are the indices the keys kernel wrote: < n)
+    if (TWO_AXES)
+      e[j] = counted ? ((v[j] & AXIS_FLAG) ? end_col_t : end_col)[v[j] & INDEX_MASK & ~AXIS_FLAG] : 0u;
+    else
+      e[j] = counted ? end_col[v[j] & INDEX_MASK] : 0u;  // (values are the indices the keys kernel wrote: < n)
     if (counted) {
       const unsigned long long P = ((unsigned long long)seg << 32) | e[j];
       if (!SKIP_EMPTY || e[j] > (uint32_t)k[j]) {
