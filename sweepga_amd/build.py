@@ -100,6 +100,24 @@ def build_sort_bench(force=False, verbose=False):
     return SORT_BENCH
 
 
+PRIM_CHECK_SRC = os.path.join(HERE, "..", "tests", "native", "prim_check.cpp")
+PRIM_CHECK = os.path.join(HERE, "bin", "prim_check")
+
+
+def build_prim_check(force=False, verbose=False):
+    """tests/native/prim_check.cpp: the scans, the flag compaction and the radix sorts case by case from a list, outputs to files
+    (a GPU box tool; tests/test_gpu_primitives_native.py runs it and checks every output against tests/prim_model.py)."""
+    if not force and os.path.exists(PRIM_CHECK) and os.path.getmtime(PRIM_CHECK) >= max(os.path.getmtime(PRIM_CHECK_SRC), os.path.getmtime(LIB)):
+        return PRIM_CHECK
+    os.makedirs(os.path.dirname(PRIM_CHECK), exist_ok=True)
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O2", "-std=c++17", PRIM_CHECK_SRC, "-o", PRIM_CHECK, "-L", HERE, "-lsweepga_gpu",
+           "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return PRIM_CHECK
+
+
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
@@ -178,6 +196,7 @@ def build(force=False, verbose=False):
     build_alnstats(force=force, verbose=verbose)
     build_synth(force=force, verbose=verbose)
     build_sort_bench(force=force, verbose=verbose)
+    build_prim_check(force=force, verbose=verbose)
     return LIB
 
 

@@ -187,8 +187,10 @@ static inline int swg_run_with_arena(swg_ctx* ctx, F&& body) {
   } while (0)
 
 // ---- primitives (swg_sort.hip) ---------------------------------------------------------------
-// Exclusive prefix sum of n u32 values, in place allowed (out may equal in).  If total_out is
-// non-null it receives the grand total (device pointer, u32... as u64).
+// Exclusive prefix sum of n u32 values, in place allowed (out may equal in).  The sums are taken in 32 bits: every
+// element of the output is the sum of the elements before it modulo 2^32 (callers scan +1 / 0xffffffff deltas and rely on
+// the wrap, swg_sharing.hip).  If total_out is non-null it receives the grand total (device pointer): the same 32-bit sum,
+// i.e. modulo 2^32, zero-extended into the u64 -- NOT the 64-bit sum of the elements (n = 0 writes 0).
 int swg_exclusive_scan_u32(swg_ctx* ctx, const uint32_t* in, uint32_t* out, uint64_t n,
                            uint64_t* d_total_out);
 // Inclusive running maximum of n u32 values (in place allowed).
