@@ -832,6 +832,73 @@ int swg_sharing_records_device(swg_ctx* ctx, const swg_records* rec, const uint3
  * device (ctx may be NULL then).  A handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
 int swg_paf_sharing(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, int detailed, char* out_text[2], uint64_t out_len[2]);
 
+/* ---- dot plot: the records before and after the filter, rasterised on the device ---------------------------
+ * x is the target axis, y the query axis; each is a concatenation of sequences: x_off[s] / y_off[s] is where sequence s begins on
+ * its axis, SWG_DOT_ABSENT = not on this axis; x_total / y_total are the axes' lengths.  px(a) = a * width / x_total, py(a) = a *
+ * height / y_total (floor, 64-bit); 1 <= width, height <= 16384 and 1 <= total < 2^48 keep the product below 2^62.  A record is
+ * DRAWN when q_end > q_start, t_end > t_start and both its sequences are on their axes (intra-genome and self records like any
+ * other; start <= end is assumed); it is KEPT when status != 0.  Endpoints: x0 = px(x_off[t] + t_start), x1 = px(x_off[t] + t_end
+ * - 1), ya = py(y_off[q] + q_start), yb = py(y_off[q] + q_end - 1); strand '+': (y0, y1) = (ya, yb), strand '-': (yb, ya), the
+ * line falls.  dx = x1 - x0, dy = |y1 - y0|, L = max(dx, dy); the record's pixels are, for k = 0 .. L,
+ *   x = x0 + (2 k dx + L) / (2 L),  y = y0 +- (2 k dy + L) / (2 L)      (floor; L = 0: the one pixel (x0, y0))
+ * so a record touches a pixel at most once.  Four uint32 count planes of height * width entries, index y * width + x with y = 0
+ * at the axis origin: plane 2 * set + strand, set 0 = all drawn records, set 1 = the kept ones, strand 0 = '+', 1 = '-'; a drawn
+ * record adds 1 to each of its pixels in its ALL plane, a kept one also in its KEPT plane.  hits[p] = the sum of plane p;
+ * drawn[set] = the drawn records of the set (drawn[1] = 0 without a status), always written.  Values do not depend on the order of
+ * the records.  Only the planes named by `want` are allocated, cleared, summed and read back: an unwanted plane's pointer is never
+ * touched, its hits stay as found.  q_id, t_id, the four coordinates and strand are read (32-bit layout).  Errors: a NULL context
+ * (there is no CPU path), reserved != 0, want == 0 or a bit beyond the four, a KEPT bit with status == NULL, a wanted plane with
+ * a NULL array, width, height or a total out of range, an id >= n_seq, a drawn record that ends beyond the total of an axis
+ * (x_off[t] + t_end > x_total, likewise y): SWG_ERR_INVALID; n >= 2^31 records: SWG_ERR_RANGE.  Scratch comes from the context's
+ * arena, SWG_ERR_OOM when the memory limit does not hold it: 4 bytes per record (the list of records longer than a pixel) and 4 *
+ * width * height per wanted plane; swg_dotplot_records stages its host columns there too: 26 more bytes per record and 16 per
+ * sequence. */
+#define SWG_DOT_ABSENT UINT64_MAX
+#define SWG_DOT_ALL_PLUS 1u   /* plane 0 */
+#define SWG_DOT_ALL_MINUS 2u  /* plane 1 */
+#define SWG_DOT_KEPT_PLUS 4u  /* plane 2 */
+#define SWG_DOT_KEPT_MINUS 8u /* plane 3 */
+typedef struct swg_dot_axes {
+  uint32_t width, height;
+  uint64_t x_total, y_total;
+  const uint64_t* x_off; /* [n_seq] */
+  const uint64_t* y_off; /* [n_seq] */
+} swg_dot_axes; /* 40 bytes */
+typedef struct swg_dot_request {
+  uint32_t want;      /* the four bits above */
+  uint32_t reserved;  /* 0 */
+  uint32_t* plane[4]; /* in: caller-owned [height * width], fully written when wanted */
+  uint64_t hits[4];   /* out, wanted planes only */
+  uint64_t drawn[2];  /* out: drawn records, ALL and KEPT */
+} swg_dot_request; /* 88 bytes */
+/* rec: host pointers; x_off, y_off and status[n] (NULL: only the ALL planes) on the host. */
+int swg_dotplot_records(swg_ctx* ctx, const swg_records* rec, const swg_dot_axes* axes, const uint8_t* status, swg_dot_request* req);
+/* The same with the six columns and strand of rec, status, x_off and y_off in device memory of ctx's GPU; the request and its
+ * planes stay on the host. */
+int swg_dotplot_records_device(swg_ctx* ctx, const swg_records* rec, const swg_dot_axes* axes, const uint8_t* status, swg_dot_request* req);
+/* The dot plot of an open PAF: out[0] receives the image, out[1] the layout table (release each with swg_free), under the marking
+ * protocol of swg_paf_sharing: an entry that is NULL on entry is skipped, any other value asks for text k and is replaced by it.
+ * The y axis holds the sequences that occur as the query of at least one record of the handle, whatever its status, and whose name
+ * starts with query_prefix (NULL or "" = all), ordered by (genome id under the last-'#' map, sequence id); the x axis the same for
+ * targets and target_prefix.  Lengths follow the last-seen rule of swg_paf_components, offsets are cumulative, the total is the
+ * sum.  The axes are made on the host from the handle's id columns; the four planes come from one device call.
+ *   image   binary PPM: `P6\n<W> <H>\n255\n` and 3 W H bytes; image row r is y = H - 1 - r (the origin is bottom-left).  The first
+ *           rule that holds gives the colour: kept+ + kept- > 0 and kept- > kept+ (200,30,30); kept+ + kept- > 0 (0,0,0); all+ +
+ *           all- > 0 and all- > all+ (245,190,190); all+ + all- > 0 (190,190,190); the pixel's column is px(off), or its row
+ *           py(off), of the first sequence of a genome other than the axis' first (225,232,245); otherwise (255,255,255).
+ *   layout  tab-separated, header `axis sequence genome offset length first_pixel last_pixel`, the rows of x, then of y, in axis
+ *           order (genome names keep their trailing '#'; first_pixel = px(offset), last_pixel = px(offset + length - 1); a
+ *           sequence of length 0: both px(min(offset, total - 1))).
+ * status is needed (SWG_ERR_INVALID without); width or height outside 1 .. 16384: SWG_ERR_INVALID.  A PAF without records, or an
+ * axis without a sequence or a base, gives an all-white image and the header-only table; that, and the layout alone, need no
+ * device (ctx may be NULL then).  A handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+typedef struct swg_dot_view {
+  uint32_t width, height;
+  const char* query_prefix;  /* NULL or "" = all */
+  const char* target_prefix; /* NULL or "" = all */
+} swg_dot_view; /* 24 bytes */
+int swg_paf_dotplot(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_dot_view* view, char* out[2], uint64_t out_len[2]);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -39,7 +39,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_blocks_records", "swg_blocks_records_device", "swg_paf_blocks",
            "swg_components_records", "swg_components_records_device", "swg_paf_components",
            "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts",
-           "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing"]
+           "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing",
+           "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot"]
 
 
 class SwgError(RuntimeError):
@@ -194,6 +195,20 @@ class SwgDepthList(C.Structure):
 
 class SwgSharingRequest(C.Structure):
     _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("set", SwgDepthList * 2)]   # set[ALL, KEPT]
+
+
+class SwgDotAxes(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("x_total", C.c_uint64), ("y_total", C.c_uint64),
+                ("x_off", C.c_void_p), ("y_off", C.c_void_p)]
+
+
+class SwgDotRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("plane", C.c_void_p * 4), ("hits", C.c_uint64 * 4),
+                ("drawn", C.c_uint64 * 2)]
+
+
+class SwgDotView(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("query_prefix", C.c_char_p), ("target_prefix", C.c_char_p)]
 
 
 def load():
@@ -400,6 +415,12 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(SwgSharingRequest)]
     lib.swg_paf_sharing.restype = C.c_int
     lib.swg_paf_sharing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_dotplot_records", "swg_dotplot_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.POINTER(SwgDotAxes), C.c_void_p, C.POINTER(SwgDotRequest)]
+    lib.swg_paf_dotplot.restype = C.c_int
+    lib.swg_paf_dotplot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgDotView), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_interval_texts.restype = C.c_int
     lib.swg_paf_interval_texts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p

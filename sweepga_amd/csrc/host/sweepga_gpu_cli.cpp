@@ -336,6 +336,44 @@ void write_sharing(const std::string& table_path, const std::string& bed_path, s
   }
 }
 
+// --dotplot / --dotplot-layout: the image and the layout table of swg_paf_dotplot, both from one device call when both are asked
+// for.  The layout's "-" = standard error.
+void write_dotplot(const std::string& image_path, const std::string& layout_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
+                   const swg_dot_view& view) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {image_path.empty() ? nullptr : &marker, layout_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_dotplot(ctx, paf, status, &view, text, len) != SWG_OK) die(3, std::string("--dotplot: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? image_path : layout_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
+// --dotplot-size: N or WxH, each side in 1 .. 16384
+bool parse_dot_size(const std::string& v, uint32_t* w, uint32_t* h) {
+  auto side = [](const std::string& t, uint32_t* out) {
+    if (t.empty() || t.size() > 5 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    const int x = std::atoi(t.c_str());
+    if (x < 1 || x > 16384) return false;
+    *out = (uint32_t)x;
+    return true;
+  };
+  const size_t x = v.find('x');
+  if (x == std::string::npos) {
+    if (!side(v, w)) return false;
+    *h = *w;
+    return true;
+  }
+  return side(v.substr(0, x), w) && side(v.substr(x + 1), h);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -361,6 +399,9 @@ int main(int argc, char** argv) {
   std::string lost_path, covered_path;  // --lost, --covered: empty = no file
   std::string sharing_path, sharing_bed_path;  // --sharing, --sharing-bed: empty = no file
   bool sharing_detailed = false;
+  std::string dotplot_path, dotplot_layout_path, dotplot_query, dotplot_target;  // --dotplot, --dotplot-layout: empty = no file
+  swg_dot_view dot_view{2048, 2048, nullptr, nullptr};
+  bool dotplot_flag = false;  // (one of --dotplot-size / --dotplot-query / --dotplot-target was given)
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -431,6 +472,20 @@ int main(int argc, char** argv) {
     else if (a == "--sharing") { sharing_path = value(); if (sharing_path.empty()) die(2, "empty value for --sharing"); }
     else if (a == "--sharing-detailed") sharing_detailed = true;
     else if (a == "--sharing-bed") { sharing_bed_path = value(); if (sharing_bed_path.empty()) die(2, "empty value for --sharing-bed"); }
+    else if (a == "--dotplot") {
+      dotplot_path = value();
+      if (dotplot_path.empty()) die(2, "empty value for --dotplot");
+      if (dotplot_path == "-") die(2, "--dotplot writes a binary image: it needs a file");
+    }
+    else if (a == "--dotplot-layout") { dotplot_layout_path = value(); if (dotplot_layout_path.empty()) die(2, "empty value for --dotplot-layout"); }
+    else if (a == "--dotplot-size") {
+      const std::string v = value();
+      if (v.empty()) die(2, "empty value for --dotplot-size");
+      if (!parse_dot_size(v, &dot_view.width, &dot_view.height)) die(2, "invalid value for --dotplot-size: N or WxH, each side in 1 .. 16384");
+      dotplot_flag = true;
+    }
+    else if (a == "--dotplot-query") { dotplot_query = value(); if (dotplot_query.empty()) die(2, "empty value for --dotplot-query"); dotplot_flag = true; }
+    else if (a == "--dotplot-target") { dotplot_target = value(); if (dotplot_target.empty()) die(2, "empty value for --dotplot-target"); dotplot_flag = true; }
     else if (a == "--component-min-bases") {
       if (!parse_metric_number(value(), &component_par.min_bases)) die(2, "bad --component-min-bases");
       component_flag = true;
@@ -456,6 +511,7 @@ int main(int argc, char** argv) {
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
+                "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -489,6 +545,15 @@ int main(int argc, char** argv) {
                 "  --sharing-detailed  with --sharing: after `#spectrum`, `genome all|kept depth bases` for every depth that occurs\n"
                 "  --sharing-bed FILE  after the filter: `sequence start end n_all n_kept`, the stretches covered by a constant number\n"
                 "                      of genomes before (n_all >= 1) and after the filter; with --sharing, both come from one device call\n"
+                "  --dotplot FILE      after the filter: a dot plot of the mappings as a binary PPM, targets along x and queries along y,\n"
+                "                      sequences in (genome, first appearance) order, the origin bottom-left: kept mappings black, kept\n"
+                "                      inversions red, dropped mappings grey, dropped inversions pink, genome borders pale blue.  Rasterised\n"
+                "                      on the device; with --no-filter kept = all\n"
+                "  --dotplot-size N|WxH  the image's size in pixels, each side in 1 .. 16384 (default 2048)\n"
+                "  --dotplot-layout FILE  `axis sequence genome offset length first_pixel last_pixel` for every sequence of either axis\n"
+                "                      (- = standard error); with --dotplot, both come from one device call\n"
+                "  --dotplot-query PREFIX   only query sequences whose name starts with PREFIX go on the y axis\n"
+                "  --dotplot-target PREFIX  only target sequences whose name starts with PREFIX go on the x axis\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -502,6 +567,10 @@ int main(int argc, char** argv) {
   if (components_path.empty() && (components_detailed || component_flag))
     die(2, "--components-detailed, --component-min-bases and --component-min-share need --components");
   if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
+  if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
+    die(2, "--dotplot-size, --dotplot-query and --dotplot-target need --dotplot or --dotplot-layout");
+  dot_view.query_prefix = dotplot_query.empty() ? nullptr : dotplot_query.c_str();
+  dot_view.target_prefix = dotplot_target.empty() ? nullptr : dotplot_target.c_str();
   if (input.empty()) die(2, "usage: sweepga-gpu <in.paf> [--output-file out.paf] [filter flags]   (--help)");
 
   if (!no_filter && !bad_sparsify.empty()) die(1, "--sparsify '" + bad_sparsify + "' is not valid for post-alignment PAF/1aln filtering");
@@ -566,7 +635,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty())
+        sharing_bed_path.empty() && dotplot_path.empty())
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -625,6 +694,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--sharing: the file has a value >= 2^32, its columns are rebased: sharing of 64-bit columns is not supported");
   }
+  if ((!dotplot_path.empty() || !dotplot_layout_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--dotplot: the file has a value >= 2^32, its columns are rebased: a dot plot of 64-bit columns is not supported");
+  }
   if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
@@ -680,6 +753,12 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_sharing(sharing_path, sharing_bed_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), sharing_detailed);
+    }
+    if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {  // nothing is dropped: the kept planes equal the all planes
+      std::fflush(out);
+      if (n && !dotplot_path.empty() && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_dotplot(dotplot_path, dotplot_layout_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), dot_view);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -811,6 +890,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_sharing(sharing_path, sharing_bed_path, ctx, paf, status.data(), sharing_detailed);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --sharing: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --dotplot / --dotplot-layout: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {
+    const auto tb = clk::now();
+    write_dotplot(dotplot_path, dotplot_layout_path, ctx, paf, status.data(), dot_view);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --dotplot: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 
