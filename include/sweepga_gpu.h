@@ -899,6 +899,83 @@ typedef struct swg_dot_view {
 } swg_dot_view; /* 24 bytes */
 int swg_paf_dotplot(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_dot_view* view, char* out[2], uint64_t out_len[2]);
 
+/* ---- lift: caller-given regions projected through the mappings, on the device ----------------------------
+ * A region is (seq, start, end), start <= end, half-open, on a sequence id of the record set; seq == UINT32_MAX is "a name the
+ * input does not have" and has no hits.  Regions are numbered 0 .. m - 1 in the order given; they may overlap, repeat or be empty.
+ * Record i is a HIT of region r on axis 0 (query) when q_id[i] == seq, q_end[i] > q_start[i] and max(start, q_start[i]) <
+ * min(end, q_end[i]); on axis 1 (target) the same with t_id, t_start, t_end.  Self and intra-genome records count like any other
+ * (no genome rule); a record with q_id == t_id can be a hit on both axes; start <= end of the records is assumed.  The set is
+ * SWG_IV_ALL (every record) or SWG_IV_KEPT (status != 0, the rule of swg_paf_write).  For a hit, [s0, s1) is the record's side on
+ * the axis (the source), [d0, d1) on dst_seq its other side, L = s1 - s0 > 0, D = d1 - d0; the clip is ca = max(start, s0), cb =
+ * min(end, s1), o0 = ca - s0, o1 = cb - s0, f(o) = floor(o D / L), c(o) = ceil(o D / L) in unsigned 64 bits (exact: o D <=
+ * (2^32 - 1)^2).  No CIGAR is on the device: the projection is linear interpolation, rounded outward,
+ *   strand '+':  dst = [d0 + f(o0), d0 + c(o1))        strand '-':  dst = [d1 - c(o1), d1 - f(o0))
+ * so a region that holds the whole source side gives exactly [d0, d1), dst lies inside [d0, d1], is non-empty whenever D > 0,
+ * and growing the region never shrinks it.  Rows are ordered by (region, axis, s0, record), s0 the record's own start on the
+ * axis; every value but `record` is independent of the order of the records, and the rows of a region do not depend on the other
+ * regions.  summary[r].hits[set][axis] counts the hits of region r in both sets from the same pass (KEPT: 0 without a status; an
+ * unwanted axis: 0): a region with hits in ALL and none in KEPT is one the filter left without a projection.  candidates[axis]
+ * is the number of index entries the join looked at (section 23: the price of the prune, >= the hits of ALL on that axis; among
+ * records with one start it depends on their order, the one figure here that does).
+ * Capacity protocol of swg_breadth_counts: n > capacity still returns SWG_OK, leaves `rows` alone and has not run the write
+ * pass.  m == 0 or n == 0 records needs no device work: n = 0 and zeroed summaries.  q_id, t_id, the four coordinates and strand
+ * are read (32-bit layout).  Errors: a NULL context (there is no CPU path), reserved != 0 (request or region), axes == 0 or a bit
+ * beyond bit 1, set > 1, KEPT without a status, a region with start > end or a seq that is neither < n_seq nor UINT32_MAX, a
+ * record id >= n_seq: SWG_ERR_INVALID; 2^31 records or regions or more: SWG_ERR_RANGE (so a region has fewer than 2^31 hits per
+ * set and axis, and the counters cannot overflow).  Scratch comes from the context's arena, SWG_ERR_OOM when the memory limit
+ * does not hold it: per wanted axis 24 bytes per record (two 8-byte key buffers, two 4-byte value buffers; the running maximum
+ * and the gathered ends live in the sort's spare pair), 12 bytes per region and 8 per tile of 1024 candidates; 16 bytes per region
+ * for the summary, 16 more when both axes give rows, and 32 per row when the rows are written.  swg_lift_records stages its host
+ * columns there too: 26 more bytes per record and 16 per region. */
+typedef struct swg_lift_region {
+  uint32_t seq, start, end;
+  uint32_t reserved; /* 0 */
+} swg_lift_region; /* 16 bytes */
+typedef struct swg_lift_row {
+  uint32_t region, record;     /* index into the regions; index into the records (what status[] indexes) */
+  uint32_t src_start, src_end; /* ca, cb */
+  uint32_t dst_seq;
+  uint32_t dst_start, dst_end;
+  uint32_t flags;              /* bit 0: strand (1 = '-'), bit 1: axis (1 = target); other bits 0 */
+} swg_lift_row; /* 32 bytes */
+typedef struct swg_lift_summary {
+  uint32_t hits[2][2]; /* [set][axis] */
+} swg_lift_summary; /* 16 bytes */
+#define SWG_LIFT_AXIS_QUERY 1u
+#define SWG_LIFT_AXIS_TARGET 2u
+#define SWG_LIFT_MINUS 1u /* row flags */
+#define SWG_LIFT_ON_TARGET 2u
+typedef struct swg_lift_request {
+  uint32_t set;              /* rows of SWG_IV_ALL (0) or SWG_IV_KEPT (1) */
+  uint32_t axes;             /* bit 0 query, bit 1 target; at least one */
+  uint64_t n;                /* out: rows */
+  uint64_t candidates[2];    /* out: candidates per axis (0 for an unwanted axis) */
+  uint64_t capacity;         /* in: entries `rows` can hold */
+  swg_lift_row* rows;        /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+  swg_lift_summary* summary; /* in: caller-owned [m] or NULL; written whenever non-NULL */
+} swg_lift_request; /* 56 bytes */
+/* rec: host pointers; status[n] (NULL: SWG_IV_ALL only) and regions[m] on the host. */
+int swg_lift_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                     swg_lift_request* req);
+/* The same with the six columns and strand of rec, status and regions in device memory of ctx's GPU; the request, its rows and
+ * its summary stay on the host. */
+int swg_lift_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                            swg_lift_request* req);
+/* BED regions lifted through an open PAF: out_text[0] receives the rows, out_text[1] the summary (release each with swg_free),
+ * under the marking protocol of swg_paf_sharing (an entry that is NULL on entry is skipped).  BED: tab-separated, columns 1-3
+ * (name, start, end) required, column 4 an optional label (default `name:start-end`); empty lines and lines starting with `#`,
+ * `track` or `browser` are skipped; a malformed line, start > end or a value >= 2^32 is SWG_ERR_INVALID with the line number in
+ * swg_alnstats_last_error(); a name the handle does not know becomes seq = UINT32_MAX.  set: SWG_IV_ALL or SWG_IV_KEPT (the
+ * rows' set; KEPT needs a status); axes as in the request.  Tab-separated texts:
+ *   rows     one line per row in row order: dst_name dst_start dst_end label src_name src_start src_end strand(+|-) axis(q|t) record
+ *   summary  header `label sequence start end all_q all_t kept_q kept_t state`, then one line per region in input order; state:
+ *            `unknown` for an unknown name, `none` without hits in ALL on the wanted axes, `lost` with hits in ALL and none in
+ *            KEPT, else `kept`.  Without a status the kept columns are `-` and state is `unknown`, `none` or `all`.
+ * The BED is always parsed.  Empty BED text, or a PAF without records, gives the header-only summary and empty rows, and needs
+ * no device (ctx may be NULL then).  A handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                 char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -40,7 +40,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_components_records", "swg_components_records_device", "swg_paf_components",
            "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts",
            "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing",
-           "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot"]
+           "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot",
+           "swg_lift_records", "swg_lift_records_device", "swg_paf_lift"]
 
 
 class SwgError(RuntimeError):
@@ -209,6 +210,23 @@ class SwgDotRequest(C.Structure):
 
 class SwgDotView(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("query_prefix", C.c_char_p), ("target_prefix", C.c_char_p)]
+
+
+class SwgLiftRegion(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("seq", "start", "end", "reserved")]
+
+
+class SwgLiftRow(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("region", "record", "src_start", "src_end", "dst_seq", "dst_start", "dst_end", "flags")]
+
+
+class SwgLiftSummary(C.Structure):
+    _fields_ = [("hits", (C.c_uint32 * 2) * 2)]   # hits[set][axis]
+
+
+class SwgLiftRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
+                ("rows", C.c_void_p), ("summary", C.c_void_p)]
 
 
 def load():
@@ -421,6 +439,13 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.POINTER(SwgDotAxes), C.c_void_p, C.POINTER(SwgDotRequest)]
     lib.swg_paf_dotplot.restype = C.c_int
     lib.swg_paf_dotplot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgDotView), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_lift_records", "swg_lift_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SwgLiftRequest)]
+    lib.swg_paf_lift.restype = C.c_int
+    lib.swg_paf_lift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_uint64)]
     lib.swg_paf_interval_texts.restype = C.c_int
     lib.swg_paf_interval_texts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p

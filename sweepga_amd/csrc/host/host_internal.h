@@ -73,6 +73,11 @@ int swg_components_run(swg_ctx* ctx, const swg_records* rec, bool on_device, con
 // per sequence of the handle, the length on the line that mentions it last (target column after query column)
 int swg_paf_seq_last_lengths(const swg_paf* p, std::vector<uint32_t>* seq_len);
 
+// ---- lift (swg_lift.hip: kernels and record seams; lift_text.cpp: the BED parser and the texts of swg_paf_lift) ----
+// columns of rec, status and regions on the host (on_device = false: staged in the arena) or on the device; req on the host
+int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                 swg_lift_request* req);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

@@ -1,0 +1,194 @@
+// swg_paf_lift: BED regions parsed on the host, lifted through an open PAF by one device call
+// (swg_lift.hip), and the two texts -- rows and per-region summary -- written with the handle's names.
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+#include <vector>
+
+#include "../../../include/sweepga_gpu.h"
+#include "host_internal.h"
+
+namespace {
+
+struct BedRegion {
+  std::string name, label;
+};
+
+bool starts_with(std::string_view s, const char* prefix) { return s.substr(0, std::strlen(prefix)) == prefix; }
+
+// decimal digits only, a value below 2^32
+bool parse_u32(std::string_view t, uint32_t* out) {
+  if (t.empty() || t.size() > 10) return false;
+  uint64_t v = 0;
+  for (char ch : t) {
+    if (ch < '0' || ch > '9') return false;
+    v = v * 10 + (uint64_t)(ch - '0');
+  }
+  if (v >> 32) return false;
+  *out = (uint32_t)v;
+  return true;
+}
+
+// The regions of a BED text in line order.  Tab-separated; name, start, end required, a non-empty fourth column is the label (default
+// name:start-end), further columns are ignored; empty lines and lines starting with '#', "track" or "browser" are skipped.
+int parse_bed(const char* bed, uint64_t len, const std::unordered_map<std::string_view, uint32_t>& ids, std::vector<swg_lift_region>* regions,
+              std::vector<BedRegion>* text) {
+  uint64_t line_no = 0;
+  for (uint64_t pos = 0; pos < len;) {
+    const void* nl = std::memchr(bed + pos, '\n', len - pos);
+    const uint64_t end = nl ? (uint64_t)((const char*)nl - bed) : len;
+    std::string_view line(bed + pos, end - pos);
+    pos = end + 1;
+    ++line_no;
+    if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+    if (line.empty() || line[0] == '#' || starts_with(line, "track") || starts_with(line, "browser")) continue;
+    std::string_view col[4];
+    int n_col = 0;
+    for (size_t at = 0; n_col < 4;) {
+      const size_t tab = line.find('\t', at);
+      col[n_col++] = line.substr(at, tab == std::string_view::npos ? std::string_view::npos : tab - at);
+      if (tab == std::string_view::npos) break;
+      at = tab + 1;
+    }
+    const unsigned long long ln = line_no;
+    if (n_col < 3) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: BED line %llu: fewer than three tab-separated columns", ln);
+    if (col[0].empty()) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: BED line %llu: empty sequence name", ln);
+    swg_lift_region g{0, 0, 0, 0};
+    if (!parse_u32(col[1], &g.start)) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: BED line %llu: start is not a number below 2^32", ln);
+    if (!parse_u32(col[2], &g.end)) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: BED line %llu: end is not a number below 2^32", ln);
+    if (g.start > g.end) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: BED line %llu: start > end", ln);
+    const auto it = ids.find(col[0]);
+    g.seq = it == ids.end() ? UINT32_MAX : it->second;
+    BedRegion b;
+    b.name.assign(col[0]);
+    if (n_col == 4 && !col[3].empty()) b.label.assign(col[3]);
+    else b.label = b.name + ':' + std::to_string(g.start) + '-' + std::to_string(g.end);
+    regions->push_back(g);
+    text->push_back(std::move(b));
+  }
+  return SWG_OK;
+}
+
+char* text_copy(const std::string& o) {
+  char* t = static_cast<char*>(std::malloc(o.size() + 1));
+  if (!t) return nullptr;
+  std::memcpy(t, o.data(), o.size());
+  t[o.size()] = 0;
+  return t;
+}
+
+void append_u64(std::string& o, uint64_t v, char sep) {
+  o += std::to_string(v);
+  o += sep;
+}
+
+}  // namespace
+
+extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                            char** out_text, uint64_t* out_len) {
+  if (!p || !out_text || !out_len || (!bed && bed_len)) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: NULL argument");
+  const bool wanted[2] = {out_text[0] != nullptr, out_text[1] != nullptr};
+  out_text[0] = out_text[1] = nullptr;
+  out_len[0] = out_len[1] = 0;
+  if (!wanted[0] && !wanted[1]) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: neither text is asked for");
+  if (set > 1) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: set must be SWG_IV_ALL or SWG_IV_KEPT");
+  if (axes == 0 || axes >> 2) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: axes names nothing, or a bit beyond the two");
+  if (set == SWG_IV_KEPT && !status) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: the kept rows need a status column");
+  if (swg_paf_seq_offsets(p) || swg_paf_record_offsets(p, 0))
+    return swg_alnstats_error(SWG_ERR_UNSUPPORTED,
+                              "swg_paf_lift: the file has a value >= 2^32, its columns are rebased: a lift through 64-bit columns is not supported");
+  try {
+    const uint32_t n_names = swg_paf_num_sequences(p);
+    std::unordered_map<std::string_view, uint32_t> ids;
+    ids.reserve(n_names);
+    for (uint32_t s = 0; s < n_names; ++s) ids.emplace(swg_paf_sequence_name(p, s), s);
+    std::vector<swg_lift_region> regions;
+    std::vector<BedRegion> bed_text;
+    const int parsed = parse_bed(bed, bed_len, ids, &regions, &bed_text);
+    if (parsed != SWG_OK) return parsed;
+    const swg_records* rec = swg_paf_records(p);
+    const uint64_t m = regions.size();
+    std::string text[2];
+    text[1] = "label\tsequence\tstart\tend\tall_q\tall_t\tkept_q\tkept_t\tstate\n";
+    if (m && rec->n) {
+      if (!ctx) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: NULL context");
+      std::vector<swg_lift_summary> summary(m);
+      std::vector<swg_lift_row> rows;
+      swg_lift_request req{};
+      req.set = set, req.axes = axes;
+      req.summary = summary.data();
+      if (wanted[0]) {  // a first guess at the rows; a second call when there are more
+        rows.resize(std::max<uint64_t>(4 * m, uint64_t(1) << 16));
+        req.capacity = rows.size(), req.rows = rows.data();
+      }
+      int rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
+      if (rc == SWG_OK && wanted[0] && req.n > req.capacity) {
+        rows.resize(req.n);
+        req.capacity = rows.size(), req.rows = rows.data();
+        rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
+      }
+      if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+      if (wanted[0]) {
+        for (uint64_t k = 0; k < req.n; ++k) {
+          const swg_lift_row& w = rows[k];
+          const uint32_t ax = w.flags >> 1 & 1u;
+          std::string& o = text[0];
+          o += swg_paf_sequence_name(p, w.dst_seq);
+          o += '\t';
+          append_u64(o, w.dst_start, '\t');
+          append_u64(o, w.dst_end, '\t');
+          o += bed_text[w.region].label;
+          o += '\t';
+          o += bed_text[w.region].name;
+          o += '\t';
+          append_u64(o, w.src_start, '\t');
+          append_u64(o, w.src_end, '\t');
+          o += w.flags & SWG_LIFT_MINUS ? "-\t" : "+\t";
+          o += ax ? "t\t" : "q\t";
+          append_u64(o, w.record, '\n');
+        }
+      }
+      if (wanted[1]) {
+        for (uint64_t r = 0; r < m; ++r) {
+          const swg_lift_summary& s = summary[r];
+          std::string& o = text[1];
+          o += bed_text[r].label;
+          o += '\t';
+          o += bed_text[r].name;
+          o += '\t';
+          append_u64(o, regions[r].start, '\t');
+          append_u64(o, regions[r].end, '\t');
+          append_u64(o, s.hits[0][0], '\t');
+          append_u64(o, s.hits[0][1], '\t');
+          if (status) {
+            append_u64(o, s.hits[1][0], '\t');
+            append_u64(o, s.hits[1][1], '\t');
+          } else {
+            o += "-\t-\t";
+          }
+          const bool any_all = s.hits[0][0] + (uint64_t)s.hits[0][1] > 0, any_kept = s.hits[1][0] + (uint64_t)s.hits[1][1] > 0;
+          o += regions[r].seq == UINT32_MAX ? "unknown\n" : !any_all ? "none\n" : !status ? "all\n" : any_kept ? "kept\n" : "lost\n";
+        }
+      }
+    }
+    for (int k = 0; k < 2; ++k) {
+      if (!wanted[k]) continue;
+      out_text[k] = text_copy(text[k]);
+      if (!out_text[k]) {
+        std::free(out_text[0]);
+        out_text[0] = out_text[1] = nullptr;
+        out_len[0] = out_len[1] = 0;
+        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+      }
+      out_len[k] = text[k].size();
+    }
+    return SWG_OK;
+  } catch (const std::bad_alloc&) {
+    return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+  }
+}

@@ -356,6 +356,26 @@ void write_dotplot(const std::string& image_path, const std::string& layout_path
   }
 }
 
+// --lift / --lift-summary: the rows and the summary of swg_paf_lift (BED regions projected through the mappings), both from one
+// device call when both are asked for.  "-" = standard error.
+void write_lift(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
+                const std::string& bed, uint32_t set, uint32_t axes) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_lift(ctx, paf, status, bed.data(), bed.size(), set, axes, text, len) != SWG_OK) die(3, std::string("--lift: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? rows_path : summary_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
 // --dotplot-size: N or WxH, each side in 1 .. 16384
 bool parse_dot_size(const std::string& v, uint32_t* w, uint32_t* h) {
   auto side = [](const std::string& t, uint32_t* out) {
@@ -402,6 +422,9 @@ int main(int argc, char** argv) {
   std::string dotplot_path, dotplot_layout_path, dotplot_query, dotplot_target;  // --dotplot, --dotplot-layout: empty = no file
   swg_dot_view dot_view{2048, 2048, nullptr, nullptr};
   bool dotplot_flag = false;  // (one of --dotplot-size / --dotplot-query / --dotplot-target was given)
+  std::string lift_regions_path, lift_path, lift_summary_path, lift_bed;  // --lift-regions, --lift, --lift-summary: empty = not given
+  uint32_t lift_set = SWG_IV_KEPT, lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
+  bool lift_flag = false;  // (--lift-set or --lift-axis was given)
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -486,6 +509,24 @@ int main(int argc, char** argv) {
     }
     else if (a == "--dotplot-query") { dotplot_query = value(); if (dotplot_query.empty()) die(2, "empty value for --dotplot-query"); dotplot_flag = true; }
     else if (a == "--dotplot-target") { dotplot_target = value(); if (dotplot_target.empty()) die(2, "empty value for --dotplot-target"); dotplot_flag = true; }
+    else if (a == "--lift-regions") { lift_regions_path = value(); if (lift_regions_path.empty()) die(2, "empty value for --lift-regions"); }
+    else if (a == "--lift") { lift_path = value(); if (lift_path.empty()) die(2, "empty value for --lift"); }
+    else if (a == "--lift-summary") { lift_summary_path = value(); if (lift_summary_path.empty()) die(2, "empty value for --lift-summary"); }
+    else if (a == "--lift-set") {
+      const std::string v = value();
+      if (v == "kept") lift_set = SWG_IV_KEPT;
+      else if (v == "all") lift_set = SWG_IV_ALL;
+      else die(2, "invalid value for --lift-set: kept or all");
+      lift_flag = true;
+    }
+    else if (a == "--lift-axis") {
+      const std::string v = value();
+      if (v == "query") lift_axes = SWG_LIFT_AXIS_QUERY;
+      else if (v == "target") lift_axes = SWG_LIFT_AXIS_TARGET;
+      else if (v == "both") lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
+      else die(2, "invalid value for --lift-axis: query, target or both");
+      lift_flag = true;
+    }
     else if (a == "--component-min-bases") {
       if (!parse_metric_number(value(), &component_par.min_bases)) die(2, "bad --component-min-bases");
       component_flag = true;
@@ -512,6 +553,7 @@ int main(int argc, char** argv) {
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
+                "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -554,6 +596,14 @@ int main(int argc, char** argv) {
                 "                      (- = standard error); with --dotplot, both come from one device call\n"
                 "  --dotplot-query PREFIX   only query sequences whose name starts with PREFIX go on the y axis\n"
                 "  --dotplot-target PREFIX  only target sequences whose name starts with PREFIX go on the x axis\n"
+                "  --lift-regions BED  regions (name start end [label]) to project through the mappings after the filter\n"
+                "  --lift FILE         `dst_name dst_start dst_end label src_name src_start src_end strand axis record`: where each region\n"
+                "                      lands on the other side of every mapping that covers it (linear interpolation, rounded outward;\n"
+                "                      - = standard error)\n"
+                "  --lift-summary FILE `label sequence start end all_q all_t kept_q kept_t state` per region: its hits before and after the\n"
+                "                      filter; state lost = the filter left it without a projection; with --lift, one device call\n"
+                "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
+                "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -569,6 +619,31 @@ int main(int argc, char** argv) {
   if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
     die(2, "--dotplot-size, --dotplot-query and --dotplot-target need --dotplot or --dotplot-layout");
+  const bool lift = !lift_regions_path.empty();
+  if (!lift && (!lift_path.empty() || !lift_summary_path.empty() || lift_flag))
+    die(2, "--lift, --lift-summary, --lift-set and --lift-axis need --lift-regions");
+  if (lift && lift_path.empty() && lift_summary_path.empty()) die(2, "--lift-regions needs --lift or --lift-summary");
+  if (lift) {  // read now: an unreadable BED is a usage error, found before anything is begun
+    FILE* f = std::fopen(lift_regions_path.c_str(), "rb");
+    if (!f) die(2, "cannot open " + lift_regions_path + ": " + std::strerror(errno));
+    char buf[1 << 16];
+    size_t got;
+    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) lift_bed.append(buf, got);
+    const bool failed = std::ferror(f) != 0;
+    std::fclose(f);
+    if (failed) die(2, "cannot read " + lift_regions_path);
+    // a malformed BED is a usage error too: parsed here against a handle without records, which needs no device
+    char marker = 0;
+    char* text[2] = {nullptr, &marker};
+    uint64_t len[2] = {0, 0};
+    const uint8_t none = 0;
+    swg_paf* empty = nullptr;
+    if (swg_paf_open_buffer("", 0, 1, &empty) != SWG_OK) die(3, swg_paf_last_error());
+    const int rc = swg_paf_lift(nullptr, empty, &none, lift_bed.data(), lift_bed.size(), lift_set, lift_axes, text, len);
+    swg_paf_close(empty);
+    if (rc != SWG_OK) die(2, std::string("--lift-regions: ") + swg_alnstats_last_error());
+    swg_free(text[1]);
+  }
   dot_view.query_prefix = dotplot_query.empty() ? nullptr : dotplot_query.c_str();
   dot_view.target_prefix = dotplot_target.empty() ? nullptr : dotplot_target.c_str();
   if (input.empty()) die(2, "usage: sweepga-gpu <in.paf> [--output-file out.paf] [filter flags]   (--help)");
@@ -635,7 +710,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty())
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -698,6 +773,12 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--dotplot: the file has a value >= 2^32, its columns are rebased: a dot plot of 64-bit columns is not supported");
   }
+  if (lift) {
+    if (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0)) {  // (likewise)
+      gpu_init.join();
+      die(3, "--lift: the file has a value >= 2^32, its columns are rebased: a lift through 64-bit columns is not supported");
+    }
+  }
   if (!blocks_path.empty() && !no_filter && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
@@ -759,6 +840,12 @@ int main(int argc, char** argv) {
       if (n && !dotplot_path.empty() && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_dotplot(dotplot_path, dotplot_layout_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), dot_view);
+    }
+    if (lift) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_lift(lift_path, lift_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -896,6 +983,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_dotplot(dotplot_path, dotplot_layout_path, ctx, paf, status.data(), dot_view);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --dotplot: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --lift / --lift-summary: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (lift) {
+    const auto tb = clk::now();
+    write_lift(lift_path, lift_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

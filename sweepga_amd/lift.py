@@ -1,0 +1,171 @@
+"""The lift seen from Python: caller-given regions projected through the mappings of a filter call on the device
+(csrc/swg_lift.hip).  lift_records / lift_records_device are the two record seams, Lift.from_paf BED text through an open PafFile."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import SWG_OK, SwgError, SwgLiftRequest, SwgRecords, default_context, load
+
+COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
+REGION_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32)])
+ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "record", "src_start", "src_end", "dst_seq", "dst_start", "dst_end", "flags")])
+UNKNOWN = 2**32 - 1
+SET_ALL, SET_KEPT = 0, 1
+AXIS_QUERY, AXIS_TARGET, AXIS_BOTH = 1, 2, 3
+MINUS, ON_TARGET = 1, 2
+SETS = {"all": SET_ALL, "kept": SET_KEPT}
+AXES = {"query": AXIS_QUERY, "target": AXIS_TARGET, "both": AXIS_BOTH}
+
+
+class LiftResult:
+    """rows: a ROW_DTYPE array in (region, axis, start on the axis, record) order, or None when the capacity given did not hold
+    them; n: their number; summary: an (m, 2, 2) uint32 array, hits[region][set][axis]; candidates: (query axis, target axis)."""
+
+    def __init__(self, rows, n, summary, candidates):
+        self.rows, self.n, self.summary, self.candidates = rows, n, summary, candidates
+
+
+def regions_array(regions):
+    """A REGION_DTYPE array from one, or from an iterable of (seq, start, end)."""
+    if isinstance(regions, np.ndarray) and regions.dtype == REGION_DTYPE:
+        return np.ascontiguousarray(regions)
+    out = np.zeros(len(regions), dtype=REGION_DTYPE)
+    for k, (seq, start, end) in enumerate(regions):
+        out[k] = (seq, start, end, 0)
+    return out
+
+
+def _call(ctx, fn, rec, status_addr, regions_addr, m, set_, axes, capacity):
+    """capacity None: the two-call protocol (count, then fetch); a number: one call with an array of that size."""
+    req = SwgLiftRequest()
+    req.set, req.axes = int(set_), int(axes)
+    summary = np.zeros((m, 2, 2), dtype=np.uint32)
+    req.summary = summary.ctypes.data if m else None
+    rows = None
+    if capacity is not None:
+        rows = np.zeros(int(capacity), dtype=ROW_DTYPE)
+        req.capacity, req.rows = int(capacity), rows.ctypes.data if capacity else None
+    ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(req)))
+    if capacity is None:
+        rows = np.zeros(int(req.n), dtype=ROW_DTYPE)
+        if req.n:
+            req.capacity, req.rows = int(req.n), rows.ctypes.data
+            ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(req)))
+    elif req.n > capacity:
+        rows = None
+    else:
+        rows = rows[:int(req.n)]
+    return LiftResult(rows, int(req.n), summary, (int(req.candidates[0]), int(req.candidates[1])))
+
+
+def _status(status, n):
+    if status is None:
+        return None
+    st = np.ascontiguousarray(status, dtype=np.uint8)
+    if st.size < n:
+        raise ValueError("status has fewer entries than records")
+    return st if st.size else np.zeros(1, dtype=np.uint8)
+
+
+def lift_records(ctx, records, strand, n_seq, regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_records.  `records`: a dict of numpy columns (q_id, t_id, q_start, q_end, t_start, t_end); strand: uint8 per record
+    (0 = '+'); regions: a REGION_DTYPE array or (seq, start, end) triples, seq = UNKNOWN for a name the input does not have;
+    set: "all" / "kept" (or 0 / 1), axes: "query" / "target" / "both" (or the bit mask).  Returns a LiftResult."""
+    regs = regions_array(regions)
+    rec = SwgRecords()
+    rec.n = len(records["q_id"])
+    keep = [np.ascontiguousarray(records[k], dtype=np.uint32) for k in COLUMNS] + [np.ascontiguousarray(strand, dtype=np.uint8)]
+    if any(a.size != int(rec.n) for a in keep):
+        raise ValueError("the columns and strand differ in length")
+    for k, a in zip(COLUMNS + ("strand",), keep):
+        setattr(rec, k, a.ctypes.data if a.size else None)
+    rec.n_seq = int(n_seq)
+    st = _status(status, int(rec.n))
+    return _call(ctx, ctx.lib.swg_lift_records, rec, st.ctypes.data if st is not None else None, regs.ctypes.data if regs.size else None,
+                 regs.size, SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+def lift_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end to
+    contiguous 4-byte tensors of one length, strand and status (or None) are 1-byte tensors with an entry per record, regions a
+    tensor of 16 * n_regions bytes laid out as REGION_DTYPE.  (Anything with .data_ptr(), .numel() and .element_size() works; the
+    caller keeps the tensors alive and their work finished.)  Rows and summary come back as numpy arrays on the host."""
+    rec = SwgRecords()
+    rec.n = int(columns["q_id"].numel())
+    for k in COLUMNS:
+        t = columns[k]
+        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
+            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
+        setattr(rec, k, int(t.data_ptr()))
+    for name, t in (("strand", strand), ("status", status)):
+        if t is not None and (t.element_size() != 1 or int(t.numel()) < int(rec.n)):
+            raise ValueError(f"{name} must be 1-byte with an entry per record")
+    if int(regions.numel()) * regions.element_size() < 16 * int(n_regions):
+        raise ValueError("regions holds fewer than 16 bytes per region")
+    rec.strand = int(strand.data_ptr())
+    rec.n_seq = int(n_seq)
+    return _call(ctx, ctx.lib.swg_lift_records_device, rec, int(status.data_ptr()) if status is not None else None, int(regions.data_ptr()),
+                 int(n_regions), SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+def parse_rows(text):
+    """The rows text as a ROW_DTYPE-like structured array with names: (dst_name, dst_start, dst_end, label, src_name, src_start,
+    src_end, strand, axis, record) per line."""
+    dt = np.dtype([("dst_name", object), ("dst_start", np.uint32), ("dst_end", np.uint32), ("label", object), ("src_name", object),
+                   ("src_start", np.uint32), ("src_end", np.uint32), ("strand", "U1"), ("axis", "U1"), ("record", np.uint32)])
+    lines = [ln.split("\t") for ln in text.split("\n") if ln]
+    out = np.zeros(len(lines), dtype=dt)
+    for k, f in enumerate(lines):
+        out[k] = (f[0], int(f[1]), int(f[2]), f[3], f[4], int(f[5]), int(f[6]), f[7], f[8], int(f[9]))
+    return out
+
+
+class Lift:
+    """BED regions lifted through an open PafFile: `text` (one line per row: dst_name dst_start dst_end label src_name src_start
+    src_end strand axis record) and `summary_text` (label sequence start end all_q all_t kept_q kept_t state per region); `rows` and
+    `summary` are the same parsed into structured numpy arrays.  None where not asked for."""
+
+    def __init__(self, text, summary_text):
+        self.text, self.summary_text = text, summary_text
+
+    @property
+    def rows(self):
+        return parse_rows(self.text) if self.text is not None else None
+
+    @property
+    def summary(self):
+        if self.summary_text is None:
+            return None
+        dt = np.dtype([("label", object), ("sequence", object), ("start", np.uint32), ("end", np.uint32), ("all_q", np.uint32),
+                       ("all_t", np.uint32), ("kept_q", np.int64), ("kept_t", np.int64), ("state", object)])
+        lines = [ln.split("\t") for ln in self.summary_text.split("\n")[1:] if ln]
+        out = np.zeros(len(lines), dtype=dt)
+        for k, f in enumerate(lines):
+            out[k] = (f[0], f[1], int(f[2]), int(f[3]), int(f[4]), int(f[5]), -1 if f[6] == "-" else int(f[6]), -1 if f[7] == "-" else int(f[7]), f[8])
+        return out
+
+    @classmethod
+    def from_paf(cls, paf, status, bed_text, set="kept", axes="both", ctx=None, rows=True, summary=True):
+        """swg_paf_lift: both texts from one device call.  status None: set must be "all".  ctx: a Context, anything with a `.ctx`
+        (PafFilter), or None = the default context, which is only opened when there are records and regions."""
+        ctx = getattr(ctx, "ctx", ctx)
+        lib = load()
+        bed = bed_text.encode("utf-8", errors="surrogateescape") if isinstance(bed_text, str) else bytes(bed_text)
+        rebased = bool(lib.swg_paf_seq_offsets(paf.handle)) or bool(lib.swg_paf_record_offsets(paf.handle, 0))   # (refused by the library)
+        if ctx is None and paf.n and bed.strip() and not rebased:
+            ctx = default_context()
+        st = _status(status, paf.n)
+        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
+        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
+        for k, wanted in enumerate((rows, summary)):
+            p[k] = C.addressof(marker) if wanted else None
+        rc = lib.swg_paf_lift(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None, bed, len(bed),
+                              SETS.get(set, set), AXES.get(axes, axes), p, n)
+        if rc != SWG_OK:
+            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
+        text = [None, None]
+        for k, wanted in enumerate((rows, summary)):
+            if wanted:
+                text[k] = C.string_at(p[k], n[k]).decode("utf-8", errors="surrogateescape")
+                lib.swg_free(C.c_void_p(p[k]))
+        return cls(text[0], text[1])
