@@ -234,7 +234,8 @@ int swg_merge_chains(swg_ctx* ctx, const swg_records* rec, uint64_t max_gap, uin
 int swg_union_find_sets(swg_ctx* ctx, uint64_t n, uint64_t m, const uint32_t* xs,
                         const uint32_t* ys, uint32_t* set_of, uint64_t* n_sets);
 
-/* f64::ln as the reference evaluates it (glibc log) for n host doubles, computed on the GPU. */
+/* f64::ln as the reference evaluates it (glibc log) for n host doubles, computed on the GPU: any double,
+ * glibc's branches for arguments near 1, zero, negatives, subnormals, inf and NaN included. */
 int swg_log(swg_ctx* ctx, uint64_t n, const double* x, double* y);
 /* ln(first + i * stride) for i in [0, n), compared on the device against nothing: returns the
  * values so a test can compare them with the host libm. */

@@ -4,7 +4,8 @@
 //                            (mash.rs:78-107).  h = DefaultHasher (SipHash-1-3, zero keys) over `<[u8] as Hash>`: le64(k)
 //                            then the bytes; h_fwd over the window as it is (case kept), h_rev over its reverse complement
 //                            upper-cased (mash.rs:122-131).
-//   swg_mash_distances ..... all-vs-all -1/k * ln(2J / (1 + J)) over the SETS of two sketches (mash.rs:39-73), glibc ln.
+//   swg_mash_distances ..... all-vs-all -1/k * ln(2J / (1 + J)) over the SETS of two sketches (mash.rs:39-73), glibc ln for any
+//                            double (swg_log_glibc_any: the ratio is a fraction, in glibc's near-1 branch from J = 15/17).
 //   swg_mash_random_pairs .. bit j of row i (i < j) = SipHash-1-3(le64(i) || le64(j)) <= fraction * 2^64, saturated
 //                            (knn_graph.rs:365-386).
 //
@@ -317,7 +318,7 @@ __global__ void __launch_bounds__(256) mash_dist_kernel(const uint64_t* __restri
       d = 1.0;
     } else {
       const double ratio = __dmul_rn(2.0, jac) / __dadd_rn(1.0, jac);  // no contraction: the reference's operation order
-      d = ratio <= 0.0 ? 1.0 : __dmul_rn(-1.0 / (double)k, swg_log_glibc(ratio));
+      d = ratio <= 0.0 ? 1.0 : __dmul_rn(-1.0 / (double)k, swg_log_glibc_any(ratio));  // a fraction: glibc's near-1 branch from J = 15/17
     }
   }
   dist[(uint64_t)i * n + j] = d;

@@ -108,13 +108,52 @@ def test_pack_records_keeps_wide_coordinates():
     assert not p.wide and p.cols["q_end"].dtype == np.uint32
 
 
+def _log_check_exe():
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "native", "log_check")
+    deps = [exe + ".cpp"] + [os.path.join(ROOT, "sweepga_amd", "csrc", h) for h in ("swg_log.h", "glibc_log_table.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-fopenmp", "-mfma", "-o", exe, exe + ".cpp"])
+    return exe
+
+
 def test_device_log_restatement_on_host():
     """sweepga_amd/csrc/swg_log.h (the arithmetic the kernels run) == host libm log, checked on the CPU
     for every integer length < 2^24 and a strided sample up to 2^40."""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "native", "log_check")
-    src = exe + ".cpp"
-    if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(src):
-        subprocess.check_call(["g++", "-O2", "-fopenmp", "-mfma", "-o", exe, src])
+    exe = _log_check_exe()
     assert subprocess.run([exe, "1", str(1 << 24)], capture_output=True, text=True).stdout.strip() == "0"
     assert subprocess.run([exe, str(1 << 24), str(1 << 22), "262147"], capture_output=True, text=True).stdout.strip() == "0"
+
+
+def test_device_log_any_restatement_on_host(tmp_path):
+    """swg_log_glibc_any == host libm log, bit for bit (NaN == NaN), for every kind of argument a caller can feed it:
+    all 8,002,000 Mash ratios with union <= 4000 (943,530 of them in glibc's near-1 window), 4e6 doubles inside the
+    window and its edges, 4e6 doubles over all normal binades, integers up to 2^53 and in [2^63, 2^64), and the specials.
+    swg_log_glibc, the integer-only function of the hot paths, is run over the two wide integer ranges as well.
+    Before swg_log_glibc_any existed, `log_check mash 4000` on swg_log_glibc printed 23306."""
+    import subprocess
+    from tests import log_sets as ls
+    exe = _log_check_exe()
+
+    def run(*args):
+        r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True)
+        return r.stdout.strip(), r.stderr
+
+    def run_set(name, x):
+        p = tmp_path / (name + ".f64")
+        np.ascontiguousarray(x, dtype="<f8").tofile(p)
+        out, err = run("file", p)
+        os.remove(p)
+        return out, err
+
+    out, err = run("mash", 4000)
+    assert "8002000 ratios, 943530 of them >= 0.9375" in err, err
+    assert out == "0", ("mash ratios", out, err)
+    rng = np.random.default_rng(20240607)
+    for name, x in (("window", ls.window(rng, 4_000_000)), ("edges", ls.window_edges()), ("binades", ls.binades(rng, 4_000_000)),
+                    ("integers", ls.integers(rng, 1_000_000)), ("specials", ls.specials(rng))):
+        out, err = run_set(name, x)
+        assert out == "0", (name, out, err)
+    for first, stride, n in (ls.INT_RANGE_53, ls.INT_RANGE_64):
+        assert run(first, n, stride)[0] == "0", (first, stride)

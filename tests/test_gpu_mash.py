@@ -99,6 +99,92 @@ def test_distances_bit_equal(env):
             assert np.all(np.diag(d) == 0.0)
 
 
+HIGH_J_U = (18, 36, 72, 92, 200, 1000, 5000)
+# the smallest (inter, union) whose ratio 2J / (1 + J) the integer-domain table logarithm got wrong in the last bit
+HIGH_J_WITNESSES = ((17, 18), (34, 36), (70, 71), (79, 80), (89, 92))
+
+
+def _nested(rng, U):
+    """n = min(U, 128) sketches over a sorted pool of U distinct values: sketch i = the pool's first U - i values, so the
+    pair i < j has inter = U - j and union = U - i by construction"""
+    pool = np.unique(rng.integers(0, 2**64 - 1, U + 64, dtype=np.uint64, endpoint=True))[:U]
+    assert len(pool) == U
+    return [pool[:U - i].copy() for i in range(min(U, 128))]
+
+
+def _check_nested(mash, ctx, sk, U, k):
+    n = len(sk)
+    d, inter, union = mash.distances(ctx, sk, k, counts_too=True)
+    i, j = np.triu_indices(n, 1)
+    ci, cu = U - j, U - i
+    assert np.array_equal(inter[i, j], ci) and np.array_equal(inter[j, i], ci), (U, k)
+    assert np.array_equal(union[i, j], cu) and np.array_equal(union[j, i], cu), (U, k)
+    want = np.array([mm.distance_from_counts(int(a), int(b), k) for a, b in zip(ci, cu)], dtype=np.float64)
+    for got in (d[i, j], d[j, i]):
+        bad = np.nonzero(got.view(np.uint64) != want.view(np.uint64))[0]
+        assert bad.size == 0, (U, k, bad.size, int(ci[bad[0]]), int(cu[bad[0]]), float(got[bad[0]]).hex(), float(want[bad[0]]).hex())
+    assert np.all(np.diag(d) == 0.0)
+    return ci, cu
+
+
+def test_distances_bit_equal_at_high_jaccard(env):
+    """Distance, intersection and union at J >= 15/17, where 2J / (1 + J) >= 0.9375 lies in the near-1 window of glibc's
+    log: near-identical sketches with (inter, union) known by construction, bytes for bytes against the model in both
+    triangles.  The table-only logarithm returned -0x1.daee8ab72e7e5p-6 for ln(34/35), the ratio of (17, 18); libm and
+    the model give ...e4p-6."""
+    import math
+    mash, ctx = env
+    rng = np.random.default_rng(29)
+    seen = set()
+    for U in HIGH_J_U:
+        sk = _nested(rng, U)
+        for k in (15, 21):
+            ci, cu = _check_nested(mash, ctx, sk, U, k)
+        j = ci / cu
+        ratio = (2.0 * j) / (1.0 + j)
+        seen.update((U, int(a), int(b)) for a, b in zip(ci[ratio >= 0.9375], cu[ratio >= 0.9375]))
+    # not vacuous: enough pairs in the window, the known witnesses among them, and the model on libm's side of one
+    assert len(seen) >= 10_000, len(seen)
+    in_window = {(a, b) for _, a, b in seen}
+    assert all(w in in_window for w in HIGH_J_WITNESSES), [w for w in HIGH_J_WITNESSES if w not in in_window]
+    j = 17 / 18
+    assert math.log((2.0 * j) / (1.0 + j)) != float.fromhex("-0x1.daee8ab72e7e5p-6")
+    assert mm.distance_from_counts(17, 18, 15) == (-1.0 / 15) * float.fromhex("-0x1.daee8ab72e7e4p-6")
+    print(f"high-J pairs in the window: {len(seen)} per k")
+
+
+def test_distances_high_jaccard_with_repeats(env):
+    """the nested sketches with every value repeated 1 to 3 times: sets are what counts, so the same counts and distances"""
+    mash, ctx = env
+    rng = np.random.default_rng(31)
+    for U in (92, 1000):
+        sk = [np.repeat(v, rng.integers(1, 4, len(v))) for v in _nested(rng, U)]
+        assert all(len(v) > len(np.unique(v)) for v in sk[:-1]) and all(np.all(v[1:] >= v[:-1]) for v in sk)
+        _check_nested(mash, ctx, sk, U, 15)
+
+
+def test_distances_high_jaccard_unstaged(env):
+    """second sketch longer than the kernel's LDS staging buffer (4096 values): two sketches of 40,000 values that share all
+    but 100 (J = 39900 / 40100), and a short one before them so that a short first sketch meets a long second one"""
+    mash, ctx = env
+    rng = np.random.default_rng(37)
+    pool = np.unique(rng.integers(0, 2**64 - 1, 40_300, dtype=np.uint64, endpoint=True))[:40_100]
+    assert len(pool) == 40_100
+    drop = rng.permutation(40_100)[:200]
+    a = np.delete(pool, drop[:100])
+    b = np.delete(pool, drop[100:])
+    sk = [a[:3000].copy(), a, b]
+    assert len(a) == len(b) == 40_000 and mm.jaccard_counts(a, b) == (39_900, 40_100)
+    for k in (15, 21):
+        d, inter, union = mash.distances(ctx, sk, k, counts_too=True)
+        for i in range(3):
+            for j in range(i + 1, 3):
+                ci, cu = mm.jaccard_counts(sk[i], sk[j])
+                want = mm.distance_from_counts(ci, cu, k)
+                assert d[i, j].tobytes() == np.float64(want).tobytes() == d[j, i].tobytes(), (i, j, float(d[i, j]).hex(), want.hex())
+                assert (int(inter[i, j]), int(union[i, j]), int(inter[j, i]), int(union[j, i])) == (ci, cu, ci, cu)
+
+
 def test_random_pairs_mask_at_2_16(env):
     mash, ctx = env
     n = 1 << 16
@@ -165,6 +251,34 @@ def test_joblist_equals_restatement(env, tmp_path, strategy):
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
         assert r.stdout == mm.joblist([str(a), str(b)], strategy, 15, 1000, t, ll, str(tmp_path / "o"), reader=_model_reader)
+
+
+@pytest.mark.parametrize("strategy", ["knn:3", "tree:2:1:0.2", "giant:0.9"])
+def test_joblist_near_identical_haplotypes(env, tmp_path, strategy):
+    """The high-J route end to end: 12 haplotypes mutated at 0.1 %, so that at least half of the haplotype pairs have
+    J >= 0.8824 and their distances come from the near-1 branch of the logarithm; the Python API and the command line
+    against the model, text byte for byte.  A last-bit error in a distance rarely moves a selection, so this case is
+    expected to pass with the table-only logarithm as well: test_distances_bit_equal_at_high_jaccard is the one that
+    catches that.  This one is here so that sketches, merge, distances and selection are run together at such J."""
+    mash, ctx = env
+    recs = _haplotypes(np.random.default_rng(17), 12, mut=0.001)
+    groups = {}
+    for name, seq in recs:
+        groups.setdefault(mm.pansn_key(name), []).append(mm.sketch(seq, 15, 1000))
+    hs = [mm.merge(groups[h], 1000) for h in sorted(groups)]
+    jac = [np.divide(*mm.jaccard_counts(hs[i], hs[j])) for i in range(len(hs)) for j in range(i + 1, len(hs))]
+    assert len(jac) == 66 and sum(x >= 0.8824 for x in jac) >= 33, sorted(jac)
+    a, b = tmp_path / "a.fa.gz", tmp_path / "b.fa"
+    _write_fa(a, recs[:10], gz=True)
+    _write_fa(b, recs[10:])
+    paths = [str(a), str(b)]
+    want = mm.joblist(paths, strategy, 15, 1000, 8, 0, str(tmp_path / "o"), reader=_model_reader)
+    assert want and mash.joblist(ctx, paths, strategy, 15, 1000, 8, 0, str(tmp_path / "o")) == want
+    cli = os.path.join(ROOT, "sweepga_amd", "bin", "sweepga-gpu")
+    r = subprocess.run([cli, "--joblist", str(a), str(b), "--sparsify", strategy, "--joblist-output-dir", str(tmp_path / "o")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout == want
 
 
 @pytest.mark.parametrize("n_hap", [10, 11, 50, 51])

@@ -29,17 +29,39 @@ def sw():
 
 
 def test_device_log_equals_host_libm(sw):
-    """Device ln == glibc log bit for bit: all lengths < 2^22, then strided samples up to 2^40."""
+    """Device ln == glibc log bit for bit.  swg_log_range (swg_log_glibc, integers): all lengths < 2^22, then strided
+    samples up to 2^40, one that ends just under 2^53 and one over [2^63, 2^64).  swg_log (swg_log_glibc_any, any double):
+    every Mash ratio with union <= 1500, 2^20 doubles in glibc's near-1 window and its edges, 2^20 doubles over all
+    normal binades, and the specials (two NaNs are equal whatever their payload)."""
     import ctypes as C
+    from tests import log_sets as ls
     ctx = sw.default_context(0)
-    for first, stride, n in ((1, 1, 1 << 22), (1 << 22, 977, 1 << 22), (1 << 32, 1_000_003, 1 << 20)):
+
+    def host_log(x):
+        host = np.zeros(len(x), dtype=np.float64)
+        orc.lib().orc_log_array(C.c_uint64(len(x)), x.ctypes.data_as(C.c_void_p), host.ctypes.data_as(C.c_void_p))
+        return host
+
+    for first, stride, n in ((1, 1, 1 << 22), (1 << 22, 977, 1 << 22), (1 << 32, 1_000_003, 1 << 20), ls.INT_RANGE_53, ls.INT_RANGE_64):
         dev = np.zeros(n, dtype=np.float64)
         ctx.check(ctx.lib.swg_log_range(ctx.handle, first, stride, n, dev.ctypes.data_as(C.c_void_p)))
-        x = (first + stride * np.arange(n, dtype=np.uint64)).astype(np.float64)
-        host = np.zeros(n, dtype=np.float64)
-        orc.lib().orc_log_array(C.c_uint64(n), x.ctypes.data_as(C.c_void_p), host.ctypes.data_as(C.c_void_p))
+        x = (np.uint64(first) + np.uint64(stride) * np.arange(n, dtype=np.uint64)).astype(np.float64)
+        host = host_log(x)
         bad = np.nonzero(dev.view(np.uint64) != host.view(np.uint64))[0]
         assert bad.size == 0, f"{bad.size} log mismatches, first at x={x[bad[0]]}"
+
+    rng = np.random.default_rng(20240607)
+    inter, un = ls.mash_counts(1500)
+    ratios = ls.mash_ratio(inter, un)
+    assert len(ratios) == 1500 * 1501 // 2 and int((ratios >= 0.9375).sum()) > 100_000
+    for name, x in (("mash ratios", ratios), ("window", np.concatenate([ls.window(rng, 1 << 20), ls.window_edges()])),
+                    ("binades", ls.binades(rng, 1 << 20)), ("specials", ls.specials(rng))):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        dev = np.full(len(x), 12345.0)
+        ctx.check(ctx.lib.swg_log(ctx.handle, len(x), x.ctypes.data_as(C.c_void_p), dev.ctypes.data_as(C.c_void_p)))
+        host = host_log(x)
+        bad = np.nonzero((dev.view(np.uint64) != host.view(np.uint64)) & ~(np.isnan(dev) & np.isnan(host)))[0]
+        assert bad.size == 0, f"{name}: {bad.size} log mismatches, first at x={x[bad[0]].hex()}: {dev[bad[0]].hex()} != {host[bad[0]].hex()}"
 
 
 KAT = [
