@@ -977,6 +977,72 @@ int swg_lift_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t*
 int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
                  char** out_text, uint64_t* out_len);
 
+/* ---- transitive lift: the closure of each region under the lift, hop by hop, on the device -----------------
+ * Per region, independently of every other region (all sets are point sets per sequence, all arithmetic is in integers):
+ *   hop 0      F_0 = V_0 = { [start, end) on seq } when seq is known and start < end, else both empty
+ *   hop h >= 1 a piece (s, [x, y)) of F_{h-1} is WALKED when h == 1 or y - x >= min_len (the region itself always is).  A walked
+ *              piece is lifted as the region (s, x, y) of the lift above: for every wanted axis and every record of the set that
+ *              is a hit, dst by the outward-rounded rule, empty dst (D == 0) dropped.  P_h = the union of these intervals;
+ *              F_h = the maximal intervals of P_h \ V_{h-1} (touching intervals are one, a gap of one base separates);
+ *              V_h = V_{h-1} u P_h.  The walk stops after hop max_hops, or when no region has a piece left to walk from.
+ * Rows: one per piece of every F_h, hop 0 included, ordered by (region, seq, start); the pieces of a region are disjoint; adjacent
+ * pieces of different hops stay separate rows.  No strand is carried: a merged piece can come from both orientations.  Nothing
+ * depends on the order of the records.  summary[r]: bases = the sum of the rows' lengths, pieces = the rows, sequences = the
+ * distinct seq among them, hops = the largest hop of a row, flags bit 0 (SWG_CLOSURE_CUT) = a row of hop max_hops has length >=
+ * max(min_len, 1): max_hops ended the walk, not the data.  An unknown or empty region has all fields 0.  min_len == 0 behaves as 1.
+ * Out: n = rows; hops_run = the hops h >= 1 whose frontier F_{h-1} was not empty for every region (<= max_hops); projections =
+ * the dst intervals made, summed over the hops (before the union); candidates[axis] as in the lift, summed over the hops.
+ * Capacity protocol of the lift.  m == 0 gives n = 0.  A record set of n == 0 records still has the hop-0 rows of its known,
+ * non-empty regions (pieces = 1, hops = 0): they are made on the host, without a kernel (the device seam copies the regions back).
+ * Errors as in the lift (reserved != 0 of the request included), plus max_hops == 0 or > 65,535: SWG_ERR_INVALID; 2^30 intervals
+ * or more in one hop's union: SWG_ERR_RANGE.  Scratch comes from the context's arena, SWG_ERR_OOM when the memory limit does not
+ * hold it: per wanted axis the index of the lift, 24 bytes per record, built ONCE and joined by every hop; 45 bytes per region;
+ * per hop 12 bytes per frontier slot and wanted axis and 32 per interval of the union (P_h + |V_{h-1}|: the slots of the new
+ * frontier and of the new visited set) -- these stay until the call ends -- and, given back after the hop, 16 per projection and
+ * 124 per interval of the union (two events of 16 bytes, and per event 24 of sort buffers, 8 of depth, 4 of position, 2 flags
+ * and 8 of edge lists); at the end 64 bytes per row, 24 more when the rows are fetched.  swg_lift_closure_records stages its
+ * host columns there too: 26 more bytes per record, 16 per region. */
+typedef struct swg_closure_row {
+  uint32_t region, seq;
+  uint32_t start, end;
+  uint32_t hop;
+  uint32_t reserved; /* 0 */
+} swg_closure_row; /* 24 bytes */
+typedef struct swg_closure_summary {
+  uint64_t bases;
+  uint32_t pieces, sequences, hops, flags;
+} swg_closure_summary; /* 24 bytes */
+#define SWG_CLOSURE_CUT 1u
+typedef struct swg_closure_request {
+  uint32_t set;                 /* SWG_IV_ALL (0) or SWG_IV_KEPT (1) */
+  uint32_t axes;                /* bit 0 query, bit 1 target; at least one */
+  uint32_t max_hops;            /* 1 .. 65,535 */
+  uint32_t min_len;             /* a piece shorter than this is reported and not walked on */
+  uint64_t capacity;            /* in: entries `rows` can hold */
+  swg_closure_row* rows;        /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+  swg_closure_summary* summary; /* in: caller-owned [m] or NULL; written whenever non-NULL */
+  uint64_t n;                   /* out: rows */
+  uint64_t projections;         /* out */
+  uint64_t candidates[2];       /* out */
+  uint32_t hops_run;            /* out */
+  uint32_t reserved;            /* 0 */
+} swg_closure_request; /* 80 bytes */
+/* rec: host pointers; status[n] (NULL: SWG_IV_ALL only) and regions[m] on the host. */
+int swg_lift_closure_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                             swg_closure_request* req);
+/* The same with the six columns and strand of rec, status and regions in device memory of ctx's GPU. */
+int swg_lift_closure_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                                    swg_closure_request* req);
+/* BED regions walked through an open PAF: the BED parser, the marking protocol and the refusals of swg_paf_lift.  Texts:
+ *   rows     one line per row in row order: name start end label hop   (BED-like: the piece first; no strand, see above)
+ *   summary  header `label sequence start end pieces sequences genomes bases hops state`, then one line per region in input order;
+ *            genomes = the distinct genome prefixes (up to the last '#') of the rows' sequences; state: `unknown` for an unknown
+ *            name, `none` when nothing lies beyond hop 0 (an empty region included), `cut` when SWG_CLOSURE_CUT is set, else `closed`.
+ * Empty BED text gives the header-only summary and empty rows.  A PAF without records knows no name: every region is `unknown`
+ * and there are no rows.  Neither needs a device (ctx may be NULL then). */
+int swg_paf_lift_closure(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                         uint32_t max_hops, uint32_t min_len, char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

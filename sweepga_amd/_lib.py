@@ -41,7 +41,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_intervals_records", "swg_intervals_records_device", "swg_paf_intervals", "swg_paf_interval_texts",
            "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing",
            "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot",
-           "swg_lift_records", "swg_lift_records_device", "swg_paf_lift"]
+           "swg_lift_records", "swg_lift_records_device", "swg_paf_lift",
+           "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure"]
 
 
 class SwgError(RuntimeError):
@@ -227,6 +228,20 @@ class SwgLiftSummary(C.Structure):
 class SwgLiftRequest(C.Structure):
     _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
                 ("rows", C.c_void_p), ("summary", C.c_void_p)]
+
+
+class SwgClosureRow(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")]
+
+
+class SwgClosureSummary(C.Structure):
+    _fields_ = [("bases", C.c_uint64)] + [(k, C.c_uint32) for k in ("pieces", "sequences", "hops", "flags")]
+
+
+class SwgClosureRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("max_hops", C.c_uint32), ("min_len", C.c_uint32), ("capacity", C.c_uint64),
+                ("rows", C.c_void_p), ("summary", C.c_void_p), ("n", C.c_uint64), ("projections", C.c_uint64), ("candidates", C.c_uint64 * 2),
+                ("hops_run", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 def load():
@@ -446,6 +461,13 @@ def load():
     lib.swg_paf_lift.restype = C.c_int
     lib.swg_paf_lift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_uint64)]
+    for name in ("swg_lift_closure_records", "swg_lift_closure_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SwgClosureRequest)]
+    lib.swg_paf_lift_closure.restype = C.c_int
+    lib.swg_paf_lift_closure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_paf_interval_texts.restype = C.c_int
     lib.swg_paf_interval_texts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.swg_alnstats_last_error.restype = C.c_char_p

@@ -77,6 +77,12 @@ int swg_paf_seq_last_lengths(const swg_paf* p, std::vector<uint32_t>* seq_len);
 // columns of rec, status and regions on the host (on_device = false: staged in the arena) or on the device; req on the host
 int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                  swg_lift_request* req);
+// the same for the transitive lift (swg_lift_closure.hip)
+int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                         swg_closure_request* req);
+// hop 0 on the host (lift_text.cpp), all there is without records: validates the regions (returns the lift's bad-input bits, 0 = fine),
+// fills req->n and the summaries, and the rows when they fit
+uint32_t swg_closure_hop0_host(const swg_lift_region* regions, uint64_t m, uint32_t n_seq, swg_closure_request* req);
 
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53

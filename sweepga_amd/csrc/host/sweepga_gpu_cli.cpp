@@ -376,6 +376,27 @@ void write_lift(const std::string& rows_path, const std::string& summary_path, s
   }
 }
 
+// --lift-closure / --lift-closure-summary: the two texts of swg_paf_lift_closure (the regions walked through the mappings for up to
+// `hops` hops), both from one walk.  "-" = standard error.
+void write_lift_closure(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
+                        const std::string& bed, uint32_t set, uint32_t axes, uint32_t hops, uint32_t min_len) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_lift_closure(ctx, paf, status, bed.data(), bed.size(), set, axes, hops, min_len, text, len) != SWG_OK)
+    die(3, std::string("--lift-hops: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? rows_path : summary_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
 // --dotplot-size: N or WxH, each side in 1 .. 16384
 bool parse_dot_size(const std::string& v, uint32_t* w, uint32_t* h) {
   auto side = [](const std::string& t, uint32_t* out) {
@@ -425,6 +446,9 @@ int main(int argc, char** argv) {
   std::string lift_regions_path, lift_path, lift_summary_path, lift_bed;  // --lift-regions, --lift, --lift-summary: empty = not given
   uint32_t lift_set = SWG_IV_KEPT, lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
   bool lift_flag = false;  // (--lift-set or --lift-axis was given)
+  std::string closure_path, closure_summary_path;  // --lift-closure, --lift-closure-summary: empty = not given
+  uint64_t lift_hops = 0, lift_min_length = 100;   // --lift-hops (0 = not given), --lift-min-length
+  bool lift_min_length_flag = false;
   uint64_t mash_k = 15, mash_s = 1000;  // mash.rs:11-15
   unsigned long tree_near = 0, tree_far = 0;
   double tree_rand = 0.0;
@@ -512,6 +536,13 @@ int main(int argc, char** argv) {
     else if (a == "--lift-regions") { lift_regions_path = value(); if (lift_regions_path.empty()) die(2, "empty value for --lift-regions"); }
     else if (a == "--lift") { lift_path = value(); if (lift_path.empty()) die(2, "empty value for --lift"); }
     else if (a == "--lift-summary") { lift_summary_path = value(); if (lift_summary_path.empty()) die(2, "empty value for --lift-summary"); }
+    else if (a == "--lift-hops") { if (!parse_u64(value(), &lift_hops) || lift_hops < 1 || lift_hops > 65535) die(2, "invalid value for --lift-hops: 1 .. 65535"); }
+    else if (a == "--lift-closure") { closure_path = value(); if (closure_path.empty()) die(2, "empty value for --lift-closure"); }
+    else if (a == "--lift-closure-summary") { closure_summary_path = value(); if (closure_summary_path.empty()) die(2, "empty value for --lift-closure-summary"); }
+    else if (a == "--lift-min-length") {
+      if (!parse_u64(value(), &lift_min_length) || lift_min_length > UINT32_MAX) die(2, "invalid value for --lift-min-length: 0 .. 2^32 - 1");
+      lift_min_length_flag = true;
+    }
     else if (a == "--lift-set") {
       const std::string v = value();
       if (v == "kept") lift_set = SWG_IV_KEPT;
@@ -554,6 +585,7 @@ int main(int argc, char** argv) {
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
+                "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
                 "  --stats REPORT      after the filter, before the output is written: what `alnstats <in.paf> <out.paf>` would print,\n"
@@ -604,6 +636,14 @@ int main(int argc, char** argv) {
                 "                      filter; state lost = the filter left it without a projection; with --lift, one device call\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
+                "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
+                "                      what a region reaches through a third genome when no mapping joins the two directly\n"
+                "  --lift-closure FILE `name start end label hop`: the disjoint pieces each region reaches, with the hop that found them\n"
+                "                      (hop 0 = the region itself; no strand: a merged piece can come from both orientations)\n"
+                "  --lift-closure-summary FILE  `label sequence start end pieces sequences genomes bases hops state` per region; state\n"
+                "                      none = nothing beyond the region, closed = the walk ended by itself, cut = N ended it\n"
+                "  --lift-min-length N a piece shorter than N bases is reported but not walked on (default 100): the projection is\n"
+                "                      rounded outward, so the walk back through the same mapping reaches a few bases beyond the region\n"
                 "Filter path of pangenome/sweepga on an MI355X (libsweepga_gpu.so).  No CPU fallback.");
       return 0;
     } else if (a.rfind("-", 0) == 0 && a != "-") die(2, "unknown flag " + a);
@@ -622,7 +662,12 @@ int main(int argc, char** argv) {
   const bool lift = !lift_regions_path.empty();
   if (!lift && (!lift_path.empty() || !lift_summary_path.empty() || lift_flag))
     die(2, "--lift, --lift-summary, --lift-set and --lift-axis need --lift-regions");
-  if (lift && lift_path.empty() && lift_summary_path.empty()) die(2, "--lift-regions needs --lift or --lift-summary");
+  if (!lift_hops && (!closure_path.empty() || !closure_summary_path.empty() || lift_min_length_flag))
+    die(2, "--lift-closure, --lift-closure-summary and --lift-min-length need --lift-hops");
+  if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
+  if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
+  if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
+  const bool lift_once = lift && (!lift_path.empty() || !lift_summary_path.empty());  // the one-hop reports are asked for
   if (lift) {  // read now: an unreadable BED is a usage error, found before anything is begun
     FILE* f = std::fopen(lift_regions_path.c_str(), "rb");
     if (!f) die(2, "cannot open " + lift_regions_path + ": " + std::strerror(errno));
@@ -845,7 +890,10 @@ int main(int argc, char** argv) {
       std::fflush(out);
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
-      write_lift(lift_path, lift_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes);
+      if (lift_once) write_lift(lift_path, lift_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes);
+      if (lift_hops)
+        write_lift_closure(closure_path, closure_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes,
+                           (uint32_t)lift_hops, (uint32_t)lift_min_length);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -987,8 +1035,14 @@ int main(int argc, char** argv) {
   // ---- --lift / --lift-summary: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
   if (lift) {
     const auto tb = clk::now();
-    write_lift(lift_path, lift_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes);
-    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+    if (lift_once) write_lift(lift_path, lift_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes);
+    if (lift_once && !quiet) std::fprintf(stderr, "[sweepga-gpu] --lift: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+    if (lift_hops) {  // --lift-hops: the transitive lift through the same set and axes
+      const auto tc = clk::now();
+      write_lift_closure(closure_path, closure_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes, (uint32_t)lift_hops,
+                         (uint32_t)lift_min_length);
+      if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift-hops: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tc).count());
+    }
   }
   const auto t2s = clk::now();
 

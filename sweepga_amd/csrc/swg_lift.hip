@@ -27,29 +27,25 @@
 //                   rank + the other axis' share: the rows come out in (region, axis, s0, record) order without a sort.
 //
 // No work-group waits for another inside a launch; every carry goes through the library's scans between launches.
+//
+// The index (lift_limits, lift_keys, the sort, lift_gather, the prefix maximum) is built by swg_lift_limits / swg_lift_index_build,
+// which swg_lift_index.h declares with the device side of a join (lift_candidates, lift_tile_heads): the transitive lift
+// (swg_lift_closure.hip) builds it once and joins every hop's frontier against it.
 #include <algorithm>
 #include <cstring>
 #include <new>
 
 #include "swg_internal.h"
+#include "swg_lift_index.h"
 #include "swg_pair_table.h"
 #include "host/host_internal.h"
 
 namespace {
 
 using namespace swg_pair_table;
-// device scalars: bad input (bit 0: a record id out of range, bit 1: a region with reserved != 0, bit 2: a region with start > end,
-// bit 3: a region's seq neither < n_seq nor UINT32_MAX), the largest start per axis, the rows per axis
-enum { D_BAD = 0, D_MAX_START = 1, D_ROWS = 3, D_TOTAL = 5 };
-constexpr int T = 1024;            // candidates per tile
-constexpr int ITEMS = T / TB;      // per thread
-constexpr uint32_t KEPT_BIT = 0x80000000u;
-constexpr uint32_t UNKNOWN_SEQ = 0xffffffffu;
-
-struct LiftCols {
-  const uint32_t *id[2], *start[2], *end[2];  // [axis]: 0 = query, 1 = target
-  const uint8_t *strand, *status;
-};
+using namespace swg_lift_ix;
+// device scalars after lift_limits' (swg_lift_index.h): the rows per axis
+enum { D_ROWS = 3, D_TOTAL = 5 };
 
 __global__ __launch_bounds__(TB) void lift_limits_kernel(uint64_t n, uint32_t n_seq, LiftCols c, unsigned long long* __restrict__ scalars) {
   __shared__ unsigned long long l_max[2][WAVES];
@@ -103,17 +99,6 @@ __global__ __launch_bounds__(TB) void lift_gather_kernel(uint64_t n, uint32_t n_
   M[p] = (seq << 32) | e;
 }
 
-// the first position of a[0 .. n) whose value is >= v (n when none)
-__device__ __forceinline__ uint64_t lower_bound64(const uint64_t* __restrict__ a, uint64_t n, uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(TB) void lift_ranges_kernel(uint64_t m, const swg_lift_region* __restrict__ regions, uint64_t n, uint32_t n_seq,
                                                          const uint64_t* __restrict__ keys, const uint64_t* __restrict__ M, int pb, uint64_t max_start,
                                                          uint64_t* __restrict__ w, uint32_t* __restrict__ first, unsigned long long* __restrict__ scalars) {
@@ -129,14 +114,7 @@ __global__ __launch_bounds__(TB) void lift_ranges_kernel(uint64_t m, const swg_l
   if (bad) {
     atomicOr(&scalars[D_BAD], bad);
   } else if (g.seq != UNKNOWN_SEQ && g.start < g.end) {
-    const uint64_t base = (uint64_t)g.seq << pb;
-    const uint64_t lo = lower_bound64(keys, n, base);
-    const uint64_t b = g.end < max_start + 1 ? g.end : max_start + 1;  // (base + max_start + 1 may be the next sequence's first key: right)
-    const uint64_t hi = lo + lower_bound64(keys + lo, n - lo, base + b);
-    // inside [lo, hi) the high half of M is seq: M > seq << 32 | a  <=>  the prefix maximum of the ends exceeds a
-    const uint64_t at = lo + lower_bound64(M + lo, hi - lo, (((uint64_t)g.seq << 32) | g.start) + 1);
-    width = hi - at;
-    p0 = (uint32_t)at;
+    width = lift_candidates(n, keys, M, pb, max_start, g.seq, g.start, g.end, &p0);
   }
   w[r] = width;
   first[r] = p0;
@@ -156,9 +134,6 @@ struct LiftJoin {
   swg_lift_row* rows;
   uint64_t n_rows;
 };
-
-// the first region whose scanned offset exceeds v: the region that candidate v of the stream belongs to
-__device__ __forceinline__ uint64_t region_of(const uint64_t* __restrict__ W, uint64_t m, uint64_t v) { return lower_bound64(W, m, v + 1); }
 
 __device__ __forceinline__ void lift_row(const LiftJoin& J, uint32_t r, uint32_t v, uint32_t s1, uint64_t at) {
   const uint32_t rec = v & ~KEPT_BIT, ax = J.axis;
@@ -187,54 +162,9 @@ __device__ __forceinline__ void lift_tiles(const LiftJoin& J) {
   for (uint64_t t = blockIdx.x; t < J.ntiles; t += gridDim.x) {
     const uint64_t g0 = t * T;
     const uint32_t cnt = (uint32_t)(J.C - g0 < T ? J.C - g0 : T);
-    if (threadIdx.x == 0) l_span[0] = region_of(J.W, J.m, g0);
-    if (threadIdx.x == 64) l_span[1] = region_of(J.W, J.m, g0 + cnt - 1);
-    for (int s = threadIdx.x; s < T; s += TB) {
-      l_hs[s] = 0;
-      if (!WRITE) l_cnt[0][s] = l_cnt[1][s] = 0;
-    }
-    __syncthreads();
-    const uint64_t rf = l_span[0], rl = l_span[1];  // (rf <= rl < m: both candidates exist)
-    if (threadIdx.x == 0) {
-      const uint64_t before = rf ? J.W[rf - 1] : 0;
-      l_hreg[0] = (uint32_t)rf;
-      l_ha[0] = J.regions[rf].start;
-      l_hbase[0] = J.first[rf] + (uint32_t)(g0 - before);
-    }
-    for (uint64_t r = rf + 1 + threadIdx.x; r <= rl; r += TB) {  // regions that begin inside the tile; those without candidates fall through
-      const uint64_t before = J.W[r - 1];
-      if (J.W[r] == before) continue;
-      const uint32_t s = (uint32_t)(before - g0);
-      if (s >= (uint32_t)T) continue;  // (never)
-      l_hs[s] = s;
-      l_hreg[s] = (uint32_t)r;
-      l_ha[s] = J.regions[r].start;
-      l_hbase[s] = J.first[r] - s;
-    }
-    __syncthreads();
-    {  // running maximum of the head slots: blocked, ITEMS slots per thread
-      uint32_t h[ITEMS], run = 0;
-#pragma unroll
-      for (int j = 0; j < ITEMS; ++j) {
-        h[j] = l_hs[threadIdx.x * ITEMS + j];
-        run = h[j] > run ? h[j] : run;
-        h[j] = run;
-      }
-      uint32_t inc = run;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d && o > inc) inc = o;
-      }
-      if (lane == 63) l_wave[0][wave] = inc;
-      __syncthreads();
-      uint32_t carry = __shfl_up(inc, 1);
-      if (lane == 0) carry = 0;
-      for (int w = 0; w < wave; ++w) carry = l_wave[0][w] > carry ? l_wave[0][w] : carry;
-#pragma unroll
-      for (int j = 0; j < ITEMS; ++j) l_hs[threadIdx.x * ITEMS + j] = h[j] > carry ? h[j] : carry;
-    }
-    __syncthreads();
+    if (!WRITE)
+      for (int s = threadIdx.x; s < T; s += TB) l_cnt[0][s] = l_cnt[1][s] = 0;
+    lift_tile_heads(J.W, J.m, J.first, J.regions, g0, cnt, l_hs, l_hreg, l_ha, l_hbase, l_wave[0], l_span);
     // the candidates: striped, slot = j * TB + thread
     uint32_t hs[ITEMS], v[ITEMS], e[ITEMS];
     uint64_t votes[ITEMS];
@@ -318,9 +248,10 @@ __global__ void lift_totals_kernel(const uint64_t* __restrict__ tile0, uint64_t 
   if (threadIdx.x == 1) scalars[D_ROWS + 1] = ntiles1 ? tile1[ntiles1 - 1] : 0;
 }
 
-struct AxisIndex {
-  uint64_t *keys = nullptr, *M = nullptr, *W = nullptr, *tile = nullptr;
-  uint32_t *V = nullptr, *E = nullptr, *first = nullptr;
+// one axis of a lift call: the index, and the candidate stream of the call's regions over it
+struct AxisIndex : LiftIndex {
+  uint64_t *W = nullptr, *tile = nullptr;
+  uint32_t* first = nullptr;
   uint64_t C = 0, ntiles = 0;
 };
 
@@ -341,35 +272,20 @@ int lift_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, con
   SWG_CHECK_ARENA(ctx);
   SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
   SWG_HIP(ctx, hipMemsetAsync(summary, 0, m * 4 * sizeof(uint32_t), st));
-  SWG_LAUNCH(ctx, "lift_limits", lift_limits_kernel<<<grid_for(ctx, n), TB, 0, st>>>(n, n_seq, c, scalars));
-  SWG_KERNEL_CHECK(ctx);
+  SWG_TRY(swg_lift_limits(ctx, n, n_seq, c, scalars));
   uint64_t h[D_TOTAL];
   SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, D_ROWS));
   SWG_TRY(bad_input(ctx, h[D_BAD]));
-  const unsigned grid_n = (unsigned)((n + TB - 1) / TB), grid_m = (unsigned)((m + TB - 1) / TB);
+  const unsigned grid_m = (unsigned)((m + TB - 1) / TB);
   AxisIndex ix[2];
   for (uint32_t ax = 0; ax < 2; ++ax) {
     if (!(axes >> ax & 1u)) continue;
     AxisIndex& x = ix[ax];
-    const uint64_t max_start = h[D_MAX_START + ax];
-    const int pb = swg_bits_for(max_start);
-    x.keys = swg_alloc<uint64_t>(ctx, n);
-    x.M = swg_alloc<uint64_t>(ctx, n);
-    x.V = swg_alloc<uint32_t>(ctx, n);
-    x.E = swg_alloc<uint32_t>(ctx, n);
+    SWG_TRY(swg_lift_index_build(ctx, n, n_seq, c, ax, h[D_MAX_START + ax], &x));
     x.W = swg_alloc<uint64_t>(ctx, m);
     x.first = swg_alloc<uint32_t>(ctx, m);
     SWG_CHECK_ARENA(ctx);
-    SWG_LAUNCH(ctx, "lift_keys", lift_keys_kernel<<<grid_n, TB, 0, st>>>(n, n_seq, c.id[ax], c.start[ax], c.end[ax], c.status, pb, x.keys, x.V));
-    SWG_KERNEL_CHECK(ctx);
-    {
-      swg_prof_scope sort_scope(ctx, "lift_sort");
-      SWG_TRY(swg_radix_sort_pairs(ctx, &x.keys, &x.V, &x.M, &x.E, n, 0, pb + swg_bits_for(n_seq)));  // (the spare pair: M and E)
-    }
-    SWG_LAUNCH(ctx, "lift_gather", lift_gather_kernel<<<grid_n, TB, 0, st>>>(n, n_seq, x.keys, x.V, c.end[ax], pb, x.E, x.M));
-    SWG_KERNEL_CHECK(ctx);
-    SWG_TRY(swg_inclusive_max_scan_u64(ctx, x.M, x.M, n));
-    SWG_LAUNCH(ctx, "lift_ranges", lift_ranges_kernel<<<grid_m, TB, 0, st>>>(m, regions, n, n_seq, x.keys, x.M, pb, max_start, x.W, x.first, scalars));
+    SWG_LAUNCH(ctx, "lift_ranges", lift_ranges_kernel<<<grid_m, TB, 0, st>>>(m, regions, n, n_seq, x.keys, x.M, x.pb, x.max_start, x.W, x.first, scalars));
     SWG_KERNEL_CHECK(ctx);
     SWG_TRY(swg_inclusive_sum_scan_u64(ctx, x.W, x.W, m));
     SWG_TRY(swg_read_scalars(ctx, x.W + (m - 1), &x.C, 1));  // sizes the join's grid
@@ -437,6 +353,35 @@ int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
 }
 
 }  // namespace
+
+int swg_lift_ix::swg_lift_limits(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, unsigned long long* scalars) {
+  SWG_LAUNCH(ctx, "lift_limits", lift_limits_kernel<<<grid_for(ctx, n), TB, 0, ctx->stream>>>(n, n_seq, c, scalars));
+  SWG_KERNEL_CHECK(ctx);
+  return SWG_OK;
+}
+
+int swg_lift_ix::swg_lift_index_build(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, uint32_t ax, uint64_t max_start, LiftIndex* out) {
+  hipStream_t st = ctx->stream;
+  LiftIndex& x = *out;
+  const unsigned grid_n = (unsigned)((n + TB - 1) / TB);
+  const int pb = swg_bits_for(max_start);
+  x.max_start = max_start, x.pb = pb;
+  x.keys = swg_alloc<uint64_t>(ctx, n);
+  x.M = swg_alloc<uint64_t>(ctx, n);
+  x.V = swg_alloc<uint32_t>(ctx, n);
+  x.E = swg_alloc<uint32_t>(ctx, n);
+  SWG_CHECK_ARENA(ctx);
+  SWG_LAUNCH(ctx, "lift_keys", lift_keys_kernel<<<grid_n, TB, 0, st>>>(n, n_seq, c.id[ax], c.start[ax], c.end[ax], c.status, pb, x.keys, x.V));
+  SWG_KERNEL_CHECK(ctx);
+  {
+    swg_prof_scope sort_scope(ctx, "lift_sort");
+    SWG_TRY(swg_radix_sort_pairs(ctx, &x.keys, &x.V, &x.M, &x.E, n, 0, pb + swg_bits_for(n_seq)));  // (the spare pair: M and E)
+  }
+  SWG_LAUNCH(ctx, "lift_gather", lift_gather_kernel<<<grid_n, TB, 0, st>>>(n, n_seq, x.keys, x.V, c.end[ax], pb, x.E, x.M));
+  SWG_KERNEL_CHECK(ctx);
+  SWG_TRY(swg_inclusive_max_scan_u64(ctx, x.M, x.M, n));
+  return SWG_OK;
+}
 
 // the seams' argument checks, then the device work inside an arena frame (also the device half of swg_paf_lift, host/lift_text.cpp)
 int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,

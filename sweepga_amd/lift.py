@@ -1,10 +1,12 @@
 """The lift seen from Python: caller-given regions projected through the mappings of a filter call on the device
-(csrc/swg_lift.hip).  lift_records / lift_records_device are the two record seams, Lift.from_paf BED text through an open PafFile."""
+(csrc/swg_lift.hip).  lift_records / lift_records_device are the two record seams, Lift.from_paf BED text through an open PafFile.
+lift_closure_records / lift_closure_records_device / LiftClosure.from_paf are the same three for the transitive lift
+(csrc/swg_lift_closure.hip): what each region reaches in up to max_hops hops, as disjoint pieces with the hop that found them."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgError, SwgLiftRequest, SwgRecords, default_context, load
+from ._lib import SWG_OK, SwgClosureRequest, SwgError, SwgLiftRequest, SwgRecords, default_context, load
 
 COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
 REGION_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32)])
@@ -13,6 +15,9 @@ UNKNOWN = 2**32 - 1
 SET_ALL, SET_KEPT = 0, 1
 AXIS_QUERY, AXIS_TARGET, AXIS_BOTH = 1, 2, 3
 MINUS, ON_TARGET = 1, 2
+CLOSURE_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")])
+CLOSURE_SUMMARY_DTYPE = np.dtype([("bases", np.uint64), ("pieces", np.uint32), ("sequences", np.uint32), ("hops", np.uint32), ("flags", np.uint32)])
+CLOSURE_CUT = 1
 SETS = {"all": SET_ALL, "kept": SET_KEPT}
 AXES = {"query": AXIS_QUERY, "target": AXIS_TARGET, "both": AXIS_BOTH}
 
@@ -67,11 +72,8 @@ def _status(status, n):
     return st if st.size else np.zeros(1, dtype=np.uint8)
 
 
-def lift_records(ctx, records, strand, n_seq, regions, status=None, set="all", axes="both", capacity=None):
-    """swg_lift_records.  `records`: a dict of numpy columns (q_id, t_id, q_start, q_end, t_start, t_end); strand: uint8 per record
-    (0 = '+'); regions: a REGION_DTYPE array or (seq, start, end) triples, seq = UNKNOWN for a name the input does not have;
-    set: "all" / "kept" (or 0 / 1), axes: "query" / "target" / "both" (or the bit mask).  Returns a LiftResult."""
-    regs = regions_array(regions)
+def _host_records(records, strand, n_seq):
+    """(SwgRecords over the caller's numpy columns, the arrays that must stay alive)"""
     rec = SwgRecords()
     rec.n = len(records["q_id"])
     keep = [np.ascontiguousarray(records[k], dtype=np.uint32) for k in COLUMNS] + [np.ascontiguousarray(strand, dtype=np.uint8)]
@@ -80,16 +82,10 @@ def lift_records(ctx, records, strand, n_seq, regions, status=None, set="all", a
     for k, a in zip(COLUMNS + ("strand",), keep):
         setattr(rec, k, a.ctypes.data if a.size else None)
     rec.n_seq = int(n_seq)
-    st = _status(status, int(rec.n))
-    return _call(ctx, ctx.lib.swg_lift_records, rec, st.ctypes.data if st is not None else None, regs.ctypes.data if regs.size else None,
-                 regs.size, SETS.get(set, set), AXES.get(axes, axes), capacity)
+    return rec, keep
 
 
-def lift_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=None, set="all", axes="both", capacity=None):
-    """swg_lift_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end to
-    contiguous 4-byte tensors of one length, strand and status (or None) are 1-byte tensors with an entry per record, regions a
-    tensor of 16 * n_regions bytes laid out as REGION_DTYPE.  (Anything with .data_ptr(), .numel() and .element_size() works; the
-    caller keeps the tensors alive and their work finished.)  Rows and summary come back as numpy arrays on the host."""
+def _device_records(columns, strand, n_seq, regions, n_regions, status):
     rec = SwgRecords()
     rec.n = int(columns["q_id"].numel())
     for k in COLUMNS:
@@ -104,8 +100,77 @@ def lift_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=
         raise ValueError("regions holds fewer than 16 bytes per region")
     rec.strand = int(strand.data_ptr())
     rec.n_seq = int(n_seq)
+    return rec
+
+
+def lift_records(ctx, records, strand, n_seq, regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_records.  `records`: a dict of numpy columns (q_id, t_id, q_start, q_end, t_start, t_end); strand: uint8 per record
+    (0 = '+'); regions: a REGION_DTYPE array or (seq, start, end) triples, seq = UNKNOWN for a name the input does not have;
+    set: "all" / "kept" (or 0 / 1), axes: "query" / "target" / "both" (or the bit mask).  Returns a LiftResult."""
+    regs = regions_array(regions)
+    rec, keep = _host_records(records, strand, n_seq)
+    st = _status(status, int(rec.n))
+    return _call(ctx, ctx.lib.swg_lift_records, rec, st.ctypes.data if st is not None else None, regs.ctypes.data if regs.size else None,
+                 regs.size, SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+def lift_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end to
+    contiguous 4-byte tensors of one length, strand and status (or None) are 1-byte tensors with an entry per record, regions a
+    tensor of 16 * n_regions bytes laid out as REGION_DTYPE.  (Anything with .data_ptr(), .numel() and .element_size() works; the
+    caller keeps the tensors alive and their work finished.)  Rows and summary come back as numpy arrays on the host."""
+    rec = _device_records(columns, strand, n_seq, regions, n_regions, status)
     return _call(ctx, ctx.lib.swg_lift_records_device, rec, int(status.data_ptr()) if status is not None else None, int(regions.data_ptr()),
                  int(n_regions), SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+class LiftClosureResult:
+    """rows: a CLOSURE_ROW_DTYPE array in (region, seq, start) order, or None when the capacity given did not hold them; n: their
+    number; summary: a CLOSURE_SUMMARY_DTYPE array per region; hops_run, projections (summed over the hops) and candidates (query
+    axis, target axis; summed over the hops) as the request returns them."""
+
+    def __init__(self, rows, n, summary, hops_run, projections, candidates):
+        self.rows, self.n, self.summary, self.hops_run, self.projections, self.candidates = rows, n, summary, hops_run, projections, candidates
+
+
+def _closure_call(ctx, fn, rec, status_addr, regions_addr, m, set_, axes, max_hops, min_len, capacity):
+    req = SwgClosureRequest()
+    req.set, req.axes, req.max_hops, req.min_len = int(set_), int(axes), int(max_hops), int(min_len)
+    summary = np.zeros(m, dtype=CLOSURE_SUMMARY_DTYPE)
+    req.summary = summary.ctypes.data if m else None
+    rows = None
+    if capacity is not None:
+        rows = np.zeros(int(capacity), dtype=CLOSURE_ROW_DTYPE)
+        req.capacity, req.rows = int(capacity), rows.ctypes.data if capacity else None
+    ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(req)))
+    if capacity is None:
+        rows = np.zeros(int(req.n), dtype=CLOSURE_ROW_DTYPE)
+        if req.n:
+            req.capacity, req.rows = int(req.n), rows.ctypes.data
+            ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(req)))
+    elif req.n > capacity:
+        rows = None
+    else:
+        rows = rows[:int(req.n)]
+    return LiftClosureResult(rows, int(req.n), summary, int(req.hops_run), int(req.projections), (int(req.candidates[0]), int(req.candidates[1])))
+
+
+def lift_closure_records(ctx, records, strand, n_seq, regions, max_hops, min_len=100, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_closure_records: the arguments of lift_records, plus the largest number of hops (1 .. 65,535) and the length below
+    which a piece is reported but not walked on.  Returns a LiftClosureResult."""
+    regs = regions_array(regions)
+    rec, keep = _host_records(records, strand, n_seq)
+    st = _status(status, int(rec.n))
+    return _closure_call(ctx, ctx.lib.swg_lift_closure_records, rec, st.ctypes.data if st is not None else None,
+                         regs.ctypes.data if regs.size else None, regs.size, SETS.get(set, set), AXES.get(axes, axes), max_hops, min_len, capacity)
+
+
+def lift_closure_records_device(ctx, columns, strand, n_seq, regions, n_regions, max_hops, min_len=100, status=None, set="all", axes="both",
+                                capacity=None):
+    """swg_lift_closure_records_device: the arguments of lift_records_device, plus max_hops and min_len."""
+    rec = _device_records(columns, strand, n_seq, regions, n_regions, status)
+    return _closure_call(ctx, ctx.lib.swg_lift_closure_records_device, rec, int(status.data_ptr()) if status is not None else None,
+                         int(regions.data_ptr()), int(n_regions), SETS.get(set, set), AXES.get(axes, axes), max_hops, min_len, capacity)
 
 
 def parse_rows(text):
@@ -161,6 +226,63 @@ class Lift:
             p[k] = C.addressof(marker) if wanted else None
         rc = lib.swg_paf_lift(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None, bed, len(bed),
                               SETS.get(set, set), AXES.get(axes, axes), p, n)
+        if rc != SWG_OK:
+            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
+        text = [None, None]
+        for k, wanted in enumerate((rows, summary)):
+            if wanted:
+                text[k] = C.string_at(p[k], n[k]).decode("utf-8", errors="surrogateescape")
+                lib.swg_free(C.c_void_p(p[k]))
+        return cls(text[0], text[1])
+
+
+class LiftClosure:
+    """BED regions walked through an open PafFile hop by hop: `text` (one line per piece: name start end label hop; no strand -- a
+    merged piece can come from both orientations) and `summary_text` (label sequence start end pieces sequences genomes bases hops
+    state per region); `rows` and `summary` are the same parsed into structured numpy arrays.  None where not asked for."""
+
+    def __init__(self, text, summary_text):
+        self.text, self.summary_text = text, summary_text
+
+    @property
+    def rows(self):
+        if self.text is None:
+            return None
+        dt = np.dtype([("name", object), ("start", np.uint32), ("end", np.uint32), ("label", object), ("hop", np.uint32)])
+        lines = [ln.split("\t") for ln in self.text.split("\n") if ln]
+        out = np.zeros(len(lines), dtype=dt)
+        for k, f in enumerate(lines):
+            out[k] = (f[0], int(f[1]), int(f[2]), f[3], int(f[4]))
+        return out
+
+    @property
+    def summary(self):
+        if self.summary_text is None:
+            return None
+        dt = np.dtype([("label", object), ("sequence", object), ("start", np.uint32), ("end", np.uint32), ("pieces", np.uint32),
+                       ("sequences", np.uint32), ("genomes", np.uint32), ("bases", np.uint64), ("hops", np.uint32), ("state", object)])
+        lines = [ln.split("\t") for ln in self.summary_text.split("\n")[1:] if ln]
+        out = np.zeros(len(lines), dtype=dt)
+        for k, f in enumerate(lines):
+            out[k] = (f[0], f[1], int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), int(f[8]), f[9])
+        return out
+
+    @classmethod
+    def from_paf(cls, paf, status, bed_text, max_hops, min_len=100, set="kept", axes="both", ctx=None, rows=True, summary=True):
+        """swg_paf_lift_closure: both texts from one walk.  status None: set must be "all".  ctx as in Lift.from_paf."""
+        ctx = getattr(ctx, "ctx", ctx)
+        lib = load()
+        bed = bed_text.encode("utf-8", errors="surrogateescape") if isinstance(bed_text, str) else bytes(bed_text)
+        rebased = bool(lib.swg_paf_seq_offsets(paf.handle)) or bool(lib.swg_paf_record_offsets(paf.handle, 0))   # (refused by the library)
+        if ctx is None and paf.n and bed.strip() and not rebased and 0 < int(max_hops) <= 65535:
+            ctx = default_context()
+        st = _status(status, paf.n)
+        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
+        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
+        for k, wanted in enumerate((rows, summary)):
+            p[k] = C.addressof(marker) if wanted else None
+        rc = lib.swg_paf_lift_closure(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None, bed,
+                                      len(bed), SETS.get(set, set), AXES.get(axes, axes), int(max_hops), int(min_len), p, n)
         if rc != SWG_OK:
             raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
         text = [None, None]
