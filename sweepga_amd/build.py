@@ -119,6 +119,26 @@ def build_prim_check(force=False, verbose=False):
     return PRIM_CHECK
 
 
+REBASE_CHECK_SRC = os.path.join(HERE, "..", "tests", "native", "rebase_check.cpp")
+REBASE_CHECK = os.path.join(HERE, "bin", "rebase_check")
+
+
+def build_rebase_check(force=False, verbose=False, out=None, extra=()):
+    """tests/native/rebase_check.cpp: the host rebasing of csrc/host/rebase.h case by case from a list, outputs to files (host code
+    only; tests/test_wide_edges_cpu.py runs it and checks every output against tests/wide_model.py).  out / extra: another
+    binary with further compiler flags (the test's sanitizer build)."""
+    out = out or REBASE_CHECK
+    deps = [REBASE_CHECK_SRC, os.path.join(CSRC, "host", "rebase.h"), os.path.join(CSRC, "host", "threads.h")]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    cmd = ["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Wextra", *extra, "-o", out, REBASE_CHECK_SRC, "-lpthread"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return out
+
+
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
@@ -198,6 +218,7 @@ def build(force=False, verbose=False):
     build_synth(force=force, verbose=verbose)
     build_sort_bench(force=force, verbose=verbose)
     build_prim_check(force=force, verbose=verbose)
+    build_rebase_check(force=force, verbose=verbose)
     return LIB
 
 

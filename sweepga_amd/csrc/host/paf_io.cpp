@@ -679,6 +679,8 @@ int parse_text(swg_paf* p, int threads) {
                                     p->wide[3].data(), p->wide[4].data(), p->wide[5].data()};
     uint32_t* const c32[6] = {p->qs.data(), p->qe.data(), p->ts.data(), p->te.data(), p->matches.data(), p->block.data()};
     swg_rebase::Result rr = swg_rebase::columns(n, p->q_id.data(), p->t_id.data(), c64, n_seq, threads, c32, p->seq_offset.data());
+    bool by_axis = false;     // rr is the second attempt's: its record, its field, and the segment's own first mapped base
+    uint64_t first_base = 0;
     if (!rr.ok && rr.bad_field < 4 && swg_rebase::axis_tables_fit(n_seq, n_last)) {
       // a sequence touched over 2^32 bases or more: one constant per sweep segment and axis instead (host/rebase.h, columns_by_axis);
       // the columns are then relative to constants the handle does not publish (swg_paf_seq_offsets: NULL)
@@ -686,10 +688,12 @@ int parse_text(swg_paf* p, int threads) {
       p->rec_off_t.assign(n, 0);
       const swg_rebase::Result r2 = swg_rebase::columns_by_axis(n, p->q_id.data(), p->t_id.data(), c64, n_seq, p->g_last.data(), n_last, threads, c32,
                                                                 p->rec_off_q.data(), p->rec_off_t.data());
+      rr = r2;  // also when it failed: the message below is about the limit per genome, which is what this attempt tested
+      by_axis = true;
       if (r2.ok) {
-        rr = r2;
         p->seq_offset.clear();
       } else {
+        first_base = (r2.bad_field < 2 ? p->rec_off_q : p->rec_off_t)[r2.bad_record];
         p->rec_off_q.clear();
         p->rec_off_t.clear();
       }
@@ -702,7 +706,8 @@ int parse_text(swg_paf* p, int threads) {
       const uint32_t sid = rr.bad_field < 2 ? p->q_id[k] : p->t_id[k];
       return paf_error(SWG_ERR_RANGE, "the stretch of sequence %s that the mappings against one genome touch spans 2^32 bases or more (%s on "
                        "line %llu, first mapped base %llu): not supported by the 32-bit device layout", p->names[sid].c_str(),
-                       swg_rebase::field_name(rr.bad_field), (unsigned long long)(p->rank[k] + 1), (unsigned long long)p->seq_offset[sid]);
+                       swg_rebase::field_name(rr.bad_field), (unsigned long long)(p->rank[k] + 1),
+                       (unsigned long long)(by_axis ? first_base : p->seq_offset[sid]));
     }
     for (auto& w : p->wide) w.alloc(0);
     lap("rebase");
@@ -1497,6 +1502,8 @@ int swg_aln_open(const swg_aln_input* in, swg_aln** out) {
       const uint64_t* const c64[6] = {in->query_start, in->query_end, in->target_start, in->target_end, in->matches, block64.data()};
       uint32_t* const c32[6] = {a->qs.data(), a->qe.data(), a->ts.data(), a->te.data(), a->matches.data(), a->block.data()};
       swg_rebase::Result rr = swg_rebase::columns(n, a->q_id.data(), a->t_id.data(), c64, n_seq, pick_threads(0), c32, a->seq_offset.data());
+      bool by_axis = false;
+      uint64_t first_base = 0;
       if (!rr.ok && rr.bad_field < 4) {  // (see swg_paf_open)
         std::vector<uint32_t> g_last;
         const uint32_t n_last = genome_table(a->names, prefix_last, &g_last);
@@ -1505,10 +1512,12 @@ int swg_aln_open(const swg_aln_input* in, swg_aln** out) {
           a->rec_off_t.assign(n, 0);
           const swg_rebase::Result r2 = swg_rebase::columns_by_axis(n, a->q_id.data(), a->t_id.data(), c64, n_seq, g_last.data(), n_last, pick_threads(0), c32,
                                                                     a->rec_off_q.data(), a->rec_off_t.data());
+          rr = r2;  // also when it failed: its record and field are the ones that break the limit per genome
+          by_axis = true;
           if (r2.ok) {
-            rr = r2;
             a->seq_offset.clear();
           } else {
+            first_base = (r2.bad_field < 2 ? a->rec_off_q : a->rec_off_t)[r2.bad_record];
             a->rec_off_q.clear();
             a->rec_off_t.clear();
           }
@@ -1517,9 +1526,14 @@ int swg_aln_open(const swg_aln_input* in, swg_aln** out) {
       if (!rr.ok) {
         const uint64_t k = rr.bad_record;
         const int f = rr.bad_field;
-        std::string what = f >= 4 ? std::string(swg_rebase::field_name(f)) + " >= 2^32"
-                                  : "the mapped stretch of sequence " + a->names[f < 2 ? a->q_id[k] : a->t_id[k]] +
-                                        " spans 2^32 bases or more";
+        std::string what;
+        if (f >= 4) {
+          what = std::string(swg_rebase::field_name(f)) + " >= 2^32";
+        } else {
+          const uint32_t sid = f < 2 ? a->q_id[k] : a->t_id[k];
+          what = "the mapped stretch of sequence " + a->names[sid] + " spans 2^32 bases or more (" + swg_rebase::field_name(f) +
+                 ", first mapped base " + std::to_string(by_axis ? first_base : a->seq_offset[sid]) + (by_axis ? " against that genome)" : ")");
+        }
         delete a;
         return paf_error(SWG_ERR_RANGE, "alignment %llu: %s: not supported by the 32-bit device layout", (unsigned long long)k,
                          what.c_str());

@@ -102,6 +102,19 @@ inline Result columns(uint64_t n, const uint32_t* q_id, const uint32_t* t_id, co
 // against ONE genome.  seq_genome = the records' seq_genome_last table.  Two tables of n_seq * n_genome offsets (the caller
 // checks that this is affordable: axis_tables_fit).  Same result convention as columns(); ids are taken as checked.
 inline bool axis_tables_fit(uint32_t n_seq, uint32_t n_genome) { return (uint64_t)n_seq * n_genome <= (uint64_t(1) << 24); }
+// What a caller whose genome table is not its own runs before columns_by_axis, which follows the table's entries unchecked: the
+// first record that names a sequence whose entry is n_genome or more (field 6, as for an id out of range).  Ids are taken as checked.
+inline Result genome_entries(uint64_t n, const uint32_t* q_id, const uint32_t* t_id, const uint32_t* seq_genome, uint32_t n_genome) {
+  Result r;
+  for (uint64_t i = 0; i < n; ++i)
+    if (seq_genome[q_id[i]] >= n_genome || seq_genome[t_id[i]] >= n_genome) {
+      r.ok = false;
+      r.bad_record = i;
+      r.bad_field = 6;
+      break;
+    }
+  return r;
+}
 inline Result columns_by_axis(uint64_t n, const uint32_t* q_id, const uint32_t* t_id, const uint64_t* const c64[6], uint32_t n_seq,
                               const uint32_t* seq_genome, uint32_t n_genome, int threads, uint32_t* const c32[6],
                               uint64_t* rec_off_q = nullptr, uint64_t* rec_off_t = nullptr) {

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(EW) void seq_lo_kernel(uint64_t n, const uint32_t* 
                                                     const uint64_t* __restrict__ qs, const uint64_t* __restrict__ qe,
                                                     const uint64_t* __restrict__ ts, const uint64_t* __restrict__ te,
                                                     uint32_t n_seq, unsigned long long* __restrict__ lo,
-                                                    unsigned long long* __restrict__ bad) {
+                                                    unsigned long long* __restrict__ bad_id) {
   const uint64_t i = (uint64_t)blockIdx.x * EW + threadIdx.x;
   bool in = i < n;
   if (__ballot(in) == 0) return;
@@ -94,8 +94,9 @@ __global__ __launch_bounds__(EW) void seq_lo_kernel(uint64_t n, const uint32_t* 
   if (in) {
     q = q_id[i];
     t = t_id[i];
-    if (q >= n_seq || t >= n_seq) {  // the ids index the table: reported like the host version does (field 6), never followed
-      atomicMin(bad, ((unsigned long long)(i + 1) << 3) | 6u);
+    if (q >= n_seq || t >= n_seq) {  // the ids index the table: never followed, and reported in a word of their own -- like the
+                                     // host version, a bad id is refused before any value that does not fit, wherever it sits
+      atomicMin(bad_id, (unsigned long long)i);
       in = false;
       q = t = 0;
     } else {
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(EW) void seq_lo_kernel(uint64_t n, const uint32_t* 
   seq_min_atomic(lo, q, a, in);
   seq_min_atomic(lo, t, b, in);
 }
-// bad[0] = 1 + smallest record index whose rebased value does not fit 32 bits (0: none), bad[1] = its field
+// bad = min over the records with a rebased value that does not fit 32 bits of (record + 1) << 3 | its first such field (~0: none)
 __global__ __launch_bounds__(EW) void rebase_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
                                                     const uint64_t* __restrict__ qs, const uint64_t* __restrict__ qe,
                                                     const uint64_t* __restrict__ ts, const uint64_t* __restrict__ te,
@@ -135,7 +136,9 @@ __global__ __launch_bounds__(EW) void rebase_kernel(uint64_t n, const uint32_t* 
 }
 
 // the same with one constant per sweep segment and axis (host/rebase.h, columns_by_axis): lo_q[(q, genome(t))], lo_t[(t, genome(q))]
-// (only behind seq_lo_kernel: the ids are known to be in range; the genome table's entries are the caller's, checked here)
+// (swg_filter_piece launches these two only after it has read seq_lo_kernel's bad_id word and found it clear: every id is then
+// below n_seq.  The genome table's entries are the caller's and are checked here: a record that names a sequence whose entry is
+// n_genome or more is skipped and reported in bad_id, the smallest such record.)
 __global__ __launch_bounds__(EW) void axis_lo_kernel(uint64_t n, const uint32_t* __restrict__ q_id, const uint32_t* __restrict__ t_id,
                                                      const uint64_t* __restrict__ qs, const uint64_t* __restrict__ qe,
                                                      const uint64_t* __restrict__ ts, const uint64_t* __restrict__ te,
@@ -167,12 +170,13 @@ __global__ __launch_bounds__(EW) void axis_rebase_kernel(uint64_t n, const uint3
                                                          const uint32_t* __restrict__ seq_genome, uint32_t n_genome,
                                                          const unsigned long long* __restrict__ lo_q, const unsigned long long* __restrict__ lo_t,
                                                          uint32_t* __restrict__ o_qs, uint32_t* __restrict__ o_qe, uint32_t* __restrict__ o_ts,
-                                                         uint32_t* __restrict__ o_te, unsigned long long* __restrict__ bad) {
+                                                         uint32_t* __restrict__ o_te, unsigned long long* __restrict__ bad,
+                                                         unsigned long long* __restrict__ bad_id) {
   const uint64_t i = (uint64_t)blockIdx.x * EW + threadIdx.x;
   if (i >= n) return;
   const uint32_t q = q_id[i], t = t_id[i], gq = seq_genome[q], gt = seq_genome[t];
   if (gq >= n_genome || gt >= n_genome) {
-    atomicMin(bad, ((unsigned long long)(i + 1) << 3) | 6u);
+    atomicMin(bad_id, (unsigned long long)i);
     return;
   }
   const unsigned long long oq = lo_q[(size_t)q * n_genome + gt], ot = lo_t[(size_t)t * n_genome + gq];
@@ -639,44 +643,47 @@ int swg_filter_piece(swg_ctx* ctx, const swg_records* rec, const swg_records64* 
   hipStream_t st = ctx->stream;
   uint32_t* c[6];
   for (auto& p : c) p = swg_alloc<uint32_t>(ctx, n);
-  unsigned long long* lo = swg_alloc<unsigned long long>(ctx, (size_t)rec->n_seq + 1);  // + the error word
+  unsigned long long* lo = swg_alloc<unsigned long long>(ctx, (size_t)rec->n_seq + 2);  // + the two error words
   SWG_CHECK_ARENA(ctx);
-  unsigned long long* bad = lo + rec->n_seq;
-  SWG_HIP(ctx, hipMemsetAsync(lo, 0xff, ((size_t)rec->n_seq + 1) * sizeof(unsigned long long), st));
+  unsigned long long* bad = lo + rec->n_seq;  // bad[0]: a value that does not fit; bad[1]: an id out of range, which wins
+  SWG_HIP(ctx, hipMemsetAsync(lo, 0xff, ((size_t)rec->n_seq + 2) * sizeof(unsigned long long), st));
   SWG_LAUNCH(ctx, "seq_lo", seq_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
-                                                                 rec64->t_start, rec64->t_end, rec->n_seq, lo, bad));
+                                                                 rec64->t_start, rec64->t_end, rec->n_seq, lo, bad + 1));
   SWG_LAUNCH(ctx, "rebase", rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
                                                                  rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len,
                                                                  rec->n_seq, lo, c[0], c[1], c[2], c[3], c[4], c[5], bad));
   SWG_KERNEL_CHECK(ctx);
-  uint64_t hb;
-  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad), &hb, 1));
+  uint64_t h2[2];
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad), h2, 2));
+  if (h2[1] != ~0ull)  // before anything else, and before the kernels below follow the ids
+    return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: sequence id out of range", (unsigned long long)h2[1]);
+  uint64_t hb = h2[0];
   if (hb != ~0ull && (hb & 7) < 4 && swg_rebase::axis_tables_fit(rec->n_seq, rec->n_genome_last)) {
     // a sequence touched over 2^32 bases or more: the constants per sweep segment -- (sequence, genome of the other side) --
     // instead (host/rebase.h, columns_by_axis)
     const size_t cells = (size_t)rec->n_seq * rec->n_genome_last;
-    unsigned long long* lo2 = swg_alloc<unsigned long long>(ctx, 2 * cells + 1);
+    unsigned long long* lo2 = swg_alloc<unsigned long long>(ctx, 2 * cells + 2);
     SWG_CHECK_ARENA(ctx);
-    unsigned long long* bad2 = lo2 + 2 * cells;
-    SWG_HIP(ctx, hipMemsetAsync(lo2, 0xff, (2 * cells + 1) * sizeof(unsigned long long), st));
+    unsigned long long* bad2 = lo2 + 2 * cells;  // as bad: [0] a value, [1] a genome table entry out of range
+    SWG_HIP(ctx, hipMemsetAsync(lo2, 0xff, (2 * cells + 2) * sizeof(unsigned long long), st));
     SWG_LAUNCH(ctx, "axis_lo", axis_lo_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end, rec64->t_start,
                                                                    rec64->t_end, rec->seq_genome_last, rec->n_genome_last, lo2, lo2 + cells));
     SWG_LAUNCH(ctx, "axis_rebase", axis_rebase_kernel<<<nblk(n), EW, 0, st>>>(n, rec64->q_id, rec64->t_id, rec64->q_start, rec64->q_end,
                                                                            rec64->t_start, rec64->t_end, rec64->matches, rec64->block_len, rec->seq_genome_last,
-                                                                           rec->n_genome_last, lo2, lo2 + cells, c[0], c[1], c[2], c[3], bad2));
+                                                                           rec->n_genome_last, lo2, lo2 + cells, c[0], c[1], c[2], c[3], bad2, bad2 + 1));
     SWG_KERNEL_CHECK(ctx);
-    SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad2), &hb, 1));
+    SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(bad2), h2, 2));
+    if (h2[1] != ~0ull)
+      return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: the seq_genome_last entry of its sequence is out of range", (unsigned long long)h2[1]);
+    hb = h2[0];
   }
   if (hb != ~0ull) {
-    static const char* const F[8] = {"query_start", "query_end", "target_start", "target_end", "matches", "block_length", "?", "?"};
-    const int f = (int)(hb & 7);
-    if (f == 6)
-      return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: sequence id out of range", (unsigned long long)((hb >> 3) - 1));
+    const int f = (int)(hb & 7);  // 0..5: ids and genome entries have their own word
     return swg_set_error(ctx, SWG_ERR_RANGE,
                          f >= 4 ? "record %llu: %s >= 2^32 is not supported"
                                 : "record %llu: the stretch of its sequence that the mappings against one genome touch spans 2^32 bases or "
                                   "more (%s): not supported by the 32-bit device layout",
-                         (unsigned long long)((hb >> 3) - 1), F[f]);
+                         (unsigned long long)((hb >> 3) - 1), swg_rebase::field_name(f));
   }
   swg_records r32 = *rec;
   r32.q_start = c[0];
@@ -1034,8 +1041,10 @@ int swg_rebase_host(swg_ctx* ctx, const swg_records64* rec, const swg_config* cf
     return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: sequence id out of range", (unsigned long long)rr.bad_record);
   if (!rr.ok && rr.bad_field < 4 && swg_rebase::axis_tables_fit(rec->n_seq, rec->n_genome_last)) {
     // a sequence touched over 2^32 bases or more: the constants per sweep segment -- (sequence, genome of the other side) -- instead
-    for (uint32_t s = 0; s < rec->n_seq; ++s)
-      if (rec->seq_genome_last[s] >= rec->n_genome_last) return swg_set_error(ctx, SWG_ERR_INVALID, "seq_genome_last[%u] out of range", s);
+    const swg_rebase::Result ge = swg_rebase::genome_entries(n, rec->q_id, rec->t_id, rec->seq_genome_last, rec->n_genome_last);
+    if (!ge.ok)  // (columns_by_axis follows the table's entries: the first record that names a bad one)
+      return swg_set_error(ctx, SWG_ERR_INVALID, "record %llu: the seq_genome_last entry of its sequence is out of range",
+                           (unsigned long long)ge.bad_record);
     try {
       rr = swg_rebase::columns_by_axis(n, rec->q_id, rec->t_id, c64, rec->n_seq, rec->seq_genome_last, rec->n_genome_last,
                                        hc ? (int)(hc > 64 ? 64 : hc) : 1, c32);
