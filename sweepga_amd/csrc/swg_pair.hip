@@ -34,6 +34,10 @@ constexpr uint32_t PAIR_CELL = WALK_CHUNK;        // a chunk = the units that be
 constexpr uint32_t PAIR_S_MAX = 1024, PAIR_M_MAX = 4096, PAIR_L_MAX = 32768, PAIR_XL_MAX = uint32_t(1) << 18;
 constexpr uint32_t PAIR_XL_CELLS = PAIR_XL_MAX / PAIR_CELL;
 constexpr uint32_t PAIR_HASH_MAX = 65536;  // inputs up to this many records find their pairs through a hash table
+// pair_sort over the third class: pairs of up to PAIR_MX_MAX records go to work-groups of 512 threads, two to a CU (pair_sort_mx)
+constexpr uint32_t PAIR_MX_MAX = 16384, PAIR_MX_CUT_DEFAULT = 8192;
+constexpr uint32_t ORDER_BIN_L = 128;       // pair_order: width of a length bin of the third class; a cut is a multiple of it
+constexpr uint32_t ORDERED = 0x80000000u;   // PairCounters::n_above: pair_order has run over list 2, the low bits are valid
 constexpr uint32_t PF_NOT_GROUPED = 1, PF_RUN_OVERFLOW = 2, PF_TOO_LONG = 4, PF_FALLBACK = 8;
 
 struct PairRun {
@@ -57,6 +61,8 @@ struct PairCounters {
   uint32_t n_runs;
   uint32_t flags;
   uint32_t n_class[4];
+  uint32_t n_above;  // pair_order: ORDERED | how many pairs at the head of list 2 are longer than the cut (see pair_order_kernel)
+  uint32_t pad_;
   uint32_t n_chunks;
   uint32_t n_long;
   unsigned long long n_alive, n_members, n_heads, n_kept, n_out;
@@ -276,22 +282,36 @@ __global__ __launch_bounds__(256) void pair_runs_kernel(uint32_t n, uint32_t cap
 // of a list carries no meaning -- a pair's chunk slots follow from its place in the input, the numbering from its keys -- so
 // every kernel that takes its pairs from these lists (pair_sort_big, pair_chains, pair_finish, pair_out) starts its longest
 // pairs first without knowing.  tmp: room for cap_tmp entries per class (a class-2 pair has more than PAIR_M_MAX records).
+// The bins of list 2 are ORDER_BIN_L lengths wide, (lo + 128 b, lo + 128 (b + 1)], so that a length `cut` that is a multiple of
+// ORDER_BIN_L is a boundary between two bins: the pairs longer than the cut are an exact prefix of the ordered list, and its
+// length is left in C->n_above together with the ORDERED bit (pair_sort's two launches over list 2 split there; without the
+// bit -- the kernel did not run, or returned early -- the list has no such prefix and one launch takes it all).
 constexpr int ORDER_NT = 1024, ORDER_BINS = 256;
+static_assert((PAIR_L_MAX - PAIR_M_MAX) % ORDER_BIN_L == 0 && (PAIR_L_MAX - PAIR_M_MAX) / ORDER_BIN_L <= (uint32_t)ORDER_BINS &&
+                  (PAIR_XL_MAX - PAIR_L_MAX) % (uint32_t)ORDER_BINS == 0 && PAIR_M_MAX % ORDER_BIN_L == 0,
+              "whole bins, a bin boundary at every multiple of ORDER_BIN_L");
 __global__ __launch_bounds__(ORDER_NT) void pair_order_kernel(const PairRun* __restrict__ runs, uint32_t* __restrict__ class_list, uint32_t cap,
-                                                              uint32_t* __restrict__ tmp, uint32_t cap_tmp,
-                                                              const PairCounters* __restrict__ C) {
+                                                              uint32_t* __restrict__ tmp, uint32_t cap_tmp, uint32_t cut,
+                                                              PairCounters* __restrict__ C) {
   __shared__ uint32_t bin_at[ORDER_BINS];
   const int tid = threadIdx.x, cls = 2 + (int)blockIdx.x;
   if (C->flags) return;  // (pair_plan gives the path up: the lists are not read)
   const uint32_t cnt = C->n_class[cls];
-  if (cnt < 2u || cnt > cap_tmp || cnt > cap) return;
-  const uint32_t lo = cls == 2 ? PAIR_M_MAX : PAIR_L_MAX, width = (cls == 2 ? PAIR_L_MAX : PAIR_XL_MAX) - lo;  // lengths in (lo, lo + width]
   uint32_t* const list = class_list + (size_t)cls * cap;
+  if (cnt > cap_tmp || cnt > cap) return;
+  if (cnt < 2u) {  // (nothing to order)
+    if (cls == 2 && tid == 0) C->n_above = ORDERED | (cnt && runs[list[0]].n > cut ? 1u : 0u);
+    return;
+  }
+  const uint32_t lo = cls == 2 ? PAIR_M_MAX : PAIR_L_MAX;  // lengths in (lo, lo + bins * bw]
+  const uint32_t bw = cls == 2 ? ORDER_BIN_L : (PAIR_XL_MAX - PAIR_L_MAX) / (uint32_t)ORDER_BINS;
   uint32_t* const t = tmp + (size_t)blockIdx.x * cap_tmp;
   auto bin_of = [&](uint32_t len) -> uint32_t {
-    const uint32_t b = (uint32_t)(((uint64_t)(len - lo - 1u) * ORDER_BINS) / width);
+    const uint32_t b = (len - lo - 1u) / bw;
     return (uint32_t)ORDER_BINS - 1u - (b < (uint32_t)ORDER_BINS ? b : (uint32_t)ORDER_BINS - 1u);
   };
+  // the first bin (in list order) of the pairs of at most `cut` records; ORDER_BINS: there are none (cut <= lo)
+  const uint32_t cut_bin = (uint32_t)ORDER_BINS - (cut > lo ? (cut - lo) / bw : 0u);
   for (int b = tid; b < ORDER_BINS; b += ORDER_NT) bin_at[b] = 0u;
   __syncthreads();
   for (uint32_t i = tid; i < cnt; i += ORDER_NT) {
@@ -317,9 +337,11 @@ __global__ __launch_bounds__(ORDER_NT) void pair_order_kernel(const PairRun* __r
     uint32_t o = inc - s;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
+      if (cls == 2 && (uint32_t)(tid * PER + j) == cut_bin) C->n_above = ORDERED | o;
       bin_at[tid * PER + j] = o;
       o += v[j];
     }
+    if (cls == 2 && cut_bin == (uint32_t)ORDER_BINS && tid == 63) C->n_above = ORDERED | o;  // (o: the whole list)
   }
   __syncthreads();  // (every read of the list is done; a thread reads back the entries of tmp it wrote itself)
   for (uint32_t i = tid; i < cnt; i += ORDER_NT) {
@@ -456,7 +478,7 @@ struct PairSortArgs {
 
 // What a pair_sort work-group does once its members are in order, shared by the two kernels below.
 //
-// emit_chunks: the chunk list of the walk from the per-cell first unit starts (cellmin; one thread).  The first unit of every
+// emit_chunks: the chunk list of the walk from the per-cell first unit starts (cellmin; one wavefront).  The first unit of every
 // cell opens a chunk, and so does the first '-' member; a chunk of LABEL_CAP_ELEMS members or more (a long unit) is also put on
 // the list of the chunks that chain_label_long_kernel labels.
 // Round 6: a pair's chunks take a stretch of the list that follows from its place in the input -- slot a / PAIR_CELL + 2 * (the
@@ -465,49 +487,96 @@ struct PairSortArgs {
 // trip was most of the 5.8 us a pair spent here, alone on its CU).  The list is zeroed per call and the kernels that walk it skip
 // empty descriptors; its length is its capacity.  (Inputs grouped through the hash table -- at most 65,536 records -- number
 // their pairs by atomics: no order to rely on, the counter stays.)
-__device__ void emit_chunks(const PairSortArgs& A, uint32_t rk_run, uint32_t a, uint32_t m, uint32_t m_plus, const uint32_t* cellmin, int n_cell) {
-  uint32_t prev = NONE, count = 0, n_long = 0, prev2 = NONE;
-  const bool mp_pending = m_plus > 0 && m_plus < m;
-  auto for_starts = [&](auto&& f) {
-    bool pend = mp_pending;
-    for (int c = 0; c < n_cell; ++c) {
-      const uint32_t v = cellmin[c];
-      if (v == NONE) continue;
-      if (pend && m_plus <= v) {
-        if (m_plus < v) f(m_plus);
-        pend = false;
-      }
-      f(v);
-    }
-    if (pend) f(m_plus);
+__device__ __forceinline__ void emit_chunks(const PairSortArgs& A, uint32_t rk_run, uint32_t a, uint32_t m, uint32_t m_plus, const uint32_t* cellmin, int n_cell) {
+  // Run by the work-group's first wavefront, a lane per cell (64 cells at a time).  The starts are the cells' minima in cell
+  // order with m_plus put in where it is not one of them; chunk k runs from start k to start k + 1, the last one to m.  A lane
+  // writes the chunk that ENDS at its cell's start: its begin is the start before it (the nearest lower lane with a start, or
+  // the last start of the 64 cells before), its index the number of starts before its own, less one.  The two chunks no lane
+  // ends -- the one that ends at an inserted m_plus, the last one -- are written by lane 0.
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t n_start = 0, n_lt = 0, before_mp = NONE, last = NONE;  // starts, starts < m_plus, the last of those, the last of all
+  bool mp_is_start = false;
+  for (int c0 = 0; c0 < n_cell; c0 += 64) {
+    const uint32_t v = c0 + lane < n_cell ? cellmin[c0 + lane] : NONE;
+    const unsigned long long mask = __ballot(v != NONE);
+    if (!mask) continue;
+    const unsigned long long lt = __ballot(v != NONE && v < m_plus);
+    mp_is_start |= __ballot(v == m_plus) != 0ull;
+    n_start += (uint32_t)__popcll(mask);
+    n_lt += (uint32_t)__popcll(lt);
+    if (lt) before_mp = (uint32_t)__shfl((int)v, 63 - __clzll(lt), 64);
+    last = (uint32_t)__shfl((int)v, 63 - __clzll(mask), 64);
+  }
+  const bool mp_ins = m_plus > 0 && m_plus < m && !mp_is_start;  // m_plus is a start of its own
+  const uint32_t count = n_start + (mp_ins ? 1u : 0u);
+  if (count == 0) return;
+  // the begin of the chunk that ends at the lane's start v (NONE: v is the first start); carry: the last start of earlier cells
+  auto begin_of = [&](uint32_t v, unsigned long long mask, uint32_t carry) -> uint32_t {
+    const unsigned long long lower = mask & below;
+    const uint32_t pv = (uint32_t)__shfl((int)v, lower ? 63 - __clzll(lower) : 0, 64);
+    uint32_t b = lower ? pv : carry;
+    if (mp_ins && m_plus < v && (b == NONE || b < m_plus)) b = m_plus;
+    return b;
   };
-  for_starts([&](uint32_t v) {
-    ++count;
-    if (prev2 != NONE && v - prev2 >= LABEL_CAP_ELEMS) ++n_long;
-    prev2 = v;
-  });
-  if (prev2 != NONE && m - prev2 >= LABEL_CAP_ELEMS) ++n_long;
-  const uint32_t slot = A.chunks_by_place ? a / PAIR_CELL + 2u * rk_run : atomicAdd(&A.C->n_chunks, count);
-  uint32_t lslot = n_long ? atomicAdd(&A.C->n_long, n_long) : 0u;
+  const bool mp_chunk = mp_ins && before_mp != NONE;                         // (before_mp, m_plus): chunk n_lt - 1
+  const bool mp_long = mp_chunk && m_plus - before_mp >= LABEL_CAP_ELEMS;
+  const uint32_t last_b = mp_ins && (last == NONE || last < m_plus) ? m_plus : last;  // (last_b, m): chunk count - 1
+  const bool last_long = m - last_b >= LABEL_CAP_ELEMS;
+  uint32_t n_long = (mp_long ? 1u : 0u) + (last_long ? 1u : 0u), n_long_lt = 0;  // n_long_lt: long chunks in front of chunk n_lt - 1
+  {
+    uint32_t carry = NONE;
+    for (int c0 = 0; c0 < n_cell; c0 += 64) {
+      const uint32_t v = c0 + lane < n_cell ? cellmin[c0 + lane] : NONE;
+      const unsigned long long mask = __ballot(v != NONE);
+      if (!mask) continue;
+      const uint32_t b = begin_of(v, mask, carry);
+      const bool lf = v != NONE && b != NONE && v - b >= LABEL_CAP_ELEMS;
+      n_long += (uint32_t)__popcll(__ballot(lf));
+      n_long_lt += (uint32_t)__popcll(__ballot(lf && v < m_plus));
+      carry = (uint32_t)__shfl((int)v, 63 - __clzll(mask), 64);
+    }
+  }
+  uint32_t slot = 0, lslot = 0;
+  if (lane == 0) {
+    slot = A.chunks_by_place ? a / PAIR_CELL + 2u * rk_run : atomicAdd(&A.C->n_chunks, count);
+    lslot = n_long ? atomicAdd(&A.C->n_long, n_long) : 0u;
+  }
+  slot = (uint32_t)__shfl((int)slot, 0, 64);
+  lslot = (uint32_t)__shfl((int)lslot, 0, 64);
   if (slot + count > A.cap_chunks || (n_long && lslot + n_long > A.cap_long)) {  // (the capacities are upper bounds: not reached)
-    atomicOr(&A.C->flags, PF_FALLBACK);
+    if (lane == 0) atomicOr(&A.C->flags, PF_FALLBACK);
     return;
   }
-  uint32_t k = 0;
-  auto emit = [&](uint32_t b, uint32_t e) {
+  auto emit = [&](uint32_t k, uint32_t b, uint32_t e, bool is_long, uint32_t lpos) {
     SpecBlock d;
     d.bb = a + b;
     d.be = a + e;
     d.ue = d.be;
     d.pad = b >= m_plus ? 1u : 0u;
-    if (e - b >= LABEL_CAP_ELEMS) A.long_list[lslot++] = slot + k;
-    A.chunks[slot + k++] = d;
+    if (is_long) A.long_list[lslot + lpos] = slot + k;
+    A.chunks[slot + k] = d;
   };
-  for_starts([&](uint32_t v) {
-    if (prev != NONE) emit(prev, v);
-    prev = v;
-  });
-  if (prev != NONE) emit(prev, m);
+  uint32_t carry = NONE, base = 0, lbase = 0;
+  for (int c0 = 0; c0 < n_cell; c0 += 64) {
+    const uint32_t v = c0 + lane < n_cell ? cellmin[c0 + lane] : NONE;
+    const unsigned long long mask = __ballot(v != NONE);
+    if (!mask) continue;
+    const uint32_t b = begin_of(v, mask, carry);
+    const bool lf = v != NONE && b != NONE && v - b >= LABEL_CAP_ELEMS;
+    const unsigned long long lmask = __ballot(lf);
+    if (v != NONE && b != NONE) {
+      const uint32_t k = base + (uint32_t)__popcll(mask & below) + (mp_ins && v > m_plus ? 1u : 0u) - 1u;
+      emit(k, b, v, lf, lbase + (uint32_t)__popcll(lmask & below) + (mp_long && v > m_plus ? 1u : 0u));
+    }
+    base += (uint32_t)__popcll(mask);
+    lbase += (uint32_t)__popcll(lmask);
+    carry = (uint32_t)__shfl((int)v, 63 - __clzll(mask), 64);
+  }
+  if (lane == 0) {
+    if (mp_chunk) emit(n_lt - 1u, before_mp, m_plus, mp_long, n_long_lt);
+    emit(count - 1u, last_b, m, last_long, n_long - 1u);
+  }
 }
 // unit_starts: the thread's E consecutive positions p0 .. p0 + E of a batch of mb members that begins at pair position
 // `base`; qs / qe are their sorted q_start / q_end.  Position p opens a unit when its q_start lies beyond every earlier q_end
@@ -620,6 +689,10 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
   const int tid = threadIdx.x;
   const PairRun run = A.runs[rk_run];
   const uint32_t a = run.a, n = run.n;
+  if (n > (uint32_t)NREC) {  // (never: the class bounds and pair_order's cut see to it; a longer pair would run past the LDS block)
+    if (tid == 0) atomicOr(&A.C->flags, PF_FALLBACK);
+    return;
+  }
   if (tid < 4) sh_cnt[tid] = 0;
   if (tid < 2) {
     sh_kmin[tid] = 0xffffffffu;
@@ -1160,7 +1233,7 @@ __device__ __forceinline__ void pair_sort_body(const PairSortArgs& A, const uint
     PT_STAMP(11);
   }
   if (A.check_degenerate && __any(degenerate) && (tid & 63) == 0) atomicOr(&A.C->flags, PF_FALLBACK);
-  if (tid == 0) emit_chunks(A, rk_run, a, m, m_plus, cellmin, NCELL);
+  if (tid < 64) emit_chunks(A, rk_run, a, m, m_plus, cellmin, NCELL);
   PT_STAMP(12);
 }
 
@@ -1558,7 +1631,7 @@ __device__ __forceinline__ void pair_sort_xl_body(const PairSortArgs& A, const u
     PT_STAMP(8);
   }
   if (A.check_degenerate && __any(degenerate) && (tid & 63) == 0) atomicOr(&A.C->flags, PF_FALLBACK);
-  if (tid == 0) emit_chunks(A, rk_run, a, m, m_plus, cellmin, (int)PAIR_XL_CELLS);
+  if (tid < 64) emit_chunks(A, rk_run, a, m, m_plus, cellmin, (int)PAIR_XL_CELLS);
   PT_STAMP(9);
 }
 
@@ -1567,6 +1640,14 @@ __global__ __launch_bounds__(NT) void pair_sort_kernel(PairSortArgs A) {
   __shared__ __attribute__((aligned(16))) char raw[pair_sort_lds_bytes<NT, ES, ER, NBK, NBIN, PERM>()];
   pair_sort_body<NT, ES, ER, NBK, NBIN, PERM>(A, A.list[blockIdx.x], raw);
 }
+// The 512-thread instance (pair_sort_mx): two work-groups share a CU only inside the register budget of 4 waves per SIMD, which
+// the launch bounds of half a CU's threads do not ask for by themselves -- this instance alone carries the attribute.
+template <>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void pair_sort_kernel<512, 16, 32, 2048, 1024, false>(PairSortArgs A) {
+  __shared__ __attribute__((aligned(16))) char raw[pair_sort_lds_bytes<512, 16, 32, 2048, 1024, false>()];
+  pair_sort_body<512, 16, 32, 2048, 1024, false>(A, A.list[blockIdx.x], raw);
+}
+static_assert(2 * pair_sort_lds_bytes<512, 16, 32, 2048, 1024, false>() <= 160 * 1024, "two work-groups in the LDS of a CU");
 // The two largest size classes in one launch: the few very long runs first (they last longest), the others fill the chip
 // beside them (launched on their own the long runs keep a handful of CUs busy and the rest of the chip waits).
 constexpr size_t PAIR_BIG_LDS = pair_sort_lds_bytes<1024, 16, 32, 4096, 1024, false>() > pair_sort_xl_lds_bytes<1024, 8, 4096>()
@@ -2713,6 +2794,31 @@ namespace {
 
 // The pairs of the input: runs of equal (q_id, t_id) (large inputs, grouped by pair as an aligner writes them), or through a
 // hash table (small inputs, grouped or not).  valid = 0: the pair-resident stage does not apply.
+// The longest pair that pair_sort gives to its 512-thread instance: a multiple of ORDER_BIN_L (pair_order's cut falls between two
+// length bins), at most what the instance holds; 0: no such launch.  SWG_PAIR_MX_MAX overrides it (experiments): a whole number
+// from 0 to PAIR_MX_MAX, rounded down to a bin boundary; anything else is said on stderr and not taken.  Beyond the instance's
+// batch of 8,192 members a pair takes several batches, and one whose coarse bin is denser than a batch gives the call to the
+// global-sort stage where the large body's batch of 16,384 would have held it: the default stays at one batch.
+static_assert(PAIR_MX_MAX == 512 * 32 && PAIR_MX_MAX % ORDER_BIN_L == 0 && PAIR_MX_CUT_DEFAULT % ORDER_BIN_L == 0 && PAIR_MX_CUT_DEFAULT <= 512 * 16,
+              "NT x ER of pair_sort_mx; the default inside its NT x ES");
+static uint32_t pair_mx_cut() {
+  static const uint32_t cut = [] {
+    const char* e = getenv("SWG_PAIR_MX_MAX");
+    if (!e) return PAIR_MX_CUT_DEFAULT;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end == e || *end != '\0' || v < 0 || v > (long)PAIR_MX_MAX) {
+      fprintf(stderr, "[swg] SWG_PAIR_MX_MAX=%s is not a number from 0 to %u: the default of %u is used\n", e, PAIR_MX_MAX, PAIR_MX_CUT_DEFAULT);
+      return PAIR_MX_CUT_DEFAULT;
+    }
+    const uint32_t c = (uint32_t)v / ORDER_BIN_L * ORDER_BIN_L;
+    const uint32_t cut = c > PAIR_M_MAX ? c : 0u;
+    if (getenv("SWG_DEBUG")) fprintf(stderr, "[swg] SWG_PAIR_MX_MAX=%s: pair_sort_mx takes pairs of up to %u records\n", e, cut);
+    return cut;
+  }();
+  return cut;
+}
+
 int pair_plan(swg_ctx* ctx, const swg_records* r, const swg_config* cfg, PairPlan* plan) {
   *plan = PairPlan{};
   if (!pair_path_wanted()) return SWG_OK;
@@ -2790,13 +2896,13 @@ int pair_plan(swg_ctx* ctx, const swg_records* r, const swg_config* cfg, PairPla
     SWG_LAUNCH(ctx, "pair_runs", pair_runs_kernel<<<(cap + 255) / 256, 256, 0, st>>>(n, cap, d_nr, starts, r->q_id, r->t_id, table, tsize - 1, runs, class_list, C));
     SWG_KERNEL_CHECK(ctx);
     if (order_knob && n > PAIR_M_MAX) {  // (no pair of the two largest classes otherwise)
-      SWG_LAUNCH(ctx, "pair_order", pair_order_kernel<<<2, ORDER_NT, 0, st>>>(runs, class_list, cap, order_tmp, cap_tmp, C));
+      SWG_LAUNCH(ctx, "pair_order", pair_order_kernel<<<2, ORDER_NT, 0, st>>>(runs, class_list, cap, order_tmp, cap_tmp, pair_mx_cut(), C));
       SWG_KERNEL_CHECK(ctx);
     }
   }
   uint64_t h[4];
-  static_assert(sizeof(PairCounters) >= 32, "the first four words are read back");
-  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<const uint64_t*>(C), h, 3));
+  static_assert(offsetof(PairCounters, n_above) == 24, "the first four words are read back: the counts and pair_order's cut");
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<const uint64_t*>(C), h, 4));
   const uint32_t n_runs = (uint32_t)h[0], flags = (uint32_t)(h[0] >> 32);
   if (flags || n_runs == 0) {
     if (dbg) fprintf(stderr, "[swg] pair path: not applicable (%u runs, flags %u)\n", n_runs, flags);
@@ -2818,6 +2924,12 @@ int pair_plan(swg_ctx* ctx, const swg_records* r, const swg_config* cfg, PairPla
   plan->ncls[1] = (uint32_t)(h[1] >> 32);
   plan->ncls[2] = (uint32_t)h[2];
   plan->ncls[3] = (uint32_t)(h[2] >> 32);
+  // pair_order's word: the ORDERED bit says that list 2 is in its order and where the pairs of at most `cut` records begin
+  const uint32_t above = (uint32_t)h[3];
+  if (pair_mx_cut() && (above & ORDERED) && (above & ~ORDERED) <= plan->ncls[2]) {
+    plan->cut = pair_mx_cut();
+    plan->n_above = above & ~ORDERED;
+  }
   plan->cap = cap;
   plan->counters = C;
   plan->runs = runs;
@@ -2933,9 +3045,18 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
       SWG_KERNEL_CHECK(ctx);
     }
   } else {
-    if (ncls[2] + ncls[3]) {  // the longest pairs first: their chunks open the list the walk's work-groups draw from
+    // List 2 in two launches when pair_order has cut it: its first n_above pairs (more than `cut` records) and the very long
+    // pairs under the 1,024-thread bodies, the others under the 512-thread instance, two work-groups to a CU.
+    const uint32_t n_above = plan_in->cut ? plan_in->n_above : ncls[2], n_mx = ncls[2] - n_above;
+    if (dbg && ncls[2]) fprintf(stderr, "[swg] pair_sort: %u pairs under pair_sort_big, %u under pair_sort_mx (cut %u)\n", n_above + ncls[3], n_mx, plan_in->cut);
+    if (n_above + ncls[3]) {  // the longest pairs first: their chunks open the list the walk's work-groups draw from
       SA.list = class_list + (size_t)2 * cap;
-      SWG_LAUNCH_N(ctx, "pair_sort_big", 0, pair_sort_big_kernel<<<ncls[2] + ncls[3], 1024, 0, st>>>(SA, class_list + (size_t)3 * cap, ncls[3]));
+      SWG_LAUNCH_N(ctx, "pair_sort_big", 0, pair_sort_big_kernel<<<n_above + ncls[3], 1024, 0, st>>>(SA, class_list + (size_t)3 * cap, ncls[3]));
+      SWG_KERNEL_CHECK(ctx);
+    }
+    if (n_mx) {
+      SA.list = class_list + (size_t)2 * cap + n_above;
+      SWG_LAUNCH_N(ctx, "pair_sort_mx", 0, pair_sort_kernel<512, 16, 32, 2048, 1024, false><<<n_mx, 512, 0, st>>>(SA));
       SWG_KERNEL_CHECK(ctx);
     }
     for (int c = 1; c >= 0; --c) {
@@ -3167,9 +3288,9 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   // ---- the flags found on the device, and the statistics
   SWG_LAUNCH(ctx, "pair_totals", pair_totals_kernel<<<(n_runs + 4095) / 4096 < 64u ? (n_runs + 4095) / 4096 : 64u, 1024, 0, st>>>(n_runs, info, sum, n_out_pair, C));
   SWG_KERNEL_CHECK(ctx);
-  uint64_t hc[9];
-  static_assert(sizeof(PairCounters) == 72, "PairCounters is read back as nine words");
-  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<const uint64_t*>(C), hc, 9));
+  uint64_t hc[10];
+  static_assert(sizeof(PairCounters) == 80 && offsetof(PairCounters, n_alive) == 40, "PairCounters is read back as ten words");
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<const uint64_t*>(C), hc, 10));
   const uint32_t flags2 = (uint32_t)(hc[0] >> 32);
   if (flags2) {
     if (dbg) fprintf(stderr, "[swg] pair path: left on the device's word (flags %u): the global-sort path takes the call\n", flags2);
@@ -3193,11 +3314,11 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   }
 #endif
   if (stats) {
-    stats->n_retained = hc[4];
-    stats->n_swept = hc[5];
-    stats->n_chains = hc[6];
-    stats->n_chains_kept = hc[7];
-    stats->n_out = hc[8];
+    stats->n_retained = hc[5];
+    stats->n_swept = hc[6];
+    stats->n_chains = hc[7];
+    stats->n_chains_kept = hc[8];
+    stats->n_out = hc[9];
   }
   *taken = 1;
   return SWG_OK;

@@ -253,6 +253,8 @@ struct PairPlan {
   int valid = 0;
   bool by_hash = false;
   uint32_t n_runs = 0, ncls[4] = {0, 0, 0, 0}, cap = 0;
+  uint32_t n_above = 0, cut = 0;   // cut != 0: list 2 is ordered, its first n_above pairs are the ones of more than `cut` records
+                                   //   (pair_sort sorts the others under its 512-thread instance, pair_sort_mx)
   void *counters = nullptr, *runs = nullptr, *class_list = nullptr, *perm = nullptr;
   bool not_grouped = false;        // why a plan over the runs of a large input is not valid: a pair has two runs, or there are more
                                    //   runs than pairs the path takes (both: what a grouping of the records by pair would cure)

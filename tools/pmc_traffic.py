@@ -34,7 +34,7 @@ def short_name(name):
     if base == "os_pass_packed" and len(t) >= 2 and t[1] == "true":
         base = "os_pass_packed_first"  # the pass that reads (key, value) pairs and writes packed words
     if base == "pair_sort" and t:      # pair_sort_kernel<NT, ES, ER, NBK, NBIN, PERM>: by size class, PERM = through the hash grouping
-        base = "pair_sort_" + ("p" if t[-1] == "true" else "") + {"64": "s", "256": "m", "1024": "l"}.get(t[0], t[0])
+        base = "pair_sort_" + ("p" if t[-1] == "true" else "") + {"64": "s", "256": "m", "512": "mx", "1024": "l"}.get(t[0], t[0])
     if base in ("pair_finish", "pair_chains") and t:    # <NT, ...>: 64 / 256 = the small size classes
         base += {"64": "_s", "256": "_m"}.get(t[0], "")
     if base in ("pair_key1", "pair_key2", "pair_rank1", "pair_rank_count", "pair_base", "pair_base_count", "pair_sizes", "pair_number_small"):
