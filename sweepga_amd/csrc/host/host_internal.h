@@ -3,12 +3,32 @@
 #define SWG_HOST_INTERNAL_H
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 
 // open_paf_input (src/paf.rs:10-30): the whole input as text -- mmap for plain files, parallel BGZF / serial gzip
 // inflate for .gz/.bgz (or the gzip magic), "-" = stdin.  *handle owns the bytes until swg_host_text_release.
 // Errors: negative code, text in swg_paf_last_error().
 int swg_host_text_load(const char* path, int threads, const char** data, size_t* len, void** handle);
 void swg_host_text_release(void* handle);
+
+// ---- the report writers' text helpers ----
+inline void append_u64(std::string& o, uint64_t v, char sep) {  // v in decimal, then sep; no allocation of its own
+  char buf[24];
+  int k = 24;
+  do buf[--k] = (char)('0' + v % 10); while (v /= 10);
+  o.append(buf + k, 24 - k);
+  o += sep;
+}
+// a text as the C ABI hands it out: malloc'd, NUL-terminated; nullptr = out of host memory
+inline char* text_copy(const std::string& o) {
+  char* t = static_cast<char*>(std::malloc(o.size() + 1));
+  if (!t) return nullptr;
+  std::memcpy(t, o.data(), o.size());
+  t[o.size()] = 0;
+  return t;
+}
 
 struct swg_ctx;
 struct swg_fasta;

@@ -76,19 +76,6 @@ int parse_bed(const char* who, const char* bed, uint64_t len, const std::unorder
   return SWG_OK;
 }
 
-char* text_copy(const std::string& o) {
-  char* t = static_cast<char*>(std::malloc(o.size() + 1));
-  if (!t) return nullptr;
-  std::memcpy(t, o.data(), o.size());
-  t[o.size()] = 0;
-  return t;
-}
-
-void append_u64(std::string& o, uint64_t v, char sep) {
-  o += std::to_string(v);
-  o += sep;
-}
-
 }  // namespace
 
 extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,

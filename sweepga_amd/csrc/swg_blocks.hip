@@ -14,7 +14,8 @@
 //   (sort)          swg_radix_sort_pairs over the 32 + bits(C + 1) key bits.
 //   blocks_gather   swg_union_tiles.h: the ends in sorted order and the tile maxima of chain << 32 | end.
 //   (scan)          swg_inclusive_max_scan_u64 over the tile maxima: the carry across work-groups, with no wait inside a launch.
-//   blocks_union    the tile again: running maximum before each record (0 when it belongs to an earlier chain), contribution =
+//   blocks_union    the tile again: running maximum before each record (running_max_before; 0 when it belongs to an earlier
+//                   chain), contribution =
 //                   max(0, end - max(start, running maximum)), folded like blocks_reduce -- the sorted order puts a chain's
 //                   records side by side -- and added to the row's cover of the axis.
 //   blocks_collect  the occupied rows as swg_block (the strand is chosen here); a chain over two sequence pairs or without a
@@ -36,7 +37,7 @@
 namespace {
 
 using namespace swg_pair_table;   // TB, WAVES, run_end, run_sum, wave_place, reserve_first
-using namespace swg_union_tiles;  // the tile of the sorted order and its first pass
+using namespace swg_union_tiles;  // the tile of the sorted order, its first pass and the running maximum
 
 // a row's 32-bit words; *_NMIN hold the complement of a minimum
 enum { W_QS_NMIN = 0, W_QE_MAX, W_TS_NMIN, W_TE_MAX, W_COUNT, W_FIRST_NMIN, W_STRAND = 6 /* words per strand */,
@@ -248,33 +249,23 @@ __global__ __launch_bounds__(TB) void blocks_gather_kernel(uint64_t n, const uin
 __global__ __launch_bounds__(TB) void blocks_union_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                           const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
                                                           uint32_t sentinel, BlockTable T, int cover) {
-  __shared__ unsigned long long l_wave[WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ unsigned long long l_wave[1][WAVES];
+  const int lane = threadIdx.x & 63;
   const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
   uint64_t k[ITEMS];
   uint32_t v[ITEMS], e[ITEMS];
   load_tile(keys, vals, n, p0, k, v);
   load_ends(ends, n, p0, e);
   bool counted[ITEMS];
-  unsigned long long mine = 0;
+  unsigned long long mine[1] = {0};
 #pragma unroll
   for (int j = 0; j < ITEMS; ++j) {
     counted[j] = p0 + j < n && (uint32_t)(k[j] >> 32) != sentinel;
-    if (counted[j]) mine = max64(mine, (k[j] & 0xffffffff00000000ull) | e[j]);
+    if (counted[j]) mine[0] = max64(mine[0], (k[j] & 0xffffffff00000000ull) | e[j]);
   }
-  // running maximum over the threads before this one: wavefront, work-group, tiles before
-  unsigned long long incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long o = __shfl_up(incl, d);
-    if (lane >= d) incl = max64(incl, o);
-  }
-  if (lane == 63) l_wave[wave] = incl;
-  __syncthreads();
-  unsigned long long r = __shfl_up(incl, 1);
-  if (lane == 0) r = 0;
-  for (int w = 0; w < wave; ++w) r = max64(r, l_wave[w]);
-  if (blockIdx.x > 0) r = max64(r, carry[blockIdx.x - 1]);
+  unsigned long long front[1];
+  running_max_before<1>(mine, l_wave, carry, 0, 1u, front);  // (one set: no second row of tile maxima, ntiles is not read)
+  unsigned long long r = front[0];
   // contributions, folded along the thread and then along the lanes
   uint32_t run_chain = 0;
   unsigned long long run[1] = {0};

@@ -18,8 +18,9 @@
 //                    (one long interval over 10^6 short ones is 1000 tiles of carry).
 //   breadth_union    the same tile again: carry-in = scanned maximum of the tile before, running maximum across the threads
 //                    of the work-group (four consecutive records per thread, wavefront scan by shuffles, four wavefronts
-//                    through LDS), contribution = max(0, end - max(start, running maximum before)) with the maximum taken
-//                    as 0 when it belongs to an earlier segment.  ALL and KEPT are two maxima in the same pass.  bases, union
+//                    through LDS: running_max_before of swg_union_tiles.h), contribution = max(0, end - max(start, running
+//                    maximum before)) with the maximum taken as 0 when it belongs to an earlier segment.  ALL and KEPT are two
+//                    maxima in the same pass.  bases, union
 //                    and the smallest record index go per genome pair through the run / LDS-table / global-table scheme of
 //                    swg_pair_table.h: one atomic per (work-group, pair, quantity).
 //   breadth_collect  the occupied pairs as lists (the host orders them by first record).
@@ -41,7 +42,7 @@
 namespace {
 
 using namespace swg_pair_table;   // the genome-pair table, the run and wavefront helpers, the host entry helpers
-using namespace swg_union_tiles;  // the tile of the sorted order and its first pass, the segment map and its keys
+using namespace swg_union_tiles;  // the tile of the sorted order, its first pass and running maximum, the segment map, the front end
 enum { D_BAD = 0, D_SEGMENTS, D_LISTED, D_LISTED_KEPT, D_TOTAL };
 enum { Q_BASES = 0, Q_UNION, T_BASES, T_UNION, Q_COUNT };  // a listed entry's sums
 
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(TB) void breadth_keys_kernel(uint64_t n, const uint
   segment_keys<AXIS>(n, q_id, t_id, start, status, seq_genome, n_seq, M, keys, vals, &scalars[D_BAD]);
 }
 
-// ---- one tile of the sorted order (load_tile, gather_tile: swg_union_tiles.h) ---------------------------------------------
+// ---- one tile of the sorted order (load_tile, gather_tile, running_max_before: swg_union_tiles.h) ---------------------------------------------
 __global__ __launch_bounds__(TB) void breadth_gather_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             const uint32_t* __restrict__ end_col, uint32_t sentinel,
                                                             uint32_t* __restrict__ ends, unsigned long long* __restrict__ tile_max,
@@ -68,7 +69,8 @@ __global__ __launch_bounds__(TB) void breadth_gather_kernel(uint64_t n, const ui
 template <int AXIS>
 __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                            const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
-                                                           uint64_t ntiles, SegMap M, const uint32_t* __restrict__ seq_genome, BreadthTable T) {
+                                                           uint64_t ntiles, uint32_t scanned, SegMap M, const uint32_t* __restrict__ seq_genome,
+                                                           BreadthTable T) {
   __shared__ LdsTable<4, AXIS == 0> l_pairs;  // (first records: the query axis writes them, the target axis leaves them alone)
   __shared__ unsigned long long l_wave[2][WAVES];
   l_pairs.clear();
@@ -79,29 +81,19 @@ __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uin
   load_tile(keys, vals, n, p0, k, v);
   load_ends(ends, n, p0, e);
   bool counted[ITEMS];
-  unsigned long long t_all = 0, t_kept = 0;
+  unsigned long long t_max[2] = {0, 0};  // ALL, KEPT
 #pragma unroll
   for (int j = 0; j < ITEMS; ++j) {
     counted[j] = p0 + j < n && (uint32_t)(k[j] >> 32) != M.sentinel;
     if (counted[j]) {
       const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
-      t_all = max64(t_all, P);
-      if (v[j] & KEPT_FLAG) t_kept = max64(t_kept, P);
+      t_max[0] = max64(t_max[0], P);
+      if (v[j] & KEPT_FLAG) t_max[1] = max64(t_max[1], P);
     }
   }
-  // running maximum over the threads before this one: wavefront, work-group, tiles before
-  unsigned long long i_all = t_all, i_kept = t_kept;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long a = __shfl_up(i_all, d), b = __shfl_up(i_kept, d);
-    if (lane >= d) i_all = max64(i_all, a), i_kept = max64(i_kept, b);
-  }
-  if (lane == 63) l_wave[0][wave] = i_all, l_wave[1][wave] = i_kept;
-  __syncthreads();  // (also: the LDS table is ready)
-  unsigned long long r_all = __shfl_up(i_all, 1), r_kept = __shfl_up(i_kept, 1);
-  if (lane == 0) r_all = r_kept = 0;
-  for (int w = 0; w < wave; ++w) r_all = max64(r_all, l_wave[0][w]), r_kept = max64(r_kept, l_wave[1][w]);
-  if (blockIdx.x > 0) r_all = max64(r_all, carry[blockIdx.x - 1]), r_kept = max64(r_kept, carry[ntiles + blockIdx.x - 1]);
+  unsigned long long r[2];
+  running_max_before<2>(t_max, l_wave, carry, ntiles, scanned, r);  // (its barrier also: the LDS table is ready)
+  unsigned long long r_all = r[0], r_kept = r[1];
   // contributions
   unsigned long long q[ITEMS][4];  // bases ALL, union ALL, bases KEPT, union KEPT
   uint32_t f_all[ITEMS], f_kept[ITEMS];
@@ -150,14 +142,8 @@ __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uin
     if (__ballot(head[j]) == 0) continue;  // wavefront-uniform (rounds 1..3: only where a segment starts inside a thread)
     unsigned long long key = EMPTY;
     if (head[j]) {
-      const uint32_t seg = (uint32_t)(k[j] >> 32);
       uint32_t seq, other;
-      if (M.set_keys) {
-        const unsigned long long product = M.set_keys[seg];
-        seq = (uint32_t)(product / M.G), other = (uint32_t)(product % M.G);
-      } else {
-        seq = seg / M.G, other = seg % M.G;
-      }
+      segment_of(M, (uint32_t)(k[j] >> 32), &seq, &other);
       const uint32_t mine = seq_genome[seq];
       key = AXIS ? (unsigned long long)other * M.G + mine : (unsigned long long)mine * M.G + other;
     }
@@ -185,13 +171,8 @@ __global__ __launch_bounds__(TB) void breadth_union_kernel(uint64_t n, const uin
 // ---- the occupied genome pairs as lists ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TB) void breadth_collect_kernel(BreadthTable T, BreadthList L) { list_slots(T, L); }
 
-struct DevCols {
-  const uint32_t *q_id, *t_id, *start[2], *end[2], *seq_genome;
-  const uint8_t* status;
-};
-
 // inside an arena frame
-int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_breadth_result* all, swg_breadth_result* kept) {
+int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const SegCols& d, swg_breadth_result* all, swg_breadth_result* kept) {
   hipStream_t st = ctx->stream;
   const bool force_hash = segmap_forced();  // test knob: the hashed segment set and pair table at any size
   const uint64_t ntiles = (n + TILE - 1) / TILE;
@@ -208,6 +189,7 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
   SWG_HIP(ctx, hipMemsetAsync(scalars, 0, D_TOTAL * sizeof(unsigned long long), st));
   const int end_bit = 32 + swg_bits_for(M.sentinel);
   const unsigned grid_n = (unsigned)((n + TB - 1) / TB), grid_t = (unsigned)ntiles;
+  const uint32_t scanned = d.status ? 3u : 1u;  // (no status: nothing is KEPT, and the KEPT maxima are not scanned)
   BreadthTable T{};
   BreadthList L{};
   for (int axis = 0; axis < 2; ++axis) {
@@ -238,9 +220,11 @@ int breadth_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
     if (d.status)
       SWG_TRY(swg_inclusive_max_scan_u64(ctx, reinterpret_cast<uint64_t*>(tile_max + ntiles), reinterpret_cast<uint64_t*>(tile_max + ntiles), ntiles));
     if (axis == 0)
-      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<0><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, d.seq_genome, T));
+      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<0><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, scanned, M,
+                                                                                       d.seq_genome, T));
     else
-      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<1><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, d.seq_genome, T));
+      SWG_LAUNCH(ctx, "breadth_union", breadth_union_kernel<1><<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, scanned, M,
+                                                                                       d.seq_genome, T));
     SWG_KERNEL_CHECK(ctx);
   }
   SWG_LAUNCH(ctx, "breadth_collect", breadth_collect_kernel<<<(unsigned)((T.slots + TB - 1) / TB), TB, 0, st>>>(T, L));
@@ -288,27 +272,16 @@ int swg_breadth_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const 
   if (!ctx) return SWG_ERR_INVALID;
   if (!rec) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: NULL records");
   const uint64_t n = rec->n;
-  const uint32_t n_seq = rec->n_seq;
   if (all) all->pairs.clear();
   if (kept) kept->pairs.clear();
   if (n == 0) return SWG_OK;
-  if (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->t_start || !rec->t_end || !seq_genome)
-    return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: NULL column (q_id, t_id, the four coordinates and seq_genome are read)");
-  if (n_seq == 0 || n_genome == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "breadth: records without sequences or genomes");
-  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: 2^31 records or more in one call");
-  if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "breadth: more than 2^31 sequences");
+  SWG_TRY(seg_check_args(ctx, "breadth", ARG_COLUMNS | ARG_COUNTS | ARG_LIMIT, rec, seq_genome, n_genome, 31));
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * 64 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
-    DevCols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, status};
-    if (!on_device) {
-      const uint32_t* col[6];
-      uint8_t* s8;
-      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end}, seq_genome,
-                            status != nullptr, status, col, &d.seq_genome, &s8));
-      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, d.seq_genome, s8};
-    }
-    return breadth_device(ctx, n, n_seq, n_genome, d, all, kept);
+    SegCols d;
+    SWG_TRY(seg_stage(ctx, rec, on_device, seq_genome, status, &d));
+    return breadth_device(ctx, n, rec->n_seq, n_genome, d, all, kept);
   });
 }
 

@@ -407,11 +407,6 @@ int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   }
 }
 
-void append_u64(std::string& o, uint64_t v, char sep) {
-  o += std::to_string(v);
-  o += sep;
-}
-
 }  // namespace
 
 int swg_components_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_len, const uint8_t* status,

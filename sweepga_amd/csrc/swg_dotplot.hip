@@ -327,14 +327,6 @@ void layout_rows(const swg_paf* p, const std::vector<std::string>& gname, const 
   }
 }
 
-char* text_copy(const std::string& o) {
-  char* t = static_cast<char*>(std::malloc(o.size() + 1));
-  if (!t) return nullptr;
-  std::memcpy(t, o.data(), o.size());
-  t[o.size()] = 0;
-  return t;
-}
-
 }  // namespace
 
 extern "C" int swg_dotplot_records(swg_ctx* ctx, const swg_records* rec, const swg_dot_axes* axes, const uint8_t* status, swg_dot_request* req) {

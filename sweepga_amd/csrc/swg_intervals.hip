@@ -4,7 +4,8 @@
 //   ALL   the union of [start, end) over the counted records          KEPT  the same over the records with status != 0
 //   LOST  ALL minus KEPT: covered before the filter, by nothing after it
 //
-// each ordered by (sequence, genome of the other side, start).  Keys, sort and tile walk are breadth's (swg_union_tiles.h):
+// each ordered by (sequence, genome of the other side, start).  Keys, sort, the tile walk and the head rule are shared
+// (swg_union_tiles.h: segment_keys, gather_tile, running_max_before, heads_tile); this file holds what a head writes (RowsOut):
 //
 //   intervals_keys        key = segment << 32 | start, value = record index | KEPT_FLAG (segment_keys)
 //   (sort)                swg_radix_sort_pairs
@@ -13,13 +14,13 @@
 //                         record raise the maximum, because it only sums; here an empty record at p would make an interval that
 //                         really begins at p after a gap look like a continuation and glue it to the interval before the gap.
 //   (scan)                swg_inclusive_max_scan_u64 over the tile maxima: the carry, however far it reaches
-//   intervals_count       the tile again.  Running maximum before each record (wavefront shuffles, wavefronts through LDS,
+//   intervals_count       the tile again (heads_tile<false>).  Running maximum before each record (wavefront shuffles, wavefronts through LDS,
 //                         carry-in from the scan).  A counted record of non-zero length is a HEAD of its set when nothing of the
 //                         set came before, or the maximum before it belongs to an earlier segment, or start > that maximum's
 //                         end (strictly: touching intervals join).  Heads per tile and set.
 //   (scan)                swg_exclusive_scan_u32 over the tile counts; the totals are the lists' n.  One read-back sizes the rows.
-//   intervals_write       the tile a third time.  The head of rank r writes row[r].{seq, other_genome, start} and, if r > 0,
-//                         row[r - 1].end = the low half of the running maximum before it: the maximum of P over a prefix
+//   intervals_write       the tile a third time (heads_tile<true> with RowsOut).  The head of rank r writes
+//                         row[r].{seq, other_genome, start} and, if r > 0, row[r - 1].end = the low half of the running maximum before it: the maximum of P over a prefix
 //                         belongs to the last segment the set touched, so it IS the previous interval's end, also when that
 //                         interval lies in another segment.  The last row's end is the low half of the last tile's scanned
 //                         maximum.  No look-ahead, no atomics, no neighbour's state.  Launched only for an axis and sets whose
@@ -32,14 +33,13 @@
 //   intervals_lost_write  rank of a leading piece = leading pieces of the A rows before it + trailing pieces of the K rows
 //                         before its first K; of a trailing piece = leading pieces up to its A + trailing pieces before it.
 //                         Scattered by rank: exact order, no atomics.
-//   intervals_bases       sum(end - start) over a row list: work-group reduction, one atomic per work-group.
+//   intervals_bases       sum(end - start) over a row list: work-group reduction, one atomic per work-group (bases_sum).
 //
 // No work-group waits for another inside a launch (no look-back, no flag): every carry goes through the library's scans
 // between launches.  With the hashed segment set (beyond 2^32 products; SWG_BREADTH_HASH=1) segments are hash slots and the
 // device order is by slot: the host then orders whole segment runs by (sequence, genome) with a stable sort -- the rows of a
 // run are in start order already.  Integer atomics only; no floating point.
 #include <algorithm>
-#include <cstring>
 #include <new>
 #include <string>
 
@@ -72,136 +72,32 @@ __global__ __launch_bounds__(TB) void intervals_gather_kernel(uint64_t n, const 
   gather_tile<true, true>(n, keys, vals, end_col, sentinel, ends, tile_max, ntiles, nullptr);
 }
 
-struct RowsOut {           // the write pass' destinations, per set (ALL, KEPT)
+struct RowsOut {           // the write pass' emitter (heads_tile, swg_union_tiles.h): the rows per set (ALL, KEPT)
+  SegMap M;
   swg_interval* rows[2];   // [total[s]]
   uint64_t* keys[2];       // [total[s]] segment << 32 | start of every row, or nullptr (only the LOST stage reads them)
   uint32_t total[2];
+  // the head of rank `at` begins row at and closes row at - 1 at the low half of the maximum in front of it
+  __device__ __forceinline__ void head(int s, uint32_t at, uint64_t key, unsigned long long prev) const {
+    swg_interval* row = rows[s] + at;
+    segment_of(M, (uint32_t)(key >> 32), &row->seq, &row->other_genome);
+    row->start = (uint32_t)key;
+    if (at > 0) row[-1].end = (uint32_t)prev;
+    if (keys[s]) keys[s][at] = key;
+  }
+  __device__ __forceinline__ void last(int s, unsigned long long max_p) const { rows[s][total[s] - 1].end = (uint32_t)max_p; }
 };
-
-// One tile of the sorted order: the heads of the sets in `sets`.  WRITE = false: their number per set into tile_cnt[s * ntiles +
-// tile].  WRITE = true: tile_cnt holds the exclusive scan of those numbers, and the heads write their rows.
-template <bool WRITE>
-__device__ __forceinline__ void heads_tile(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                           const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry, uint64_t ntiles,
-                                           const SegMap& M, uint32_t sets, uint32_t* __restrict__ tile_cnt, const RowsOut& out) {
-  __shared__ unsigned long long l_wave[2][WAVES];
-  __shared__ uint32_t l_cnt[2][WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
-  uint64_t k[ITEMS];
-  uint32_t v[ITEMS], e[ITEMS];
-  load_tile(keys, vals, n, p0, k, v);
-  load_ends(ends, n, p0, e);
-  bool live[ITEMS];  // counted and of non-zero length
-  unsigned long long t_max[2] = {0, 0};
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    live[j] = p0 + j < n && (uint32_t)(k[j] >> 32) != M.sentinel && e[j] > (uint32_t)k[j];
-    if (live[j]) {
-      const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
-      t_max[0] = max64(t_max[0], P);
-      if (v[j] & KEPT_FLAG) t_max[1] = max64(t_max[1], P);
-    }
-  }
-  // running maximum over the threads before this one: wavefront, work-group, tiles before
-  unsigned long long inc[2] = {t_max[0], t_max[1]};
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long a = __shfl_up(inc[0], d), b = __shfl_up(inc[1], d);
-    if (lane >= d) inc[0] = max64(inc[0], a), inc[1] = max64(inc[1], b);
-  }
-  if (lane == 63) l_wave[0][wave] = inc[0], l_wave[1][wave] = inc[1];
-  __syncthreads();
-  unsigned long long r[2] = {__shfl_up(inc[0], 1), __shfl_up(inc[1], 1)};
-  if (lane == 0) r[0] = r[1] = 0;
-  for (int w = 0; w < wave; ++w) r[0] = max64(r[0], l_wave[0][w]), r[1] = max64(r[1], l_wave[1][w]);
-  if (blockIdx.x > 0) {
-    r[0] = max64(r[0], carry[blockIdx.x - 1]);
-    if (sets & SET_KEPT) r[1] = max64(r[1], carry[ntiles + blockIdx.x - 1]);
-  }
-  // heads.  A maximum of 0 is "nothing of the set before": a live record has end >= 1, so its P is never 0.
-  uint32_t cnt[2] = {0, 0}, is_head[2] = {0, 0};
-  uint32_t prev_end[2][ITEMS];
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    prev_end[0][j] = prev_end[1][j] = 0;
-    if (!live[j]) continue;
-    const uint32_t seg = (uint32_t)(k[j] >> 32), start = (uint32_t)k[j];
-    const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (!(sets >> s & 1u) || (s == 1 && !(v[j] & KEPT_FLAG))) continue;
-      if (r[s] == 0 || (uint32_t)(r[s] >> 32) != seg || start > (uint32_t)r[s]) {
-        ++cnt[s];
-        is_head[s] |= 1u << j;
-        prev_end[s][j] = (uint32_t)r[s];
-      }
-      r[s] = max64(r[s], P);
-    }
-  }
-  if (!WRITE) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const uint32_t c = (uint32_t)wave_sum(cnt[s]);
-      if (lane == 0) l_cnt[s][wave] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && (sets >> threadIdx.x & 1u)) {
-      uint32_t c = 0;
-      for (int w = 0; w < WAVES; ++w) c += l_cnt[threadIdx.x][w];
-      tile_cnt[threadIdx.x * ntiles + blockIdx.x] = c;
-    }
-    return;
-  }
-  // ranks: heads of the threads before this one, of the tiles before this one
-  uint32_t rank[2] = {cnt[0], cnt[1]};
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t a = __shfl_up(rank[0], d), b = __shfl_up(rank[1], d);
-    if (lane >= d) rank[0] += a, rank[1] += b;
-  }
-  if (lane == 63) l_cnt[0][wave] = rank[0], l_cnt[1][wave] = rank[1];
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    if (!(sets >> s & 1u)) continue;
-    uint32_t at = rank[s] - cnt[s] + tile_cnt[s * ntiles + blockIdx.x];
-    for (int w = 0; w < wave; ++w) at += l_cnt[s][w];
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      if (!(is_head[s] >> j & 1u)) continue;
-      if (at < out.total[s]) {  // (always: the count pass counted these heads)
-        const uint32_t seg = (uint32_t)(k[j] >> 32);
-        uint32_t seq, other;
-        if (M.set_keys) {
-          const unsigned long long product = M.set_keys[seg];
-          seq = (uint32_t)(product / M.G), other = (uint32_t)(product % M.G);
-        } else {
-          seq = seg / M.G, other = seg % M.G;
-        }
-        swg_interval* row = out.rows[s] + at;
-        row->seq = seq, row->other_genome = other, row->start = (uint32_t)k[j];
-        if (at > 0) row[-1].end = prev_end[s][j];
-        if (out.keys[s]) out.keys[s][at] = k[j];
-      }
-      ++at;
-    }
-    // the last row's end: the maximum over everything
-    if (blockIdx.x == ntiles - 1 && threadIdx.x == 0 && out.total[s] > 0)
-      out.rows[s][out.total[s] - 1].end = (uint32_t)carry[s * ntiles + ntiles - 1];
-  }
-}
 
 __global__ __launch_bounds__(TB) void intervals_count_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                              const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
                                                              uint64_t ntiles, SegMap M, uint32_t sets, uint32_t* __restrict__ tile_cnt) {
-  heads_tile<false>(n, keys, vals, ends, carry, ntiles, M, sets, tile_cnt, RowsOut{});
+  heads_tile<false>(n, keys, vals, ends, carry, ntiles, M.sentinel, sets, tile_cnt, RowsOut{});
 }
 
 __global__ __launch_bounds__(TB) void intervals_write_kernel(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                              const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
-                                                             uint64_t ntiles, SegMap M, uint32_t sets, uint32_t* __restrict__ tile_off, RowsOut out) {
-  heads_tile<true>(n, keys, vals, ends, carry, ntiles, M, sets, tile_off, out);
+                                                             uint64_t ntiles, uint32_t sets, uint32_t* __restrict__ tile_off, RowsOut out) {
+  heads_tile<true>(n, keys, vals, ends, carry, ntiles, out.M.sentinel, sets, tile_off, out);
 }
 
 // ---- LOST = ALL minus KEPT over the two row lists ---------------------------------------------------------------------------
@@ -276,40 +172,17 @@ __global__ __launch_bounds__(TB) void intervals_lost_write_kernel(LostArgs L, ui
 }
 
 __global__ __launch_bounds__(TB) void intervals_bases_kernel(const swg_interval* __restrict__ rows, uint64_t n_rows, unsigned long long* __restrict__ sum) {
-  __shared__ unsigned long long l_sum[WAVES];
-  unsigned long long s = 0;
-  for (uint64_t x = (uint64_t)blockIdx.x * TB + threadIdx.x; x < n_rows; x += (uint64_t)gridDim.x * TB) s += rows[x].end - rows[x].start;
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) l_sum[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < WAVES; ++w) t += l_sum[w];
-    if (t) atomicAdd(sum, t);
-  }
+  bases_sum(rows, n_rows, sum);
 }
 
-struct DevCols {
-  const uint32_t *q_id, *t_id, *start[2], *end[2], *seq_genome;
-  const uint8_t* status;
-};
-
-// a list's rows from the device to where the caller wants them: `vec` (internal callers), else list->rows when they fit
+// a list's n, bases and rows to the caller (rows_hand_over); the hashed set's rows into their order on the way
 int hand_over(swg_ctx* ctx, const swg_interval* d_rows, uint64_t n_rows, uint64_t bases, bool hashed, swg_interval_list* list,
               std::vector<swg_interval>* vec) {
   list->n = n_rows;
   list->bases = bases;
-  swg_interval* dst = nullptr;
-  if (vec) {
-    vec->resize(n_rows);
-    dst = vec->data();
-  } else if (list->rows && n_rows <= list->capacity) {
-    dst = list->rows;
-  }
-  if (!dst || !n_rows) return SWG_OK;
-  SWG_HIP(ctx, hipMemcpyAsync(dst, d_rows, n_rows * sizeof(swg_interval), hipMemcpyDeviceToHost, ctx->stream));
-  SWG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (hashed)  // the device order is by hash slot: whole segment runs into (sequence, genome) order, their rows stay in start order
+  swg_interval* dst;
+  SWG_TRY(rows_hand_over(ctx, d_rows, n_rows, vec, list->rows, list->capacity, &dst));
+  if (dst && hashed)  // the device order is by hash slot: whole segment runs into (sequence, genome) order, their rows stay in start order
     std::stable_sort(dst, dst + n_rows, [](const swg_interval& a, const swg_interval& b) {
       return a.seq != b.seq ? a.seq < b.seq : a.other_genome < b.other_genome;
     });
@@ -317,7 +190,7 @@ int hand_over(swg_ctx* ctx, const swg_interval* d_rows, uint64_t n_rows, uint64_
 }
 
 // inside an arena frame.  vecs: nullptr, or [3][2] vectors that receive the rows instead of req's arrays
-int intervals_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_interval_request* req,
+int intervals_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const SegCols& d, swg_interval_request* req,
                      std::vector<swg_interval> (*vecs)[2]) {
   hipStream_t st = ctx->stream;
   const bool force_hash = segmap_forced();
@@ -370,6 +243,7 @@ int intervals_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const
     if (h[D_BAD]) return swg_set_error(ctx, SWG_ERR_INVALID, "intervals: a sequence id >= n_seq or a genome id >= n_genome");
     const uint64_t* hx = h + D_AXIS + axis * A_COUNT;
     RowsOut out{};
+    out.M = M;
     for (int s = 0; s < 2; ++s) {
       if (!(sets >> s & 1u)) continue;
       out.total[s] = (uint32_t)hx[A_HEADS + s];  // (<= n < 2^31)
@@ -382,7 +256,7 @@ int intervals_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const
       L.link = swg_alloc<uint32_t>(ctx, (uint64_t)out.total[0] + out.total[1] + 1);
     }
     SWG_CHECK_ARENA(ctx);
-    SWG_LAUNCH(ctx, "intervals_write", intervals_write_kernel<<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, M, sets, tile_cnt, out));
+    SWG_LAUNCH(ctx, "intervals_write", intervals_write_kernel<<<grid_t, TB, 0, st>>>(n, keys, vals, ends, tile_max, ntiles, sets, tile_cnt, out));
     SWG_KERNEL_CHECK(ctx);
     swg_interval* lost_rows = nullptr;
     uint64_t n_lost = 0;
@@ -430,8 +304,7 @@ int intervals_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const ui
   if (!status && (req->want >> (2 * SWG_IV_KEPT)) != 0)
     return swg_set_error(ctx, SWG_ERR_INVALID, "intervals: the KEPT and LOST lists need a status column");
   const uint64_t n = rec->n;
-  const uint32_t n_seq = rec->n_seq;
-  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "intervals: 2^31 records or more in one call");
+  SWG_TRY(seg_check_args(ctx, "intervals", ARG_LIMIT, rec, seq_genome, n_genome, 31));
   for (int s = 0; s < 3; ++s)
     for (int axis = 0; axis < 2; ++axis)
       if (req->want >> (2 * s + axis) & 1u) {
@@ -439,22 +312,13 @@ int intervals_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const ui
         if (vecs) vecs[s][axis].clear();
       }
   if (n == 0) return SWG_OK;
-  if (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->t_start || !rec->t_end || !seq_genome)
-    return swg_set_error(ctx, SWG_ERR_INVALID, "intervals: NULL column (q_id, t_id, the four coordinates and seq_genome are read)");
-  if (n_seq == 0 || n_genome == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "intervals: records without sequences or genomes");
-  if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "intervals: more than 2^31 sequences");
+  SWG_TRY(seg_check_args(ctx, "intervals", ARG_COLUMNS | ARG_COUNTS, rec, seq_genome, n_genome, 31));
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * 64 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
-    DevCols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, status};
-    if (!on_device) {
-      const uint32_t* col[6];
-      uint8_t* s8;
-      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end}, seq_genome,
-                            status != nullptr, status, col, &d.seq_genome, &s8));
-      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, d.seq_genome, s8};
-    }
-    return intervals_device(ctx, n, n_seq, n_genome, d, req, vecs);
+    SegCols d;
+    SWG_TRY(seg_stage(ctx, rec, on_device, seq_genome, status, &d));
+    return intervals_device(ctx, n, rec->n_seq, n_genome, d, req, vecs);
   });
 }
 
@@ -465,14 +329,6 @@ int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   } catch (const std::bad_alloc&) {
     return swg_set_error(ctx, SWG_ERR_OOM, "out of host memory");
   }
-}
-
-void append_u64(std::string& o, uint64_t v, char sep) {
-  char buf[24];
-  int k = 24;
-  do buf[--k] = (char)('0' + v % 10); while (v /= 10);
-  o.append(buf + k, 24 - k);
-  o += sep;
 }
 
 }  // namespace
@@ -528,14 +384,12 @@ extern "C" int swg_paf_interval_texts(swg_ctx* ctx, const swg_paf* p, const uint
           o += gname[r.other_genome];
           o += axis ? "\tt\n" : "\tq\n";
         }
-      char* t = static_cast<char*>(std::malloc(o.size() + 1));
+      char* t = text_copy(o);
       if (!t) {
         for (int b = 0; b < s; ++b)
           if (sets >> b & 1u) std::free(out_text[b]), out_text[b] = nullptr, out_len[b] = 0;
         return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
       }
-      std::memcpy(t, o.data(), o.size());
-      t[o.size()] = 0;
       out_text[s] = t;
       out_len[s] = o.size();
     }

@@ -5,17 +5,19 @@
 //
 //   sharing_keys          every record gives two entries: (segment(q, genome(t)) << 32 | q_start) at i and (segment(t, genome(q))
 //                         << 32 | t_start) at n + i; value = record index | AXIS_FLAG | KEPT_FLAG.  Records that do not count get
-//                         the sentinel segment.  SegMap and the hashed set are breadth's (swg_union_tiles.h).
+//                         the sentinel segment.  SegMap and the hashed set: swg_union_tiles.h, as in breadth and intervals.
 //   (sort)                swg_radix_sort_pairs over the 2n entries
 //   sharing_gather        gather_tile<true, true, true>: end = (AXIS_FLAG ? t_end : q_end)[record] in sorted order and the tile
 //                         maxima of P = segment << 32 | end over the entries of non-zero length, ALL and KEPT
 //   (scan)                swg_inclusive_max_scan_u64 over the tile maxima of the sets asked for
-//   sharing_count         heads per tile and set, as intervals_count: an entry is a head when nothing of its set and segment came
-//                         before it or its start lies beyond the running maximum (touching intervals join)
+//   sharing_count         heads per tile and set: heads_tile<false> of swg_union_tiles.h, the walk of intervals_count.  An entry is
+//                         a head when nothing of its set and segment came before it or its start lies beyond the running maximum
+//                         (touching intervals join)
 //   (scan)                swg_exclusive_scan_u32 over the tile counts; the totals m are the merged intervals of each set.  Read back.
-//   sharing_events        the tile again: the head of rank r writes the event (seq << 32 | start, +1) at r and closes the interval
-//                         before it: (seq' << 32 | end', -1) at m + r - 1, seq' and end' from the running maximum in front of it.
-//                         The last interval is closed from the last tile's scanned maximum.
+//   sharing_events        the tile again, heads_tile<true> with this file's emitter EventsOut: the head of rank r writes the event
+//                         (seq << 32 | start, +1) at r and closes the interval before it: (seq' << 32 | end', -1) at m + r - 1, seq'
+//                         and end' from the running maximum in front of it.  The last interval is closed from the last tile's
+//                         scanned maximum.
 // then per set:
 //   (sort)                swg_radix_sort_pairs over the 2m events, 32 + bits(n_seq) key bits; the value is the delta
 //   (scan)                swg_exclusive_scan_u32 over the deltas: the depth in front of every event.  The sums wrap; the deltas of a
@@ -98,139 +100,35 @@ __global__ __launch_bounds__(TB) void sharing_gather_kernel(uint64_t n2, const u
   gather_tile<true, true, true>(n2, keys, vals, q_end, sentinel, ends, tile_max, ntiles, nullptr, t_end);
 }
 
-struct EventsOut {       // the write pass' destinations, per set (ALL, KEPT)
+struct EventsOut {       // the write pass' emitter (heads_tile, swg_union_tiles.h): the events per set (ALL, KEPT)
+  SegMap M;
   uint64_t* keys[2];     // [2 * total[s]]: seq << 32 | position; the begins at [0, total), the ends at [total, 2 * total)
   uint32_t* deltas[2];   // [2 * total[s]]: +1, -1
   uint32_t total[2];
+  __device__ __forceinline__ void event(int s, uint64_t at, unsigned long long p, uint32_t delta) const {  // p = segment << 32 | position
+    uint32_t seq, other;
+    segment_of(M, (uint32_t)(p >> 32), &seq, &other);
+    keys[s][at] = ((uint64_t)seq << 32) | (uint32_t)p;
+    deltas[s][at] = delta;
+  }
+  // the head of rank `at` is the begin event at and closes the interval at - 1: segment and end of the maximum in front of it
+  __device__ __forceinline__ void head(int s, uint32_t at, uint64_t key, unsigned long long prev) const {
+    event(s, at, key, 1u);
+    if (at > 0) event(s, (uint64_t)total[s] + at - 1, prev, ~0u);
+  }
+  __device__ __forceinline__ void last(int s, unsigned long long max_p) const { event(s, 2 * (uint64_t)total[s] - 1, max_p, ~0u); }
 };
-
-__device__ __forceinline__ uint32_t segment_seq(const SegMap& M, uint32_t seg) {
-  return M.set_keys ? (uint32_t)(M.set_keys[seg] / M.G) : seg / M.G;
-}
-
-// One tile of the sorted order: the heads of the sets in `sets` (the rule of intervals' heads_tile).  WRITE = false: their number
-// per set into tile_cnt[s * ntiles + tile].  WRITE = true: tile_cnt holds the exclusive scan of those numbers; the head of rank r
-// writes the begin event r and the end event of the interval r - 1.
-template <bool WRITE>
-__device__ __forceinline__ void heads_tile(uint64_t n2, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                           const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry, uint64_t ntiles,
-                                           const SegMap& M, uint32_t sets, uint32_t* __restrict__ tile_cnt, const EventsOut& out) {
-  __shared__ unsigned long long l_wave[2][WAVES];
-  __shared__ uint32_t l_cnt[2][WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t p0 = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
-  uint64_t k[ITEMS];
-  uint32_t v[ITEMS], e[ITEMS];
-  load_tile(keys, vals, n2, p0, k, v);
-  load_ends(ends, n2, p0, e);
-  bool live[ITEMS];  // counted and of non-zero length
-  unsigned long long t_max[2] = {0, 0};
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    live[j] = p0 + j < n2 && (uint32_t)(k[j] >> 32) != M.sentinel && e[j] > (uint32_t)k[j];
-    if (live[j]) {
-      const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
-      t_max[0] = max64(t_max[0], P);
-      if (v[j] & KEPT_FLAG) t_max[1] = max64(t_max[1], P);
-    }
-  }
-  // running maximum over the threads before this one: wavefront, work-group, tiles before
-  unsigned long long inc[2] = {t_max[0], t_max[1]};
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long a = __shfl_up(inc[0], d), b = __shfl_up(inc[1], d);
-    if (lane >= d) inc[0] = max64(inc[0], a), inc[1] = max64(inc[1], b);
-  }
-  if (lane == 63) l_wave[0][wave] = inc[0], l_wave[1][wave] = inc[1];
-  __syncthreads();
-  unsigned long long r[2] = {__shfl_up(inc[0], 1), __shfl_up(inc[1], 1)};
-  if (lane == 0) r[0] = r[1] = 0;
-  for (int w = 0; w < wave; ++w) r[0] = max64(r[0], l_wave[0][w]), r[1] = max64(r[1], l_wave[1][w]);
-  if (blockIdx.x > 0) {
-    if (sets & SET_ALL) r[0] = max64(r[0], carry[blockIdx.x - 1]);
-    if (sets & SET_KEPT) r[1] = max64(r[1], carry[ntiles + blockIdx.x - 1]);
-  }
-  // heads.  A maximum of 0 is "nothing of the set before": a live entry has end >= 1, so its P is never 0.
-  uint32_t cnt[2] = {0, 0}, is_head[2] = {0, 0};
-  unsigned long long prev[2][ITEMS];  // the running maximum in front of a head: segment and end of the interval it closes
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    prev[0][j] = prev[1][j] = 0;
-    if (!live[j]) continue;
-    const uint32_t seg = (uint32_t)(k[j] >> 32), start = (uint32_t)k[j];
-    const unsigned long long P = (k[j] & 0xffffffff00000000ull) | e[j];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (!(sets >> s & 1u) || (s == 1 && !(v[j] & KEPT_FLAG))) continue;
-      if (r[s] == 0 || (uint32_t)(r[s] >> 32) != seg || start > (uint32_t)r[s]) {
-        ++cnt[s];
-        is_head[s] |= 1u << j;
-        prev[s][j] = r[s];
-      }
-      r[s] = max64(r[s], P);
-    }
-  }
-  if (!WRITE) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const uint32_t c = (uint32_t)wave_sum(cnt[s]);
-      if (lane == 0) l_cnt[s][wave] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && (sets >> threadIdx.x & 1u)) {
-      uint32_t c = 0;
-      for (int w = 0; w < WAVES; ++w) c += l_cnt[threadIdx.x][w];
-      tile_cnt[threadIdx.x * ntiles + blockIdx.x] = c;
-    }
-    return;
-  }
-  // ranks: heads of the threads before this one, of the tiles before this one
-  uint32_t rank[2] = {cnt[0], cnt[1]};
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t a = __shfl_up(rank[0], d), b = __shfl_up(rank[1], d);
-    if (lane >= d) rank[0] += a, rank[1] += b;
-  }
-  if (lane == 63) l_cnt[0][wave] = rank[0], l_cnt[1][wave] = rank[1];
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    if (!(sets >> s & 1u)) continue;
-    const uint32_t m = out.total[s];
-    uint32_t at = rank[s] - cnt[s] + tile_cnt[s * ntiles + blockIdx.x];
-    for (int w = 0; w < wave; ++w) at += l_cnt[s][w];
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      if (!(is_head[s] >> j & 1u)) continue;
-      if (at < m) {  // (always: the count pass counted these heads)
-        out.keys[s][at] = ((uint64_t)segment_seq(M, (uint32_t)(k[j] >> 32)) << 32) | (uint32_t)k[j];
-        out.deltas[s][at] = 1u;
-        if (at > 0) {
-          out.keys[s][(uint64_t)m + at - 1] = ((uint64_t)segment_seq(M, (uint32_t)(prev[s][j] >> 32)) << 32) | (uint32_t)prev[s][j];
-          out.deltas[s][(uint64_t)m + at - 1] = ~0u;
-        }
-      }
-      ++at;
-    }
-    // the last interval's end: the maximum over everything
-    if (blockIdx.x == ntiles - 1 && threadIdx.x == 0 && m > 0) {
-      const unsigned long long last = carry[s * ntiles + ntiles - 1];
-      out.keys[s][2 * (uint64_t)m - 1] = ((uint64_t)segment_seq(M, (uint32_t)(last >> 32)) << 32) | (uint32_t)last;
-      out.deltas[s][2 * (uint64_t)m - 1] = ~0u;
-    }
-  }
-}
 
 __global__ __launch_bounds__(TB) void sharing_count_kernel(uint64_t n2, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                            const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
                                                            uint64_t ntiles, SegMap M, uint32_t sets, uint32_t* __restrict__ tile_cnt) {
-  heads_tile<false>(n2, keys, vals, ends, carry, ntiles, M, sets, tile_cnt, EventsOut{});
+  heads_tile<false>(n2, keys, vals, ends, carry, ntiles, M.sentinel, sets, tile_cnt, EventsOut{});
 }
 
 __global__ __launch_bounds__(TB) void sharing_events_kernel(uint64_t n2, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             const uint32_t* __restrict__ ends, const unsigned long long* __restrict__ carry,
-                                                            uint64_t ntiles, SegMap M, uint32_t sets, uint32_t* __restrict__ tile_off, EventsOut out) {
-  heads_tile<true>(n2, keys, vals, ends, carry, ntiles, M, sets, tile_off, out);
+                                                            uint64_t ntiles, uint32_t sets, uint32_t* __restrict__ tile_off, EventsOut out) {
+  heads_tile<true>(n2, keys, vals, ends, carry, ntiles, out.M.sentinel, sets, tile_off, out);
 }
 
 // ---- the depth sweep over the sorted events of one set ---------------------------------------------------------------------
@@ -274,17 +172,7 @@ __global__ __launch_bounds__(TB) void sharing_runs_kernel(const uint32_t* __rest
 }
 
 __global__ __launch_bounds__(TB) void sharing_bases_kernel(const swg_depth_run* __restrict__ rows, uint64_t n_rows, unsigned long long* __restrict__ sum) {
-  __shared__ unsigned long long l_sum[WAVES];
-  unsigned long long s = 0;
-  for (uint64_t x = (uint64_t)blockIdx.x * TB + threadIdx.x; x < n_rows; x += (uint64_t)gridDim.x * TB) s += rows[x].end - rows[x].start;
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) l_sum[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < WAVES; ++w) t += l_sum[w];
-    if (t) atomicAdd(sum, t);
-  }
+  bases_sum(rows, n_rows, sum);
 }
 
 // `amount` of every lane with a key (EMPTY = none) into the spectrum: runs of one key along the lanes are summed towards their
@@ -344,24 +232,13 @@ __global__ __launch_bounds__(TB) void sharing_private_kernel(unsigned long long*
   unsigned long long* row = spectrum + (uint64_t)blockIdx.x * G;
   unsigned long long s = 0;
   for (uint32_t d = 1 + threadIdx.x; d < G; d += TB) s += row[d];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) l_sum[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < WAVES; ++w) t += l_sum[w];
-    row[0] -= t;
-  }
+  const unsigned long long t = block_sum(s, l_sum);
+  if (threadIdx.x == 0) row[0] -= t;
 }
-
-struct DevCols {
-  const uint32_t *q_id, *t_id, *start[2], *end[2], *seq_genome, *seq_len;
-  const uint8_t* status;
-};
 
 // The depth sweep of one set over its 2 m events (unsorted in ev_keys / ev_deltas), inside an arena frame: the runs on the
 // device, then what `runs` (n, bases, rows) and `spectrum` ask for.  vec: receives the rows instead of list->rows.
-int depth_sweep(swg_ctx* ctx, uint32_t m, uint64_t* ev_keys, uint32_t* ev_deltas, uint32_t n_seq, uint32_t G, const DevCols& d, bool runs, bool spectrum,
+int depth_sweep(swg_ctx* ctx, uint32_t m, uint64_t* ev_keys, uint32_t* ev_deltas, uint32_t n_seq, uint32_t G, const SegCols& d, bool runs, bool spectrum,
                 unsigned long long* scalars, unsigned long long* sc, swg_depth_list* list, std::vector<swg_depth_run>* vec) {
   hipStream_t st = ctx->stream;
   const uint64_t n_ev = 2 * (uint64_t)m;
@@ -420,17 +297,8 @@ int depth_sweep(swg_ctx* ctx, uint32_t m, uint64_t* ev_keys, uint32_t* ev_deltas
     }
     list->n = n_runs;
     list->bases = bases;
-    swg_depth_run* dst = nullptr;
-    if (vec) {
-      vec->resize(n_runs);
-      dst = vec->data();
-    } else if (list->rows && n_runs <= list->capacity) {
-      dst = list->rows;
-    }
-    if (dst && n_runs) {
-      SWG_HIP(ctx, hipMemcpyAsync(dst, rows, n_runs * sizeof(swg_depth_run), hipMemcpyDeviceToHost, st));
-      SWG_HIP(ctx, hipStreamSynchronize(st));
-    }
+    swg_depth_run* dst;
+    SWG_TRY(rows_hand_over(ctx, rows, n_runs, vec, list->rows, list->capacity, &dst));
   }
   if (spectrum) {
     Spectrum T{};
@@ -458,7 +326,7 @@ int depth_sweep(swg_ctx* ctx, uint32_t m, uint64_t* ev_keys, uint32_t* ev_deltas
 }
 
 // inside an arena frame.  vecs: nullptr, or [2] vectors that receive the rows instead of req's arrays
-int sharing_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const DevCols& d, swg_sharing_request* req, std::vector<swg_depth_run>* vecs) {
+int sharing_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const SegCols& d, swg_sharing_request* req, std::vector<swg_depth_run>* vecs) {
   hipStream_t st = ctx->stream;
   const uint32_t want = req->want;
   const uint32_t sets = (want & 0x5u ? SET_ALL : 0u) | (want & 0xau ? SET_KEPT : 0u);
@@ -478,6 +346,7 @@ int sharing_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
     SegMap M;
     segmap_alloc(ctx, n2, n_seq, G, segmap_forced(), &M);  // (every record may touch two segments)
     SWG_CHECK_ARENA(ctx);
+    out.M = M;
     if (M.set_keys) SWG_HIP(ctx, hipMemsetAsync(M.set_keys, 0xff, ((size_t)M.set_mask + 1) * sizeof(unsigned long long), st));
     const unsigned grid_n = (unsigned)((n + TB - 1) / TB), grid_t = (unsigned)ntiles;
     SWG_LAUNCH(ctx, "sharing_keys", sharing_keys_kernel<<<grid_n, TB, 0, st>>>(n, d.q_id, d.t_id, d.start[0], d.start[1], d.end[0], d.end[1], d.status,
@@ -509,7 +378,7 @@ int sharing_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const D
     }
     SWG_CHECK_ARENA(ctx);
     if (out.total[0] || out.total[1]) {
-      SWG_LAUNCH(ctx, "sharing_events", sharing_events_kernel<<<grid_t, TB, 0, st>>>(n2, keys, vals, ends, tile_max, ntiles, M, sets, tile_cnt, out));
+      SWG_LAUNCH(ctx, "sharing_events", sharing_events_kernel<<<grid_t, TB, 0, st>>>(n2, keys, vals, ends, tile_max, ntiles, sets, tile_cnt, out));
       SWG_KERNEL_CHECK(ctx);
     }
   }
@@ -536,7 +405,7 @@ int sharing_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
     if ((want >> (2 + s) & 1u) && !req->set[s].spectrum) return swg_set_error(ctx, SWG_ERR_INVALID, "sharing: a spectrum bit with a NULL spectrum");
   const uint64_t n = rec->n;
   const uint32_t n_seq = rec->n_seq;
-  if (n >= (uint64_t(1) << 30)) return swg_set_error(ctx, SWG_ERR_RANGE, "sharing: 2^30 records or more in one call");
+  SWG_TRY(seg_check_args(ctx, "sharing", ARG_LIMIT, rec, seq_genome, n_genome, 30));
   if ((want & WANT_SPECTRUM) && n_genome > MAX_SPECTRUM_GENOMES)
     return swg_set_error(ctx, SWG_ERR_RANGE, "sharing: a spectrum of more than 4096 genomes (the runs alone have no such limit)");
   for (int s = 0; s < 2; ++s) {
@@ -551,8 +420,7 @@ int sharing_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   if (n && (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->t_start || !rec->t_end))
     return swg_set_error(ctx, SWG_ERR_INVALID, "sharing: NULL column (q_id, t_id and the four coordinates are read)");
   if (!seq_genome) return swg_set_error(ctx, SWG_ERR_INVALID, "sharing: NULL seq_genome");
-  if (n_seq == 0 || n_genome == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "sharing: records without sequences or genomes");
-  if (n_seq > (uint32_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "sharing: more than 2^31 sequences");
+  SWG_TRY(seg_check_args(ctx, "sharing", ARG_COUNTS, rec, seq_genome, n_genome, 30));
   if (n == 0 && !on_device) {  // no record, nothing to sweep: column 0 is the lengths, and they are here
     for (int s = 0; s < 2; ++s) {
       if (!(want >> (2 + s) & 1u)) continue;
@@ -566,19 +434,14 @@ int sharing_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * 96 + (size_t)n_seq * 8 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
-    DevCols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, seq_len, status};
-    if (!on_device) {
-      const uint32_t* col[6];
-      uint8_t* s8;
-      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end}, seq_genome,
-                            status != nullptr, status, col, &d.seq_genome, &s8));
-      d = DevCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, d.seq_genome, nullptr, s8};
-      if (seq_len) {
-        uint32_t* len = swg_alloc<uint32_t>(ctx, n_seq);
-        SWG_CHECK_ARENA(ctx);
-        SWG_HIP(ctx, hipMemcpyAsync(len, seq_len, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        d.seq_len = len;
-      }
+    SegCols d;
+    SWG_TRY(seg_stage(ctx, rec, on_device, seq_genome, status, &d));
+    d.seq_len = seq_len;
+    if (!on_device && seq_len) {
+      uint32_t* len = swg_alloc<uint32_t>(ctx, n_seq);
+      SWG_CHECK_ARENA(ctx);
+      SWG_HIP(ctx, hipMemcpyAsync(len, seq_len, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+      d.seq_len = len;
     }
     return sharing_device(ctx, n, n_seq, n_genome, d, req, vecs);
   });
@@ -591,11 +454,6 @@ int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
   } catch (const std::bad_alloc&) {
     return swg_set_error(ctx, SWG_ERR_OOM, "out of host memory");
   }
-}
-
-void append_u64(std::string& o, uint64_t v, char sep) {
-  o += std::to_string(v);
-  o += sep;
 }
 
 // the table of swg_paf_sharing from the two spectra ([G * G] each)
@@ -678,14 +536,6 @@ std::string bed_text(const swg_paf* p, const std::vector<swg_depth_run>& all, co
   }
   flush();
   return o;
-}
-
-char* text_copy(const std::string& o) {
-  char* t = static_cast<char*>(std::malloc(o.size() + 1));
-  if (!t) return nullptr;
-  std::memcpy(t, o.data(), o.size());
-  t[o.size()] = 0;
-  return t;
 }
 
 }  // namespace

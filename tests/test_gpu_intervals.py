@@ -209,6 +209,20 @@ def test_tile_edges(sw):
     assert same_lists(both_seams(sw, {c: cols[c][perm] for c in COLS}, seq_genome, status[perm]), got)
 
 
+def test_tile_edges_with_one_set_scanned(sw):
+    """The five tiles again, wanting only the KEPT lists and then only the ALL lists: the walk then carries one set across the
+    tile edges and must leave the other set's carry alone.  The rows equal those of the all-six call, in both seams."""
+    from sweepga_amd.intervals import want_bits
+    cols, seq_genome, status, _ = tile_edge_case()
+    every = both_seams(sw, cols, seq_genome, status)
+    for name in ("kept", "all"):
+        only = both_seams(sw, cols, seq_genome, status, want=want_bits([(name, "q"), (name, "t")]))
+        assert sorted(only) == [(name, "q"), (name, "t")]
+        for a in im.AXES:
+            assert len(only[name, a]) > 1_000 and im.same_rows(only[name, a], every[name, a]), (name, a)
+            assert only.bases[name, a] == every.bases[name, a], (name, a)
+
+
 def test_a_far_carry(sw):
     """10^6 records of one unit under one long interval that KEPT does not have: 977 tiles of carry for ALL, none for KEPT."""
     n = 1_000_000

@@ -130,6 +130,21 @@ def test_around_the_tile_of_1024_entries(sw, n):
     assert sm.as_tuples(got.runs["all"])[-1] == (1, 7 * (n - 39), 7 * (n - 1) + 9, 1)
 
 
+def test_tile_edges_with_one_set_scanned(sw):
+    """The five-tile input of tests/test_gpu_intervals.py, wanting only the ALL runs (0x1) and then only the KEPT runs (0x2): the
+    other set's tile maxima are never scanned then, and a walk that read them as a carry would be using unscanned values.  The
+    runs equal those of the 0xf call, in both seams."""
+    from tests.test_gpu_intervals import tile_edge_case
+    cols, seq_genome, status, _ = tile_edge_case()
+    seq_len = lengths_for(cols, len(seq_genome))
+    every = both_seams(sw, cols, seq_genome, seq_len, status, want=0xf)
+    for bit, name in ((0x1, "all"), (0x2, "kept")):
+        only = both_seams(sw, cols, seq_genome, seq_len, status, want=bit)
+        assert sorted(only.runs) == [name] and not only.spectrum
+        assert len(only.runs[name]) > 1_000 and sm.same_rows(only.runs[name], every.runs[name]), name
+        assert only.bases[name] == every.bases[name], name
+
+
 def piles(ends):
     """Genome g = 1 .. len(ends) covers sequence 0 (genome 0) over [0, ends[g - 1]) from the target axis."""
     k = len(ends)

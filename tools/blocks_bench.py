@@ -19,12 +19,13 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import bench  # noqa: E402
 import sweepga_amd as sw  # noqa: E402
 from sweepga_amd import _lib  # noqa: E402
-from sweepga_amd.blocks import _call  # noqa: E402
+from sweepga_amd.blocks import BLOCK_DTYPE, _call  # noqa: E402
 
 REPS = 7
 OWN = ("blocks_max", "blocks_reduce", "blocks_keys", "blocks_gather", "blocks_union", "blocks_collect")
@@ -65,9 +66,14 @@ def main():
     out["records_in_chains"] = int(((status != 0) & (chain != 0)).sum())
 
     def measure(c, st, ch, tag):
+        sync()   # the first call below comes before timed(): torch's writes to these columns (the shuffle) must be complete
         r = bench.make_records(_lib, c, n, G)
-        f = lambda: _call(ctx, ctx.lib.swg_blocks_records_device, r, st.data_ptr(), ch.data_ptr())   # noqa: E731
-        t = f()
+        t = _call(ctx, ctx.lib.swg_blocks_records_device, r, st.data_ptr(), ch.data_ptr())
+        # what is timed is ONE library call into an array of the exact capacity (the wrapper above calls twice when the blocks
+        # outnumber its first guess)
+        dst, rows = _lib.SwgBlockTable(), np.zeros(max(len(t), 1), dtype=BLOCK_DTYPE)
+        dst.block_capacity, dst.blocks = len(t), C.cast(rows.ctypes.data, C.POINTER(_lib.SwgBlock))
+        f = lambda: ctx.check(ctx.lib.swg_blocks_records_device(ctx.handle, C.byref(r), st.data_ptr(), ch.data_ptr(), C.byref(dst)))   # noqa: E731
         out[tag + "_blocks"] = len(t)
         out[tag + "_largest_chain_records"] = int((t["n_core"] + t["n_inverted"] + t["n_rescued"]).max()) if len(t) else 0
         out[tag + "_ms"] = timed(f, sync)

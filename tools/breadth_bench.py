@@ -57,6 +57,7 @@ def main():
     out = {"n": n, "n_genomes": G, "reps": REPS}
 
     def measure(c, st, tag):
+        sync()   # the first call below comes before timed(): torch's writes to these columns (the shuffle) must be complete
         rec = bench.make_records(_lib, c, n, G)
         genome = c["seq_genome_last"].data_ptr()
         f = lambda: _call(ctx, ctx.lib.swg_breadth_records_device, rec, genome, G, st.data_ptr())   # noqa: E731

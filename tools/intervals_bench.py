@@ -76,6 +76,7 @@ def main():
     out = {"n": n, "n_genomes": G, "reps": REPS}
 
     def measure(c, st, tag):
+        sync()   # the first call below comes before timed(): torch's writes to these columns (the shuffle) must be complete
         rec = bench.make_records(_lib, c, n, G)
         genome = c["seq_genome_last"].data_ptr()
         for name, want in (("all_six", 0x3f), ("lost_q", 1 << 4)):
