@@ -1043,6 +1043,69 @@ int swg_lift_closure_records_device(swg_ctx* ctx, const swg_records* rec, const 
 int swg_paf_lift_closure(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
                          uint32_t max_hops, uint32_t min_len, char** out_text, uint64_t* out_len);
 
+/* ---- mosaic: the best mapping at every base (no reference counterpart) ---------------------------------
+ * The reports above say how much is covered, where, and by how many genomes; this says BY WHICH MAPPING.  Every value is an
+ * integer, every comparison exact.  On the query axis (0) record r lies on sequence q_id[r] over [q_start, q_end) and its other
+ * sequence is t_id[r]; on the target axis (1) the roles swap.  The counting rule is breadth's: a record counts only when the
+ * genomes of its two sequences differ under the caller's seq_genome, intervals are half-open, a zero-length record on the axis
+ * adds nothing, start <= end is assumed.  set: SWG_IV_ALL = the counted records, SWG_IV_KEPT = those with status != 0.
+ *   priority  P(r) = (uint64)weight[r] << 32 | (0xffffffff - r): the heavier record wins, among equal weights the lower index.
+ *             weight == NULL: rec->matches.
+ *   winner    at base x of sequence s: the record of the set on the axis with seq == s, start <= x < end and maximal P.
+ *   rows      the maximal half-open intervals of a sequence with one winner, ordered by (seq, start); stretches without a
+ *             winner are not listed.  One record can own several rows (a heavier record nested inside it cuts it in two).
+ *             bases = sum(end - start) = the bases under at least one record of the set.
+ *   share     share[g * n_genome + h] = bases of the sequences of genome g won by records whose other sequence is of genome h;
+ *             the diagonal is 0.
+ * Values and order depend neither on the launch shapes nor, with pairwise different weights, on the order of the records.
+ * `want`: SWG_MOSAIC_ROWS writes n and bases and, under the capacity protocol of swg_breadth_counts, the rows (n > capacity
+ * still returns SWG_OK and leaves `rows` alone); SWG_MOSAIC_SHARE writes all n_genome * n_genome entries of the caller's array
+ * and reads back no rows.  Errors: a NULL context (there is no CPU path), reserved != 0, want == 0 or a bit beyond the two, axis
+ * > 1, set > 1, SWG_IV_KEPT with status == NULL, the share bit with a NULL share, a sequence id >= n_seq or a genome id >=
+ * n_genome, weight == NULL with rec->matches == NULL: SWG_ERR_INVALID; n >= 2^31 records, or the share bit with n_genome > 4096
+ * (the rows stay available): SWG_ERR_RANGE.  q_id, t_id, the four coordinates and matches (weight == NULL) are read.  Scratch
+ * comes from the context's arena, SWG_ERR_OOM when the memory limit does not hold it: 48 bytes per record for the sort of the
+ * 2n boundary entries, then per DISTINCT boundary (B <= 2n + 1) 21 bytes and 8 * bits(B / T) / T for the tile table (T = 512), 5
+ * per change of winner, 20 per row and 8 * n_genome^2 for a share (DESIGN.md section 25 has the formula).  swg_mosaic_records
+ * stages its host columns there too: 29 more bytes per record. */
+typedef struct swg_mosaic_row {
+  uint32_t seq;
+  uint32_t start, end; /* half-open */
+  uint32_t record;     /* the winner */
+} swg_mosaic_row; /* 16 bytes */
+#define SWG_MOSAIC_ROWS 1u
+#define SWG_MOSAIC_SHARE 2u
+typedef struct swg_mosaic_request {
+  uint32_t want;          /* the two bits above */
+  uint32_t axis;          /* 0 = query, 1 = target */
+  uint32_t set;           /* SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t reserved;      /* 0 */
+  const uint32_t* weight; /* [n] or NULL = rec->matches; host / device as the columns */
+  uint64_t n, bases;      /* out (rows bit) */
+  uint64_t capacity;      /* in: entries `rows` can hold */
+  swg_mosaic_row* rows;   /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+  uint64_t* share;        /* in (share bit): caller-owned [n_genome * n_genome], fully written */
+} swg_mosaic_request; /* 64 bytes, no implicit padding */
+/* rec: host pointers; seq_genome[rec->n_seq], status[n] (NULL: SWG_IV_ALL only) and req->weight on the host. */
+int swg_mosaic_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                       swg_mosaic_request* req);
+/* The same with the columns of rec, seq_genome, status and req->weight in device memory of ctx's GPU; the request and its
+ * arrays stay on the host. */
+int swg_mosaic_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                              swg_mosaic_request* req);
+/* Both texts of an open PAF under its last-'#' genome map from ONE device call (release each with swg_free); a text is asked
+ * for by a non-NULL out_text[k] on entry, as in swg_paf_sharing.  The weight is the matches column, with by_length != 0 the
+ * record's end - start on the axis (computed on the device).  Tab-separated:
+ *   text 0  BED-like, one line per row: sequence start end other_sequence strand(+|-) record weight other_start other_end --
+ *           record is the 0-based record number, the other interval the whole record's; the file is a --lift-regions input.
+ *   text 1  header `genome other_genome bases`, one line per non-zero share entry in (g, h) order (names keep their trailing
+ *           '#'), then `#total <bases>`.
+ * A PAF without records gives the header-only texts (text 0 is empty) and needs no device (ctx may be NULL then).  set ==
+ * SWG_IV_KEPT with status == NULL: SWG_ERR_INVALID; a handle with rebased columns: SWG_ERR_UNSUPPORTED; more than 4096 genomes
+ * with text 1: SWG_ERR_RANGE.  Errors: text in swg_alnstats_last_error(). */
+int swg_paf_mosaic(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t set, int by_length, char** out_text,
+                   uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

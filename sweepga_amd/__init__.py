@@ -16,6 +16,7 @@ from .components import (COMPONENT_DTYPE, LINK_DTYPE, Components, components_rec
 from .breadth import BREADTH_PAIR_DTYPE, Breadth, breadth_records, breadth_records_device  # noqa: F401
 from .intervals import INTERVAL_DTYPE, Intervals, intervals_records, intervals_records_device  # noqa: F401
 from .sharing import RUN_DTYPE, Sharing, sharing_records, sharing_records_device  # noqa: F401
+from .mosaic import ROW_DTYPE, Mosaic, mosaic_records, mosaic_records_device  # noqa: F401
 from .dotplot import Dotplot, DotplotResult, dotplot_records, dotplot_records_device  # noqa: F401
 from .lift import Lift, LiftClosure, LiftClosureResult, LiftResult, lift_closure_records, lift_closure_records_device, lift_records, lift_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401

@@ -42,7 +42,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_sharing_records", "swg_sharing_records_device", "swg_paf_sharing",
            "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot",
            "swg_lift_records", "swg_lift_records_device", "swg_paf_lift",
-           "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure"]
+           "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
+           "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic"]
 
 
 class SwgError(RuntimeError):
@@ -197,6 +198,16 @@ class SwgDepthList(C.Structure):
 
 class SwgSharingRequest(C.Structure):
     _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("set", SwgDepthList * 2)]   # set[ALL, KEPT]
+
+
+class SwgMosaicRow(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("record", C.c_uint32)]
+
+
+class SwgMosaicRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("axis", C.c_uint32), ("set", C.c_uint32), ("reserved", C.c_uint32), ("weight", C.c_void_p),
+                ("n", C.c_uint64), ("bases", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgMosaicRow)),
+                ("share", C.POINTER(C.c_uint64))]
 
 
 class SwgDotAxes(C.Structure):
@@ -448,6 +459,12 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(SwgSharingRequest)]
     lib.swg_paf_sharing.restype = C.c_int
     lib.swg_paf_sharing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_mosaic_records", "swg_mosaic_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgMosaicRequest)]
+    lib.swg_paf_mosaic.restype = C.c_int
+    lib.swg_paf_mosaic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_dotplot_records", "swg_dotplot_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

@@ -104,6 +104,13 @@ int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, c
 // fills req->n and the summaries, and the rows when they fit
 uint32_t swg_closure_hop0_host(const swg_lift_region* regions, uint64_t m, uint32_t n_seq, swg_closure_request* req);
 
+// ---- mosaic (swg_mosaic.hip: kernels and seams; mosaic_text.cpp: the two texts of swg_paf_mosaic) ----
+// one line per row: sequence start end other_sequence strand record weight other_start other_end (rec: the handle's records,
+// with the matches column the device call read)
+std::string swg_mosaic_rows_text(const swg_paf* p, const swg_records* rec, const std::vector<swg_mosaic_row>& rows, uint32_t axis, bool by_length);
+// `genome other_genome bases`, one line per non-zero entry of share ([G * G], G = genome_name.size()), then `#total <bases>`
+std::string swg_mosaic_share_text(const std::vector<std::string>& genome_name, const std::vector<uint64_t>& share, uint64_t bases);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

@@ -336,6 +336,26 @@ void write_sharing(const std::string& table_path, const std::string& bed_path, s
   }
 }
 
+// --mosaic / --mosaic-share: the rows and the share table of swg_paf_mosaic (the best mapping at every base), both from one device
+// call when both are asked for.  "-" = standard error.
+void write_mosaic(const std::string& rows_path, const std::string& share_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t axis,
+                  uint32_t set, bool by_length) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, share_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_mosaic(ctx, paf, status, axis, set, by_length ? 1 : 0, text, len) != SWG_OK) die(3, std::string("--mosaic: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? rows_path : share_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
 // --dotplot / --dotplot-layout: the image and the layout table of swg_paf_dotplot, both from one device call when both are asked
 // for.  The layout's "-" = standard error.
 void write_dotplot(const std::string& image_path, const std::string& layout_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
@@ -440,6 +460,9 @@ int main(int argc, char** argv) {
   std::string lost_path, covered_path;  // --lost, --covered: empty = no file
   std::string sharing_path, sharing_bed_path;  // --sharing, --sharing-bed: empty = no file
   bool sharing_detailed = false;
+  std::string mosaic_path, mosaic_share_path;  // --mosaic, --mosaic-share: empty = no file
+  uint32_t mosaic_axis = 0, mosaic_set = SWG_IV_KEPT;
+  bool mosaic_by_length = false, mosaic_flag = false;  // (mosaic_flag: one of --mosaic-axis / --mosaic-set / --mosaic-by was given)
   std::string dotplot_path, dotplot_layout_path, dotplot_query, dotplot_target;  // --dotplot, --dotplot-layout: empty = no file
   swg_dot_view dot_view{2048, 2048, nullptr, nullptr};
   bool dotplot_flag = false;  // (one of --dotplot-size / --dotplot-query / --dotplot-target was given)
@@ -543,6 +566,29 @@ int main(int argc, char** argv) {
       if (!parse_u64(value(), &lift_min_length) || lift_min_length > UINT32_MAX) die(2, "invalid value for --lift-min-length: 0 .. 2^32 - 1");
       lift_min_length_flag = true;
     }
+    else if (a == "--mosaic") { mosaic_path = value(); if (mosaic_path.empty()) die(2, "empty value for --mosaic"); }
+    else if (a == "--mosaic-share") { mosaic_share_path = value(); if (mosaic_share_path.empty()) die(2, "empty value for --mosaic-share"); }
+    else if (a == "--mosaic-axis") {
+      const std::string v = value();
+      if (v == "query") mosaic_axis = 0;
+      else if (v == "target") mosaic_axis = 1;
+      else die(2, "invalid value for --mosaic-axis: query or target");
+      mosaic_flag = true;
+    }
+    else if (a == "--mosaic-set") {
+      const std::string v = value();
+      if (v == "kept") mosaic_set = SWG_IV_KEPT;
+      else if (v == "all") mosaic_set = SWG_IV_ALL;
+      else die(2, "invalid value for --mosaic-set: kept or all");
+      mosaic_flag = true;
+    }
+    else if (a == "--mosaic-by") {
+      const std::string v = value();
+      if (v == "matches") mosaic_by_length = false;
+      else if (v == "length") mosaic_by_length = true;
+      else die(2, "invalid value for --mosaic-by: matches or length");
+      mosaic_flag = true;
+    }
     else if (a == "--lift-set") {
       const std::string v = value();
       if (v == "kept") lift_set = SWG_IV_KEPT;
@@ -583,6 +629,7 @@ int main(int argc, char** argv) {
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
+                "         [--mosaic FILE|-] [--mosaic-share FILE|-] [--mosaic-axis query|target] [--mosaic-set kept|all] [--mosaic-by matches|length]\n"
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
@@ -619,6 +666,15 @@ int main(int argc, char** argv) {
                 "  --sharing-detailed  with --sharing: after `#spectrum`, `genome all|kept depth bases` for every depth that occurs\n"
                 "  --sharing-bed FILE  after the filter: `sequence start end n_all n_kept`, the stretches covered by a constant number\n"
                 "                      of genomes before (n_all >= 1) and after the filter; with --sharing, both come from one device call\n"
+                "  --mosaic FILE       after the filter: the best mapping at every base -- `sequence start end other_sequence strand record\n"
+                "                      weight other_start other_end`, one line per maximal stretch on which one inter-genome mapping is the\n"
+                "                      heaviest (ties: the earlier record); a tiling of what is covered, built on the device (- = standard\n"
+                "                      error), and a --lift-regions input\n"
+                "  --mosaic-share FILE `genome other_genome bases`: how much of each genome every other genome wins, then `#total bases`;\n"
+                "                      with --mosaic, both come from one device call\n"
+                "  --mosaic-axis query|target  the sequences that are tiled (default query)\n"
+                "  --mosaic-set kept|all  the mappings that compete (default kept; with --no-filter kept = all)\n"
+                "  --mosaic-by matches|length  a mapping's weight: its matches column or its length on the axis (default matches)\n"
                 "  --dotplot FILE      after the filter: a dot plot of the mappings as a binary PPM, targets along x and queries along y,\n"
                 "                      sequences in (genome, first appearance) order, the origin bottom-left: kept mappings black, kept\n"
                 "                      inversions red, dropped mappings grey, dropped inversions pink, genome borders pale blue.  Rasterised\n"
@@ -657,6 +713,8 @@ int main(int argc, char** argv) {
   if (components_path.empty() && (components_detailed || component_flag))
     die(2, "--components-detailed, --component-min-bases and --component-min-share need --components");
   if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
+  if (mosaic_path.empty() && mosaic_share_path.empty() && mosaic_flag) die(2, "--mosaic-axis, --mosaic-set and --mosaic-by need --mosaic or --mosaic-share");
+  const bool mosaic = !mosaic_path.empty() || !mosaic_share_path.empty();
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
     die(2, "--dotplot-size, --dotplot-query and --dotplot-target need --dotplot or --dotplot-layout");
   const bool lift = !lift_regions_path.empty();
@@ -755,7 +813,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -813,6 +871,10 @@ int main(int argc, char** argv) {
   if ((!sharing_path.empty() || !sharing_bed_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--sharing: the file has a value >= 2^32, its columns are rebased: sharing of 64-bit columns is not supported");
+  }
+  if (mosaic && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--mosaic: the file has a value >= 2^32, its columns are rebased: the mosaic of 64-bit columns is not supported");
   }
   if ((!dotplot_path.empty() || !dotplot_layout_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
@@ -879,6 +941,12 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_sharing(sharing_path, sharing_bed_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), sharing_detailed);
+    }
+    if (mosaic) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_mosaic(mosaic_path, mosaic_share_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), mosaic_axis, mosaic_set, mosaic_by_length);
     }
     if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {  // nothing is dropped: the kept planes equal the all planes
       std::fflush(out);
@@ -1025,6 +1093,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_sharing(sharing_path, sharing_bed_path, ctx, paf, status.data(), sharing_detailed);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --sharing: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --mosaic / --mosaic-share: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
+  if (mosaic) {
+    const auto tb = clk::now();
+    write_mosaic(mosaic_path, mosaic_share_path, ctx, paf, status.data(), mosaic_axis, mosaic_set, mosaic_by_length);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --mosaic: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --dotplot / --dotplot-layout: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
   if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {
