@@ -1834,7 +1834,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
           P.qe = s_qe[i];
           P.ts = s_ts[i];
           P.te = s_te[i];
-          P.minus = pair_desc ? D.pad : (uint32_t)(s_grp[i] & 1ull);
+          P.minus = pair_desc ? D.pad & 1u : (uint32_t)(s_grp[i] & 1ull);  // (bit 0: the strand; bit 1 is the pair stage's mark)
         } else {
 #pragma unroll
           for (int c = 0; c < KC; ++c) {
@@ -2114,7 +2114,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
           if (wstats && lane == 0) atomicAdd(&wstats[2], 1ull);  // whole-window passes
           const uint32_t ii = i0 + l;
           const uint64_t qe_l = s_qe[ii], ts_l = s_ts[ii], te_l = s_te[ii];
-          const bool minus_l = pair_desc ? D.pad != 0 : (s_grp[ii] & 1ull) != 0;
+          const bool minus_l = pair_desc ? (D.pad & 1u) != 0 : (s_grp[ii] & 1ull) != 0;
           const uint32_t e_l = readlane_u32(e_i, l);
           const uint64_t bound = qe_l + max_gap;
           uint64_t ld = INF;

@@ -417,14 +417,19 @@ constexpr int LABEL_CAP = (int)(WALK_CHUNK + BIG_UNIT);  // a chunk holds fewer 
 // the values in memory a head's step was five scattered loads issued for the few lanes still walking -- 33 vector-memory
 // instructions per 64 elements, most of them nearly empty, and the texture path was what the kernel waited for (SQ counters).
 // The head of every element goes through LDS as well and is written in element order.  Longer chunks take the old path.
-constexpr int LABEL_FAST = 1536;
+constexpr int LABEL_FAST = (int)LABEL_FAST_ELEMS;
 constexpr int LABEL_NT = 512;
 static_assert(LABEL_FAST * (2 + 2 + 3 * 4) >= LABEL_CAP * 2, "the two layouts share one LDS buffer");
 // NT threads per chunk; MB: the matches / block-length columns exist (a weighted identity is asked for).  Round 6: 512 threads
 // with three elements each instead of 256 with six (114 registers, 36 KB of LDS: four work-groups of four wavefronts per CU,
 // and the kernel waited for its loads 76 % of the time) and no LDS for the two columns nobody reads under the CLI defaults.
-template <int NT, bool MB>
-__global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, const SpecBlock* __restrict__ chunks,
+// RANKED (pair-resident path): a chunk whose descriptor carries CHUNK_RANKED -- every chunk of its pair is labelled
+// in LDS -- leaves behind what pair_finish would otherwise work out again from ok_head / hd / HeadRec: per element the rank of
+// its chain among the chunk's passing chains in position order (NONE: the chain fails) in hd, per chunk the number of passing
+// chains, and per passing '+' chain the three values the inversion capture reads, at (chunk begin + rank).  No ok_head and no
+// HeadRec is written for such a chunk.
+template <int NT, bool MB, bool RANKED>
+__global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_t n_chunks, const SpecBlock* __restrict__ chunks,
                                                          const uint32_t* __restrict__ pred,
                                                          const uint32_t* __restrict__ s_qs, const uint32_t* __restrict__ s_qe,
                                                          const uint32_t* __restrict__ s_ts, const uint32_t* __restrict__ s_te,
@@ -433,7 +438,7 @@ __global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, cons
                                                          uint64_t min_len, double min_ident, uint32_t* __restrict__ hd,
                                                          uint8_t* __restrict__ ok_head, HeadRec* __restrict__ rec,
                                                          unsigned long long* __restrict__ n_heads,
-                                                         const uint32_t* __restrict__ n_chunks_dev = nullptr) {
+                                                         const uint32_t* __restrict__ n_chunks_dev = nullptr, LabelRanked R = LabelRanked{}) {
   // (the pair-resident path, swg_pair.hip: the chunk list's length lives on the device and s_grp is nullptr -- a HeadRec's
   // group is not read there)
   if (n_chunks_dev) n_chunks = min(n_chunks, *n_chunks_dev);
@@ -445,6 +450,7 @@ __global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, cons
   uint32_t* l_te = l_ts + LABEL_FAST;
   uint32_t* l_m = MB ? l_te + LABEL_FAST : nullptr;
   uint32_t* l_b = MB ? l_m + LABEL_FAST : nullptr;
+  __shared__ uint64_t ws64[RANKED ? NT / 64 : 1];  // (the ranked form's scan: the wavefronts' totals)
   if (!MB) s_m = s_b = nullptr;
   constexpr uint16_t NO = 0xffffu;
   uint32_t heads = 0;  // chains headed in this thread's elements (a statistic: all chains, passing the filter or not)
@@ -489,13 +495,16 @@ __global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, cons
         }
       }
       __syncthreads();
+      const uint32_t pad = RANKED ? chunks[c].pad : 0u;
+      const bool rkd = RANKED && (pad & CHUNK_RANKED) != 0u;
+      uint32_t pass = 0;  // (ranked form) bit u: the thread's element of row u heads a passing chain
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t k = (uint32_t)u * NT + threadIdx.x;
         if (k >= len) continue;
         const uint32_t p = b + k;
         if (r_pr[u] != NONE) {  // a member: its head writes its label
-          ok_head[p] = 0;
+          if (!rkd) ok_head[p] = 0;
           continue;
         }
         ++heads;
@@ -518,7 +527,7 @@ __global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, cons
         if (ok) {
           const double wid = chain_weighted_identity(total_length, sm, sb);
           ok = wid >= min_ident;
-          if (ok) {
+          if (ok && !rkd) {
             HeadRec hr;
             hr.qs = qs0;
             hr.qe = qe;
@@ -529,9 +538,74 @@ __global__ __launch_bounds__(NT) void chain_label_kernel(uint32_t n_chunks, cons
             rec[p] = hr;
           }
         }
+        if (rkd) {
+          // the chain's values wait in the head's own slots (a walk reads the members' slots only, and a head's successor slot is
+          // read by nobody but the head).  A passing chain is a kept chain only while both its spans are positive -- always, for
+          // members that are not degenerate; one that is not hands the call over rather than be numbered by a
+          // rule that does not hold for it.
+          if (ok) {
+            pass |= 1u << u;
+            l_qe[k] = qe;
+            l_ts[k] = ts;
+            l_te[k] = qs0;
+            if (!(qs0 < qe && ts < te)) atomicOr(R.flags, R.fallback_bit);
+          } else {
+            succ[k] = NO;  // (what its members will find: the chain fails)
+          }
+          continue;
+        }
         // (pair-resident path, s_grp == nullptr: bits 1 and 2 say whether the chain's query / target span is positive -- what
         // pair_finish's closed-form sweep asks of a passing chain, so that it ranks the chains without reading their records)
         ok_head[p] = ok ? (uint8_t)(s_grp ? 1u : 1u | (qs0 < qe ? 2u : 0u) | (ts < te ? 4u : 0u)) : (uint8_t)0;
+      }
+      if constexpr (RANKED) {
+        if (rkd) {  // (uniform)
+          // the passing heads ranked in position order: row u of the chunk is elements u * NT .. -- one scan of the rows' flags as
+          // 16-bit counters of one word, then the rows before
+          uint64_t packed = 0;
+#pragma unroll
+          for (int u = 0; u < U; ++u) packed |= (uint64_t)((pass >> u) & 1u) << (16 * u);
+          static_assert(U <= 4 && NT < 65536, "the rows' counters share a 64-bit word");
+          uint64_t inc = packed;
+          const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t t = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += t;
+          }
+          if (lane == 63) ws64[w] = inc;
+          __syncthreads();
+          uint64_t off = 0, tot = 0;
+#pragma unroll
+          for (int j = 0; j < NT / 64; ++j) {
+            const uint64_t x = ws64[j];
+            off += j < w ? x : 0ull;
+            tot += x;
+          }
+          const uint64_t ex = off + inc - packed;
+          uint32_t row_base = 0;
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const uint32_t k = (uint32_t)u * NT + threadIdx.x;
+            if ((pass >> u) & 1u) {  // a passing head hands its rank to its members through its own successor slot
+              const uint32_t r = row_base + (uint32_t)((ex >> (16 * u)) & 0xffffu);
+              succ[k] = (uint16_t)r;
+              if ((pad & 1u) == 0u) {  // a '+' chain: the inversion capture's list
+                R.t_qs[b + r] = l_te[k];
+                R.t_qe[b + r] = l_qe[k];
+                reinterpret_cast<uint32_t*>(rec + b)[r] = l_ts[k];
+              }
+            }
+            row_base += (uint32_t)((tot >> (16 * u)) & 0xffffu);
+          }
+          if (threadIdx.x == 0) R.chunk_pass[c] = row_base;
+          __syncthreads();
+          for (uint32_t k = threadIdx.x; k < len; k += NT) {
+            const uint16_t r = succ[l_hd[k]];
+            hd[b + k] = r == NO ? NONE : (uint32_t)r;
+          }
+          continue;
+        }
       }
       __syncthreads();
       for (uint32_t k = threadIdx.x; k < len; k += NT) hd[b + k] = b + l_hd[k];
@@ -821,10 +895,10 @@ int chain_table_build(swg_ctx* ctx, const swg_records* r, const uint8_t* alive, 
     static const uint64_t lper = getenv("SWG_LABEL_BLOCKS") ? (uint64_t)atoi(getenv("SWG_LABEL_BLOCKS")) : 128;  // (work-groups per CU in the grid)
     const uint64_t lb = W.n_chunks < (uint64_t)ctx->num_cu * lper ? W.n_chunks : (uint64_t)ctx->num_cu * lper;
     if (s_m)
-      SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, true><<<(unsigned)lb, LABEL_NT, 0, st>>>((uint32_t)W.n_chunks, W.chunks, pred, s_qs, s_qe, s_ts, s_te,
+      SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, true, false><<<(unsigned)lb, LABEL_NT, 0, st>>>((uint32_t)W.n_chunks, W.chunks, pred, s_qs, s_qe, s_ts, s_te,
                                                                         s_m, s_b, s_grp, min_len, min_ident, hd, ok_head, head_rec, n_heads));
     else
-      SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, false><<<(unsigned)lb, LABEL_NT, 0, st>>>((uint32_t)W.n_chunks, W.chunks, pred, s_qs, s_qe, s_ts, s_te,
+      SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, false, false><<<(unsigned)lb, LABEL_NT, 0, st>>>((uint32_t)W.n_chunks, W.chunks, pred, s_qs, s_qe, s_ts, s_te,
                                                                         s_m, s_b, s_grp, min_len, min_ident, hd, ok_head, head_rec, n_heads));
     SWG_KERNEL_CHECK(ctx);
     only = W.big_member;
@@ -959,16 +1033,20 @@ int chain_table_build(swg_ctx* ctx, const swg_records* r, const uint8_t* alive, 
 int pair_label_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks_dev, const SpecBlock* chunks, const uint32_t* pred,
                       const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te, const uint32_t* s_m,
                       const uint32_t* s_b, uint64_t min_len, double min_ident, uint32_t* hd, uint8_t* ok_head, HeadRec* rec,
-                      unsigned long long* n_heads) {
+                      unsigned long long* n_heads, const LabelRanked* ranked) {
   if (cap_chunks == 0) return SWG_OK;
   static const uint64_t lper = getenv("SWG_LABEL_BLOCKS") ? (uint64_t)atoi(getenv("SWG_LABEL_BLOCKS")) : 128;  // (work-groups per CU in the grid)
   const uint64_t lb = cap_chunks < (uint64_t)ctx->num_cu * lper ? cap_chunks : (uint64_t)ctx->num_cu * lper;
-  if (s_m)
-    SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, true><<<(unsigned)lb, LABEL_NT, 0, ctx->stream>>>(cap_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, s_m, s_b,
+  if (ranked && !s_m)  // (the ranked form is never on together with a weighted identity)
+    SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, false, true><<<(unsigned)lb, LABEL_NT, 0, ctx->stream>>>(cap_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, s_m, s_b,
+                                                                                   nullptr, min_len, min_ident, hd, ok_head, rec, n_heads,
+                                                                                   n_chunks_dev, *ranked));
+  else if (s_m)
+    SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, true, false><<<(unsigned)lb, LABEL_NT, 0, ctx->stream>>>(cap_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, s_m, s_b,
                                                                              nullptr, min_len, min_ident, hd, ok_head, rec, n_heads,
                                                                              n_chunks_dev));
   else
-    SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, false><<<(unsigned)lb, LABEL_NT, 0, ctx->stream>>>(cap_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, s_m, s_b,
+    SWG_LAUNCH(ctx, "chain_label", chain_label_kernel<LABEL_NT, false, false><<<(unsigned)lb, LABEL_NT, 0, ctx->stream>>>(cap_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, s_m, s_b,
                                                                              nullptr, min_len, min_ident, hd, ok_head, rec, n_heads,
                                                                              n_chunks_dev));
   SWG_KERNEL_CHECK(ctx);

@@ -469,6 +469,7 @@ struct PairSortArgs {
   SpecBlock* chunks;
   uint32_t cap_chunks;
   int chunks_by_place;  // the runs are in input order (a plan over runs): a pair's chunks go to slots that follow from its place
+  int ranked;           // the ranked form is on: a pair whose chunks all fit the labelling's LDS layout has its descriptors marked
   uint32_t* long_list;  // indices (into chunks) of the chunks of LABEL_CAP_ELEMS members and more
   uint32_t cap_long;
   PairCounters* C;
@@ -524,6 +525,8 @@ __device__ __forceinline__ void emit_chunks(const PairSortArgs& A, uint32_t rk_r
   const uint32_t last_b = mp_ins && (last == NONE || last < m_plus) ? m_plus : last;  // (last_b, m): chunk count - 1
   const bool last_long = m - last_b >= LABEL_CAP_ELEMS;
   uint32_t n_long = (mp_long ? 1u : 0u) + (last_long ? 1u : 0u), n_long_lt = 0;  // n_long_lt: long chunks in front of chunk n_lt - 1
+  // (the ranked form, DESIGN 3.5b: every chunk of the pair at most LABEL_FAST_ELEMS long, and few enough of them)
+  bool over = (mp_chunk && m_plus - before_mp > LABEL_FAST_ELEMS) || m - last_b > LABEL_FAST_ELEMS || count > RANKED_MAX_CHUNKS;
   {
     uint32_t carry = NONE;
     for (int c0 = 0; c0 < n_cell; c0 += 64) {
@@ -534,6 +537,7 @@ __device__ __forceinline__ void emit_chunks(const PairSortArgs& A, uint32_t rk_r
       const bool lf = v != NONE && b != NONE && v - b >= LABEL_CAP_ELEMS;
       n_long += (uint32_t)__popcll(__ballot(lf));
       n_long_lt += (uint32_t)__popcll(__ballot(lf && v < m_plus));
+      over |= __ballot(v != NONE && b != NONE && v - b > LABEL_FAST_ELEMS) != 0ull;
       carry = (uint32_t)__shfl((int)v, 63 - __clzll(mask), 64);
     }
   }
@@ -548,12 +552,13 @@ __device__ __forceinline__ void emit_chunks(const PairSortArgs& A, uint32_t rk_r
     if (lane == 0) atomicOr(&A.C->flags, PF_FALLBACK);
     return;
   }
+  const uint32_t mark = A.ranked && !over ? CHUNK_RANKED : 0u;
   auto emit = [&](uint32_t k, uint32_t b, uint32_t e, bool is_long, uint32_t lpos) {
     SpecBlock d;
     d.bb = a + b;
     d.be = a + e;
     d.ue = d.be;
-    d.pad = b >= m_plus ? 1u : 0u;
+    d.pad = (b >= m_plus ? 1u : 0u) | mark;
     if (is_long) A.long_list[lslot + lpos] = slot + k;
     A.chunks[slot + k] = d;
   };
@@ -1724,6 +1729,13 @@ struct PairFinishArgs {
   const uint8_t* kept_in;      // a scaffold sweep with limits ran over the chain table (pair_chains_kernel): kept flag per chain ...
   const uint32_t* chain_base;  // ... whose entries of pair k start here, in the pair's all_chains order; np[2k], np[2k + 1]: the pair's
   const uint32_t* np;          //     passing chains per strand
+  // the ranked form (chunks == nullptr: off): the chunk list with pair_sort's marks, the labelling's count of passing
+  // chains per chunk, the HeadRec array as words (a marked chunk's stretch holds its passing '+' chains' t_start values)
+  const SpecBlock* chunks;
+  uint32_t cap_chunks;
+  const uint32_t* chunk_pass;
+  uint32_t* rec_w;
+  unsigned long long* ranked_stat;  // (SWG_DEBUG) pairs and records that took the ranked form, or nullptr
   uint32_t* fin;       // by position in the pair, or nullptr: the record's result -- status << 30 | pair-local chain number -- instead
                        //   of scattered writes to the output columns (pair_out_kernel brings them to input order through LDS)
   uint32_t* anum;      // by position in the pair: the anchor's (pair-local) chain number, 0 = a rescue candidate, NEVER = never rescued
@@ -2077,91 +2089,226 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
     n_deg = block_sum<NT>(cd, ws);
     kP = block_sum<NT>(cp, ws);
   };
-  sweep(false);
-  const uint32_t n_ch = n_pass0 + n_pass1;
-  if (n_ch == 0) {
-    if (tid == 0) A.sum[rk] = sm;
-    return;
-  }
-  if (n_deg) {  // a chain with an empty span: the rule needs the counts
-    all_q = n_ch <= 1;
-    all_t = (all_q ? n_ch : n_q) <= 1;
-    __syncthreads();
-    sweep(true);
-  }
-  const uint32_t kM = n_kept - kP;
   // the reference's all_chains order inside the pair: the (query, target, strand) group that appears first in the metadata
-  const bool plus_first = pi.first_mem[0] < pi.first_mem[1];
-  sm.n_pass = n_ch;
-  sm.n_kept = n_kept;
-  sm.minmem = n_pass0 && n_pass1 ? (pi.first_mem[0] < pi.first_mem[1] ? pi.first_mem[0] : pi.first_mem[1]) : (n_pass0 ? pi.first_mem[0] : pi.first_mem[1]);
-  if (tid == 0) A.sum[rk] = sm;
-  if (n_kept == 0) return;
-  __syncthreads();  // head_num / the chain list of the whole pair are written
+  const bool plus_first = plus_first0;
+  uint32_t kM = 0, out = 0;
   auto local_number = [&](uint32_t r, bool minus) -> uint32_t {  // 1-based, in the pair's all_chains order
     if (plus_first) return r + 1;
     return minus ? r - kP + 1 : r + kM + 1;
   };
-  FT_STAMP(0);
-  // ---- anchors: the members of kept chains (paf_filter.rs:517-528)
-  uint32_t out = 0;
-  for (uint32_t p0 = 0; p0 < m; p0 += NT * US) {
-    uint32_t h[US], idx[US], r[US];
-#pragma unroll
-    for (int u = 0; u < US; ++u) {
-      const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
-      h[u] = p < m ? A.hd[a + p] : a;
-      idx[u] = (p < m && !A.fin) ? A.s_idx[a + p] : 0u;
+  // ---- the ranked form: pair_sort marked the pair's chunk descriptors, and the labelling left in hd every member's
+  // rank among the passing chains of its chunk, per chunk their number, and per passing '+' chain its three values at (chunk
+  // begin + rank).  Under the flags that turn the form on a passing chain is a kept chain, so a chain's rank in the pair is its
+  // rank in its chunk plus the passing chains of the chunks before: no flags to read, no scan over the positions, no record to
+  // fetch.  A pair's chunks tile its positions in order, '+' first, in a stretch of the list that follows from its place.
+  const uint32_t slot0 = A.chunks ? a / PAIR_CELL + 2u * rk : 0u;
+  const bool ranked = A.chunks && slot0 < A.cap_chunks && (A.chunks[slot0].pad & CHUNK_RANKED) != 0u;
+  if (ranked) {
+    __shared__ uint32_t rk_beg[RANKED_MAX_CHUNKS], rk_base[RANKED_MAX_CHUNKS + 1], rk_n[3];
+    if (A.ranked_stat && tid == 0) {
+      atomicAdd(&A.ranked_stat[0], 1ull);
+      atomicAdd(&A.ranked_stat[1], (unsigned long long)run.n);
     }
+    if (tid < 64) {  // the chunk stretch: begins, and the exclusive prefix of the counts
+      uint32_t lim = run.n / PAIR_CELL + 2u;  // (the next pair's stretch begins at least this far on)
+      lim = lim < RANKED_MAX_CHUNKS ? lim : RANKED_MAX_CHUNKS;
+      lim = lim < A.cap_chunks - slot0 ? lim : A.cap_chunks - slot0;
+      uint32_t carry = 0, nck = 0, kp = 0;
+      for (uint32_t j0 = 0; j0 < lim; j0 += 64) {
+        const uint32_t j = j0 + (uint32_t)tid;
+        SpecBlock d;
+        d.ue = d.bb = d.be = d.pad = 0u;
+        if (j < lim) d = A.chunks[slot0 + j];
+        const bool valid = d.be > d.bb;  // (the list is zeroed per call: the slots behind the pair's last chunk are empty)
+        const uint32_t cnt = valid ? A.chunk_pass[slot0 + j] : 0u;
+        uint32_t inc = cnt;
 #pragma unroll
-    for (int u = 0; u < US; ++u) r[u] = A.head_num[h[u]];
-#pragma unroll
-    for (int u = 0; u < US; ++u) {
-      const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
-      uint32_t an = 0;
-      if (p < m && r[u] < NEVER) {
-        an = local_number(r[u], h[u] - a >= m_plus);
-        if (!A.fin) {
-          A.chain[idx[u]] = an;
-          A.status[idx[u]] = SWG_ST_SCAFFOLD;
+        for (int dd = 1; dd < 64; dd <<= 1) {
+          const uint32_t t = __shfl_up(inc, dd, 64);
+          if (tid >= dd) inc += t;
         }
-        ++out;
-      } else if (r[u] == NEVER) {
-        an = NEVER;
+        if (valid) {
+          rk_beg[j] = d.bb - a;
+          rk_base[j] = carry + inc - cnt;
+        }
+        kp += valid && (d.pad & 1u) == 0u ? cnt : 0u;
+        nck += (uint32_t)__popcll(__ballot(valid));
+        carry += __shfl(inc, 63, 64);
       }
-      if (A.fin && p < m) A.fin[a + p] = (an != 0u && an != NEVER) ? ((uint32_t)SWG_ST_SCAFFOLD << 30) | an : 0u;
-      if (A.rescue_d && p < m) A.anum[a + p] = an;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) kp += __shfl_xor(kp, o, 64);
+      if (tid == 0) {
+        rk_base[nck] = carry;
+        rk_n[0] = nck;
+        rk_n[1] = kp;
+        rk_n[2] = carry;
+      }
     }
-  }
-  // the alive non-members: rescue candidates unless the inversion capture takes them
-  for (uint32_t p = m + (uint32_t)tid; p < M; p += NT) {
-    if (A.rescue_d) A.anum[a + p] = 0u;
-    if (A.fin) A.fin[a + p] = 0u;
+    __syncthreads();
+    const uint32_t nck = rk_n[0];
+    kP = rk_n[1];
+    n_kept = rk_n[2];
+    kM = n_kept - kP;
+    if (n_kept == 0) {
+      if (tid == 0) A.sum[rk] = sm;
+      return;
+    }
+    sm.n_pass = n_kept;
+    sm.n_kept = n_kept;
+    sm.minmem = kP && kM ? (pi.first_mem[0] < pi.first_mem[1] ? pi.first_mem[0] : pi.first_mem[1]) : (kP ? pi.first_mem[0] : pi.first_mem[1]);
+    if (tid == 0) A.sum[rk] = sm;
+    FT_STAMP(0);
+    // ---- anchors: a member's chunk is the last one that begins at or before it.  A thread's positions only ever grow, so it
+    // follows the chunks with a cursor: the next chunk's begin and this one's base stay in registers between crossings
+    uint32_t cj = 0, c_base = rk_base[0], c_next = nck > 1u ? rk_beg[1] : NONE;
+    for (uint32_t p0 = 0; p0 < m; p0 += NT * US) {
+      uint32_t r[US];
+#pragma unroll
+      for (int u = 0; u < US; ++u) {
+        const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
+        r[u] = p < m ? A.hd[a + p] : NONE;
+      }
+#pragma unroll
+      for (int u = 0; u < US; ++u) {
+        const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
+        if (p >= m) continue;
+        while (p >= c_next) {  // (p < m < NONE: ends at the last chunk)
+          ++cj;
+          c_base = rk_base[cj];
+          c_next = cj + 1u < nck ? rk_beg[cj + 1u] : NONE;
+        }
+        uint32_t f = 0u;
+        if (r[u] != NONE) {
+          f = ((uint32_t)SWG_ST_SCAFFOLD << 30) | local_number(c_base + r[u], p >= m_plus);
+          ++out;
+        }
+        A.fin[a + p] = f;
+      }
+    }
+    for (uint32_t p = m + (uint32_t)tid; p < M; p += NT) A.fin[a + p] = 0u;
+    // ---- the kept '+' chains, chunk after chunk, for the inversion capture: chain c of the pair is chain c - base of the last
+    // chunk whose base is at or below c.  More than KP of them go to lists in memory: q_start and q_end in place -- chain c
+    // comes from position (chunk begin + c - base) >= c, and a round's values are all loaded before the first is stored -- the
+    // t_start values likewise to the head of the pair's stretch of HeadRec words, the running maxima behind them.
+    if (!A.scaffolds_only && kP > 0 && M > m_plus) {
+      const bool in_lds = kP <= (uint32_t)KP;
+      uint32_t *const g_qs = A.f_qs + a, *const g_qe = A.f_qe + a, *const g_ts = A.rec_w + (size_t)8 * a;
+      for (uint32_t c0 = 0; c0 < kP; c0 += NT) {
+        const uint32_t c = c0 + (uint32_t)tid;
+        uint32_t v_qs = 0, v_qe = 0, v_ts = 0;
+        if (c < kP) {
+          uint32_t lo = 0, hi = nck;
+          while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (rk_base[mid] <= c) lo = mid; else hi = mid;
+          }
+          const uint32_t b = rk_beg[lo], i = c - rk_base[lo];
+          v_qs = A.f_qs[a + b + i];
+          v_qe = A.f_qe[a + b + i];
+          v_ts = A.rec_w[(size_t)8 * (a + b) + i];
+        }
+        if (in_lds) {
+          if (c < kP) {
+            l_qs[c] = v_qs;
+            l_qe[c] = v_qe;
+            l_ts[c] = v_ts;
+          }
+        } else {
+          __syncthreads();
+          if (c < kP) {
+            g_qs[c] = v_qs;
+            g_qe[c] = v_qe;
+            g_ts[c] = v_ts;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  } else {
+    sweep(false);
+    const uint32_t n_ch = n_pass0 + n_pass1;
+    if (n_ch == 0) {
+      if (tid == 0) A.sum[rk] = sm;
+      return;
+    }
+    if (n_deg) {  // a chain with an empty span: the rule needs the counts
+      all_q = n_ch <= 1;
+      all_t = (all_q ? n_ch : n_q) <= 1;
+      __syncthreads();
+      sweep(true);
+    }
+    kM = n_kept - kP;
+    sm.n_pass = n_ch;
+    sm.n_kept = n_kept;
+    sm.minmem = n_pass0 && n_pass1 ? (pi.first_mem[0] < pi.first_mem[1] ? pi.first_mem[0] : pi.first_mem[1]) : (n_pass0 ? pi.first_mem[0] : pi.first_mem[1]);
+    if (tid == 0) A.sum[rk] = sm;
+    if (n_kept == 0) return;
+    __syncthreads();  // head_num / the chain list of the whole pair are written
+    FT_STAMP(0);
+    // ---- anchors: the members of kept chains (paf_filter.rs:517-528)
+    for (uint32_t p0 = 0; p0 < m; p0 += NT * US) {
+      uint32_t h[US], idx[US], r[US];
+#pragma unroll
+      for (int u = 0; u < US; ++u) {
+        const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
+        h[u] = p < m ? A.hd[a + p] : a;
+        idx[u] = (p < m && !A.fin) ? A.s_idx[a + p] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < US; ++u) r[u] = A.head_num[h[u]];
+#pragma unroll
+      for (int u = 0; u < US; ++u) {
+        const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
+        uint32_t an = 0;
+        if (p < m && r[u] < NEVER) {
+          an = local_number(r[u], h[u] - a >= m_plus);
+          if (!A.fin) {
+            A.chain[idx[u]] = an;
+            A.status[idx[u]] = SWG_ST_SCAFFOLD;
+          }
+          ++out;
+        } else if (r[u] == NEVER) {
+          an = NEVER;
+        }
+        if (A.fin && p < m) A.fin[a + p] = (an != 0u && an != NEVER) ? ((uint32_t)SWG_ST_SCAFFOLD << 30) | an : 0u;
+        if (A.rescue_d && p < m) A.anum[a + p] = an;
+      }
+    }
+    // the alive non-members: rescue candidates unless the inversion capture takes them
+    for (uint32_t p = m + (uint32_t)tid; p < M; p += NT) {
+      if (A.rescue_d) A.anum[a + p] = 0u;
+      if (A.fin) A.fin[a + p] = 0u;
+    }
   }
   FT_STAMP(1);
   // ---- inversion capture (paf_filter.rs:535-597): a '-' record that is not an anchor joins the first kept '+' chain of its
   // pair whose window and diagonal it sits on
   if (!A.scaffolds_only && kP > 0 && M > m_plus) {
     const bool in_lds = kP <= (uint32_t)KP;
+    // the kept '+' chains beyond KP of them: lists in memory at the pair's offset (the ranked form: t_start and the running
+    // maxima in the pair's stretch of HeadRec words)
+    uint32_t *const g_qs = A.f_qs + a, *const g_qe = A.f_qe + a;
+    uint32_t* const g_ts = ranked ? A.rec_w + (size_t)8 * a : A.f_ts + a;
+    uint32_t* const g_pm = ranked ? g_ts + m : A.f_pm + a;
     // running maximum of the chains' ends
     uint64_t carry = 0;
     for (uint32_t c0b = 0; c0b < kP; c0b += NT) {
       const uint32_t c = c0b + tid;
-      const uint64_t v = c < kP ? (uint64_t)(in_lds ? l_qe[c] : A.f_qe[a + c]) : 0ull;
+      const uint64_t v = c < kP ? (uint64_t)(in_lds ? l_qe[c] : g_qe[c]) : 0ull;
       uint64_t tot;
       uint64_t ex = block_excl_max<NT>(v, ws64, &tot);
       ex = ex > carry ? ex : carry;
       if (c < kP) {
         const uint32_t pm = (uint32_t)(v > ex ? v : ex);
-        if (in_lds) l_pm[c] = pm; else A.f_pm[a + c] = pm;
+        if (in_lds) l_pm[c] = pm; else g_pm[c] = pm;
       }
       carry = tot > carry ? tot : carry;
     }
     __syncthreads();  // the running maxima, and the anchors' chain numbers
-    const uint32_t* __restrict__ c_qs = in_lds ? l_qs : A.f_qs + a;
-    const uint32_t* __restrict__ c_qe = in_lds ? l_qe : A.f_qe + a;
-    const uint32_t* __restrict__ c_ts = in_lds ? l_ts : A.f_ts + a;
-    const uint32_t* __restrict__ c_pm = in_lds ? l_pm : A.f_pm + a;
+    const uint32_t* __restrict__ c_qs = in_lds ? l_qs : g_qs;
+    const uint32_t* __restrict__ c_qe = in_lds ? l_qe : g_qe;
+    const uint32_t* __restrict__ c_ts = in_lds ? l_ts : g_ts;
+    const uint32_t* __restrict__ c_pm = in_lds ? l_pm : g_pm;
     const uint64_t gap = A.gap, max_dev = A.max_dev;
     for (uint32_t p = m_plus + tid; p < M; p += NT) {
       const uint32_t iw = A.s_idx[a + p];
@@ -3001,7 +3148,16 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   PairSum* sum = swg_alloc<PairSum>(ctx, n_runs);
   uint32_t* n_out_pair = swg_alloc<uint32_t>(ctx, n_runs);
   const uint32_t cap_chunks = n / PAIR_CELL + 2 * n_runs + 16;  // (emit_chunks: a pair's stretch of the list follows from its place)
-  SpecBlock* chunks = swg_alloc<SpecBlock>(ctx, cap_chunks);
+  // The ranked form: under the default flags -- no limits on the scaffold filter, no rescue, no weighted identity,
+  // the unlimited mapping sweep taken as the identity (a degenerate alive record hands the call over), a plan over runs -- a
+  // chain that passes the span filter is a kept chain, and the labelling ranks the kept chains of the pairs whose chunks it
+  // labels in LDS where it has them.  SWG_PAIR_RANKED=0: every pair takes pair_finish's own ranking.
+  static const bool ranked_knob = !(getenv("SWG_PAIR_RANKED") && atoi(getenv("SWG_PAIR_RANKED")) == 0);
+  const bool ranked = ranked_knob && !limited && !rescue && !need_wid && sweep_assumed_identity && !by_hash;
+  // (the passing chains per chunk lie behind the chunk list: zeroed with it)
+  SpecBlock* chunks = swg_alloc<SpecBlock>(ctx, (size_t)cap_chunks + (ranked ? ((size_t)cap_chunks + 3) / 4 : 0));
+  uint32_t* chunk_pass = ranked ? reinterpret_cast<uint32_t*>(chunks + cap_chunks) : nullptr;
+  unsigned long long* ranked_stat = ranked && dbg ? swg_alloc<unsigned long long>(ctx, 2) : nullptr;
   const uint32_t cap_long = n / LABEL_CAP_ELEMS + 1;
   uint32_t* long_list = swg_alloc<uint32_t>(ctx, cap_long);
   SWG_CHECK_ARENA(ctx);
@@ -3017,7 +3173,8 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   }
   SWG_HIP(ctx, hipMemsetAsync(n_out_pair, 0, (size_t)n_runs * sizeof(uint32_t), st));
   if (!by_hash) {  // (emit_chunks: fixed slots, the list's length is its capacity)
-    SWG_HIP(ctx, hipMemsetAsync(chunks, 0, (size_t)cap_chunks * sizeof(SpecBlock), st));
+    SWG_HIP(ctx, hipMemsetAsync(chunks, 0, (size_t)cap_chunks * (sizeof(SpecBlock) + (ranked ? sizeof(uint32_t) : 0)), st));
+    if (ranked_stat) SWG_HIP(ctx, hipMemsetAsync(ranked_stat, 0, 2 * sizeof(unsigned long long), st));
     SWG_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&C->n_chunks), (int)cap_chunks, 1, st));
   }
   PairSortArgs SA{};
@@ -3031,7 +3188,7 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   SA.perm = perm;
   SA.orig = plan_in->orig;
   SA.code = code; SA.s_qs = s_qs; SA.s_qe = s_qe; SA.s_ts = s_ts; SA.s_te = s_te; SA.s_m = need_wid ? s_m : nullptr; SA.s_b = need_wid ? s_b : nullptr; SA.s_idx = s_idx; SA.pred = pred;
-  SA.info = info; SA.chunks = chunks; SA.cap_chunks = cap_chunks; SA.chunks_by_place = by_hash ? 0 : 1; SA.long_list = long_list; SA.cap_long = cap_long; SA.C = C; SA.gl_first = gl_first; SA.seq_genome_last = r->seq_genome_last;
+  SA.info = info; SA.chunks = chunks; SA.cap_chunks = cap_chunks; SA.chunks_by_place = by_hash ? 0 : 1; SA.ranked = ranked ? 1 : 0; SA.long_list = long_list; SA.cap_long = cap_long; SA.C = C; SA.gl_first = gl_first; SA.seq_genome_last = r->seq_genome_last;
   if (by_hash) {
     for (int c = 2; c >= 0; --c) {
       if (!ncls[c]) continue;
@@ -3085,9 +3242,10 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
     SWG_TRY(pair_walk_launch(ctx, cap_chunks, &C->n_chunks, chunks, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred));
     return SWG_OK;
   };
+  const LabelRanked LR{chunk_pass, s_m, s_b, &C->flags, PF_FALLBACK};  // (the two columns are not sorted without a weighted identity)
   auto short_label = [&]() -> int {
     return pair_label_launch(ctx, cap_chunks, &C->n_chunks, chunks, pred, s_qs, s_qe, s_ts, s_te, lab_m, lab_b, cfg->min_scaffold_length,
-                             cfg->min_scaffold_identity, hd, ok_head, head_rec, &C->n_heads);
+                             cfg->min_scaffold_identity, hd, ok_head, head_rec, &C->n_heads, ranked ? &LR : nullptr);
   };
   auto long_walk = [&](hipStream_t ls) -> int {
     SWG_TRY(pair_walk_long_launch(ctx, ls, cap_long, &C->n_long, long_list, chunks, n, s_qs, s_qe, s_ts, s_te, cfg->scaffold_gap, bps, pred,
@@ -3206,6 +3364,8 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
   FA.anum = anum;
   FA.n_out_pair = n_out_pair;
   FA.fin = fin;
+  FA.chunks = ranked ? chunks : nullptr; FA.cap_chunks = cap_chunks; FA.chunk_pass = chunk_pass; FA.rec_w = reinterpret_cast<uint32_t*>(head_rec);
+  FA.ranked_stat = ranked_stat;
   for (int c = 0; c < 3; ++c) {  // (the two largest classes in one launch, the very long pairs first, as pair_chains above)
     const uint32_t nb = c == 2 ? ncls[2] + ncls[3] : ncls[c];
     if (!nb) continue;
@@ -3313,6 +3473,13 @@ int scaffold_stage_pairs(swg_ctx* ctx, const swg_records* r, const swg_config* c
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fin_t), z, sizeof z);
   }
 #endif
+  if (ranked_stat) {
+    uint64_t hr[2];
+    SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<const uint64_t*>(ranked_stat), hr, 2));
+    fprintf(stderr, "[swg] pair path: ranked form: %llu of %u pairs, %llu of %u records\n", (unsigned long long)hr[0], n_runs, (unsigned long long)hr[1], n);
+  } else if (dbg) {
+    fprintf(stderr, "[swg] pair path: ranked form: off\n");
+  }
   if (stats) {
     stats->n_retained = hc[5];
     stats->n_swept = hc[6];

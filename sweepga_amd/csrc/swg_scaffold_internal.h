@@ -174,6 +174,19 @@ __device__ __forceinline__ double chain_weighted_identity(uint64_t total_length,
 }
 #endif
 constexpr uint32_t LABEL_CAP_ELEMS = WALK_CHUNK + BIG_UNIT;  // chain_label_kernel: a chunk holds fewer elements than this
+constexpr uint32_t LABEL_FAST_ELEMS = 1536;                  // ... and one of at most this many is labelled in LDS
+// The ranked form of the pair stage (swg_pair.hip): pair_sort marks every chunk descriptor of a pair whose chunks
+// all fit the labelling's LDS layout (SpecBlock::pad bit 1; bit 0 stays the strand), chain_label_kernel ranks the passing
+// chains of such a chunk where it labels them, and pair_finish numbers the pair from the chunks' counts.
+constexpr uint32_t CHUNK_RANKED = 2u;
+constexpr uint32_t RANKED_MAX_CHUNKS = 128;  // chunks of a marked pair (pair_finish stages them in LDS)
+struct LabelRanked {
+  uint32_t* chunk_pass;      // [cap_chunks], zeroed: passing chains per chunk
+  uint32_t *t_qs, *t_qe;     // per passing '+' chain, at (chunk begin + rank): q_start, chain q_end; the chain's t_start is word
+                             //   `rank` of the chunk's stretch of the HeadRec array (unused otherwise: no HeadRec is written)
+  uint32_t* flags;           // a passing chain with an empty span: *flags |= fallback_bit
+  uint32_t fallback_bit;
+};
 
 // Chunk-list launchers for the pair-resident path (swg_chain.hip, swg_chain_table.hip)
 int pair_walk_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks_dev, const SpecBlock* desc, const uint32_t* s_qs,
@@ -186,7 +199,7 @@ int pair_walk_long_launch(swg_ctx* ctx, hipStream_t st, uint32_t cap_long, const
 int pair_label_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks_dev, const SpecBlock* chunks, const uint32_t* pred,
                       const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te, const uint32_t* s_m,
                       const uint32_t* s_b, uint64_t min_len, double min_ident, uint32_t* hd, uint8_t* ok_head, HeadRec* rec,
-                      unsigned long long* n_heads);
+                      unsigned long long* n_heads, const LabelRanked* ranked = nullptr);  // (ranked: marked chunks take the ranked form)
 // the chunks of LABEL_CAP_ELEMS members and more (long_list), labelled one work-group each, on `st`
 int pair_label_long_launch(swg_ctx* ctx, hipStream_t st, uint32_t cap_long, const uint32_t* n_long_dev, const uint32_t* long_list, const SpecBlock* chunks,
                            const uint32_t* pred, const uint32_t* s_qs, const uint32_t* s_qe, const uint32_t* s_ts, const uint32_t* s_te,
