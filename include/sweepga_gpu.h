@@ -1106,6 +1106,93 @@ int swg_mosaic_records_device(swg_ctx* ctx, const swg_records* rec, const uint32
 int swg_paf_mosaic(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t set, int by_length, char** out_text,
                    uint64_t* out_len);
 
+/* ---- gaps: the indel at every link of a kept chain, and every captured inversion (no reference counterpart)
+ * A pure function of the record columns (q_id, t_id, the four coordinates and strand; 32-bit layout), status[n] and chain[n] as
+ * swg_filter* writes them, seq_genome[n_seq] and min_size.  Every value is an integer, every comparison exact.
+ *   takes part  a record with status == SWG_ST_SCAFFOLD and chain != 0 (rescued, unassigned and dropped records take no part).
+ *   strand      of a chain: '+' if any record of it that takes part is '+', else '-'.  core = its records on that strand,
+ *               inverted = the '-' records of a '+' chain (swg_block's rule).  All records of a chain share (q_id, t_id).
+ *   order       inside a chain (q_start, record index) ascending: the reference's chaining order (src/paf_filter.rs:774-866), so
+ *               the consecutive core records of a filter's own output are the links chaining made.
+ *   link        for a core record b with an earlier core record in its chain, a = the nearest such (inverted records between
+ *               the two are skipped): dq = q_start[b] - q_end[a]; dt = t_start[b] - t_end[a] on a '+' chain and t_start[a] -
+ *               t_end[b] on a '-' chain; both signed 64-bit, negative = overlap; size = dq - dt.
+ *   link row    when |size| >= min_size (min_size 0: every link): kind = SWG_GAP_INS for size > 0, SWG_GAP_DEL for size < 0,
+ *               SWG_GAP_EVEN for size == 0; left = a, right = b; q_lo / q_hi = min / max of (q_end[a], q_start[b]); t_lo / t_hi
+ *               = min / max of the two facing target ends ('+': t_end[a], t_start[b]; '-': t_start[a], t_end[b]); flags bit 0 =
+ *               dq < 0, bit 1 = dt < 0.  dq, dt and size follow from the row (|dq| = q_hi - q_lo, its sign is the flag).
+ *   inversion   every inverted record r with q_end - q_start >= min_size: kind = SWG_GAP_INV, left = right = r, its own query
+ *               and target interval, flags 0.
+ *   row order   (chain, q_start[right], right) ascending; link rows and inversion rows interleave.
+ *   summary     per ORDERED genome pair (seq_genome[q_id], seq_genome[t_id]): links = all links whatever min_size; n_ins,
+ *               ins_bases = sum(size); n_del, del_bases = sum(-size); n_inv, inv_bases = sum(q_end - q_start) -- the last six
+ *               over the rows only.  A pair has an entry when links or n_inv is non-zero; ascending (q_genome, t_genome).
+ *   spectrum    [2][33], row 0 INS and row 1 DEL, over the rows: bin = bit length of |size| (bin k: 2^(k-1) <= |size| < 2^k),
+ *               the last bin taking everything from 2^31 (|size| reaches 2^33 - 2).  Bin 0 is empty; SWG_GAP_EVEN is not counted.
+ * Nothing depends on the order of the records beyond the index tie-break, nor on a launch shape.  `want`: SWG_GAPS_ROWS writes
+ * n_rows and, under the capacity protocol of swg_breadth_counts, the rows (n_rows > capacity still returns SWG_OK and leaves
+ * `rows` alone); SWG_GAPS_SUMMARY writes n_pairs, the pairs under the same protocol, and all 66 entries of a non-NULL spectrum.
+ * Errors: a NULL context (there is no CPU path), reserved != 0, want == 0 or a bit beyond the two, a NULL column, a chain whose
+ * records that take part name two (q_id, t_id) pairs (the message names the chain), a sequence id >= n_seq or a genome id >=
+ * n_genome: SWG_ERR_INVALID; n >= 2^31 records or a chain number of 2^32 - 1: SWG_ERR_RANGE.  Scratch comes from the context's
+ * arena, SWG_ERR_OOM when the memory limit does not hold it: 24 bytes per record for the sort (two 8-byte key and two 4-byte value
+ * buffers) plus the radix sort's histograms, 6 bytes per record that takes part (class, row flag, predecessor), 4 bytes per chain
+ * NUMBER (the strand table is dense in the chain number: its largest value sizes it), 36 bytes per row, and the genome-pair
+ * table (sized by what occurs).  swg_gaps_records stages its host columns there too: 30 more bytes per record. */
+#define SWG_GAP_EVEN 0u
+#define SWG_GAP_INS 1u
+#define SWG_GAP_DEL 2u
+#define SWG_GAP_INV 3u
+typedef struct swg_gap_row {
+  uint32_t chain;       /* N of ch:Z:chain_N */
+  uint32_t left, right; /* record numbers: a and b of a link, the record itself for an inversion */
+  uint32_t q_lo, q_hi;
+  uint32_t t_lo, t_hi;
+  uint8_t kind;         /* SWG_GAP_* */
+  uint8_t flags;        /* bit 0: dq < 0, bit 1: dt < 0 */
+  uint16_t reserved;    /* 0 */
+} swg_gap_row; /* 32 bytes, no implicit padding */
+typedef struct swg_gap_pair {
+  uint32_t q_genome, t_genome; /* ORDERED pair of genome ids (query genome, target genome) */
+  uint64_t links;              /* all links of the pair, whatever min_size */
+  uint64_t n_ins, ins_bases;
+  uint64_t n_del, del_bases;
+  uint64_t n_inv, inv_bases;
+} swg_gap_pair; /* 64 bytes */
+#define SWG_GAPS_ROWS 1u
+#define SWG_GAPS_SUMMARY 2u
+#define SWG_GAPS_BINS 33
+typedef struct swg_gaps_request {
+  uint32_t want;          /* the two bits above */
+  uint32_t min_size;
+  uint64_t n_rows;        /* out (rows bit) */
+  uint64_t capacity;      /* in: entries `rows` can hold */
+  swg_gap_row* rows;      /* in: caller-owned [capacity] or NULL; written only when n_rows <= capacity */
+  uint64_t n_pairs;       /* out (summary bit) */
+  uint64_t pair_capacity; /* in: entries `pairs` can hold */
+  swg_gap_pair* pairs;    /* in: caller-owned [pair_capacity] or NULL; written only when n_pairs <= pair_capacity */
+  uint64_t* spectrum;     /* in (summary bit): caller-owned [2 * SWG_GAPS_BINS] or NULL; fully written */
+  uint64_t reserved;      /* 0 */
+} swg_gaps_request; /* 72 bytes, no implicit padding */
+/* rec: host pointers; status[n], chain[n] and seq_genome[rec->n_seq] on the host. */
+int swg_gaps_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const uint32_t* chain, const uint32_t* seq_genome,
+                     uint32_t n_genome, swg_gaps_request* req);
+/* The same with the seven columns of rec, status, chain and seq_genome in device memory of ctx's GPU (as swg_filter_device
+ * leaves them: no copy in between); the request and its arrays stay on the host. */
+int swg_gaps_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const uint32_t* chain, const uint32_t* seq_genome,
+                            uint32_t n_genome, swg_gaps_request* req);
+/* Both texts of an open PAF under its last-'#' genome map from ONE device call (release each with swg_free); a text is asked
+ * for by a non-NULL rows_text / summary_text (its length pointer must then be non-NULL too).  Tab-separated:
+ *   rows     header `#query q_start q_end target t_start t_end kind size chain dq dt left right`, then one line per row:
+ *            names from the handle, q_lo q_hi, t_lo t_hi, kind INS | DEL | INV | EVEN, size dq dt as signed decimals (INV: size =
+ *            the query length, dq = dt = 0), left and right as 0-based record numbers.
+ *   summary  header `#query_genome target_genome links ins ins_bases del del_bases inv inv_bases`, one line per genome pair
+ *            (names keep their trailing '#'), then one line `#spectrum KIND lo hi count` per non-empty bin (lo and hi inclusive).
+ * A PAF without records, or a status and chain without a chain that takes part, gives the header-only texts and needs no
+ * device (ctx may be NULL then).  A handle with rebased columns: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+int swg_paf_gaps(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const uint32_t* chain, uint32_t min_size, char** rows_text,
+                 uint64_t* rows_len, char** summary_text, uint64_t* summary_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -43,7 +43,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot",
            "swg_lift_records", "swg_lift_records_device", "swg_paf_lift",
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
-           "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic"]
+           "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
+           "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps"]
 
 
 class SwgError(RuntimeError):
@@ -198,6 +199,22 @@ class SwgDepthList(C.Structure):
 
 class SwgSharingRequest(C.Structure):
     _fields_ = [("want", C.c_uint32), ("reserved", C.c_uint32), ("set", SwgDepthList * 2)]   # set[ALL, KEPT]
+
+
+class SwgGapRow(C.Structure):
+    _fields_ = [("chain", C.c_uint32), ("left", C.c_uint32), ("right", C.c_uint32), ("q_lo", C.c_uint32), ("q_hi", C.c_uint32),
+                ("t_lo", C.c_uint32), ("t_hi", C.c_uint32), ("kind", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class SwgGapPair(C.Structure):
+    _fields_ = [("q_genome", C.c_uint32), ("t_genome", C.c_uint32), ("links", C.c_uint64), ("n_ins", C.c_uint64), ("ins_bases", C.c_uint64),
+                ("n_del", C.c_uint64), ("del_bases", C.c_uint64), ("n_inv", C.c_uint64), ("inv_bases", C.c_uint64)]
+
+
+class SwgGapsRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("min_size", C.c_uint32), ("n_rows", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgGapRow)),
+                ("n_pairs", C.c_uint64), ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgGapPair)), ("spectrum", C.POINTER(C.c_uint64)),
+                ("reserved", C.c_uint64)]
 
 
 class SwgMosaicRow(C.Structure):
@@ -465,6 +482,13 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgMosaicRequest)]
     lib.swg_paf_mosaic.restype = C.c_int
     lib.swg_paf_mosaic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_gaps_records", "swg_gaps_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SwgGapsRequest)]
+    lib.swg_paf_gaps.restype = C.c_int
+    lib.swg_paf_gaps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_dotplot_records", "swg_dotplot_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

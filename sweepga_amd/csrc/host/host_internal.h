@@ -111,6 +111,12 @@ std::string swg_mosaic_rows_text(const swg_paf* p, const swg_records* rec, const
 // `genome other_genome bases`, one line per non-zero entry of share ([G * G], G = genome_name.size()), then `#total <bases>`
 std::string swg_mosaic_share_text(const std::vector<std::string>& genome_name, const std::vector<uint64_t>& share, uint64_t bases);
 
+// ---- gaps (swg_gaps.hip: kernels and seams; gaps_text.cpp: the two texts of swg_paf_gaps) ----
+// header, then one line per row: query q_lo q_hi target t_lo t_hi kind size chain dq dt left right (rec: the handle's records)
+std::string swg_gaps_rows_text(const swg_paf* p, const swg_records* rec, const std::vector<swg_gap_row>& rows);
+// header, one line per genome pair (ascending), then `#spectrum KIND lo hi count` per non-empty bin of spectrum [2][SWG_GAPS_BINS]
+std::string swg_gaps_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_gap_pair>& pairs, const uint64_t* spectrum);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

@@ -356,6 +356,30 @@ void write_mosaic(const std::string& rows_path, const std::string& share_path, s
   }
 }
 
+// --gaps / --gaps-summary: the rows and the summary of swg_paf_gaps (the indel at every link of a kept chain, the captured
+// inversions), both from one device call when both are asked for.  "-" = standard error.  status == NULL: no filter ran, there
+// are no chains, the files hold their header lines.
+void write_gaps(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
+                const uint32_t* chain, uint32_t min_size) {
+  char* text[2] = {nullptr, nullptr};
+  uint64_t len[2] = {0, 0};
+  const std::vector<uint8_t> none(swg_paf_records(paf)->n + 1, 0);  // (no filter: nothing takes part)
+  const std::vector<uint32_t> zero(status ? 1 : none.size(), 0);
+  if (swg_paf_gaps(ctx, paf, status ? status : none.data(), status ? chain : zero.data(), min_size, rows_path.empty() ? nullptr : &text[0],
+                   rows_path.empty() ? nullptr : &len[0], summary_path.empty() ? nullptr : &text[1], summary_path.empty() ? nullptr : &len[1]) != SWG_OK)
+    die(3, std::string("--gaps: ") + swg_alnstats_last_error());
+  for (int k = 0; k < 2; ++k) {
+    const std::string& path = k == 0 ? rows_path : summary_path;
+    if (path.empty()) continue;
+    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
+    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+    if (f == stderr) std::fflush(stderr);
+    swg_free(text[k]);
+  }
+}
+
 // --dotplot / --dotplot-layout: the image and the layout table of swg_paf_dotplot, both from one device call when both are asked
 // for.  The layout's "-" = standard error.
 void write_dotplot(const std::string& image_path, const std::string& layout_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
@@ -454,6 +478,9 @@ int main(int argc, char** argv) {
   std::string breadth_path;  // --breadth: empty = no report
   bool breadth_detailed = false;
   std::string blocks_path;  // --blocks: empty = no file
+  std::string gaps_path, gaps_summary_path;  // --gaps, --gaps-summary: empty = no file
+  uint64_t gaps_min_size = 50;
+  bool gaps_flag = false;  // (--gaps-min-size was given)
   std::string components_path;  // --components: empty = no report
   bool components_detailed = false, component_flag = false;  // (component_flag: one of the two threshold flags was given)
   swg_component_params component_par{0, 0, 0};
@@ -535,6 +562,12 @@ int main(int argc, char** argv) {
     else if (a == "--breadth") { breadth_path = value(); if (breadth_path.empty()) die(2, "empty value for --breadth"); }
     else if (a == "--breadth-detailed") breadth_detailed = true;
     else if (a == "--blocks") { blocks_path = value(); if (blocks_path.empty()) die(2, "empty value for --blocks"); }
+    else if (a == "--gaps") { gaps_path = value(); if (gaps_path.empty()) die(2, "empty value for --gaps"); }
+    else if (a == "--gaps-summary") { gaps_summary_path = value(); if (gaps_summary_path.empty()) die(2, "empty value for --gaps-summary"); }
+    else if (a == "--gaps-min-size") {
+      if (!parse_metric_number(value(), &gaps_min_size) || gaps_min_size > 0xffffffffull) die(2, "bad --gaps-min-size");
+      gaps_flag = true;
+    }
     else if (a == "--components") { components_path = value(); if (components_path.empty()) die(2, "empty value for --components"); }
     else if (a == "--components-detailed") components_detailed = true;
     else if (a == "--lost") { lost_path = value(); if (lost_path.empty()) die(2, "empty value for --lost"); }
@@ -626,6 +659,7 @@ int main(int argc, char** argv) {
                 "         [--device D | --devices D0,D1,...] [--threads T] [--quiet]\n"
                 "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
                 "         [--blocks FILE|-]\n"
+                "         [--gaps FILE|-] [--gaps-summary FILE|-] [--gaps-min-size N]\n"
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
@@ -646,6 +680,14 @@ int main(int argc, char** argv) {
                 "                      matches and block length, and the tags ch:Z: nc:i: ni:i: nr:i: (core, inverted, rescued mappings)\n"
                 "                      qc:i: tc:i: (bases under at least one of them) id:f: -- built on the device (- = standard error);\n"
                 "                      empty with --no-filter or --scaffold-jump 0, which make no chains\n"
+                "  --gaps FILE         after the filter: what lies between the mappings of each kept chain -- one line per link whose\n"
+                "                      unaligned query and target stretches differ by at least --gaps-min-size (INS / DEL; dq, dt negative\n"
+                "                      = overlap) and per captured inversion (INV), `#query q_start q_end target t_start t_end kind size\n"
+                "                      chain dq dt left right`, ordered by chain and query position -- built on the device (- = standard\n"
+                "                      error); header only with --no-filter or --scaffold-jump 0, which make no chains\n"
+                "  --gaps-summary FILE per genome pair `links ins ins_bases del del_bases inv inv_bases`, then the size spectrum as\n"
+                "                      `#spectrum KIND lo hi count`; with --gaps, both come from one device call\n"
+                "  --gaps-min-size N   the smallest |size| (INV: query length) that gives a line; k/m/g suffixes (default 50)\n"
                 "  --components REPORT after the filter: per sequence its component -- the connected sets of sequences over the links\n"
                 "                      between sequence pairs that the kept mappings make -- with the component's sequences and length\n"
                 "                      and the sequence's own links, records and bases, as a tab-separated table computed on the device\n"
@@ -715,6 +757,8 @@ int main(int argc, char** argv) {
   if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
   if (mosaic_path.empty() && mosaic_share_path.empty() && mosaic_flag) die(2, "--mosaic-axis, --mosaic-set and --mosaic-by need --mosaic or --mosaic-share");
   const bool mosaic = !mosaic_path.empty() || !mosaic_share_path.empty();
+  if (gaps_path.empty() && gaps_summary_path.empty() && gaps_flag) die(2, "--gaps-min-size needs --gaps or --gaps-summary");
+  const bool gaps = !gaps_path.empty() || !gaps_summary_path.empty();
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
     die(2, "--dotplot-size, --dotplot-query and --dotplot-target need --dotplot or --dotplot-layout");
   const bool lift = !lift_regions_path.empty();
@@ -890,6 +934,10 @@ int main(int argc, char** argv) {
     gpu_init.join();
     die(3, "--blocks: the file has a value >= 2^32, its columns are rebased: blocks of 64-bit columns are not supported");
   }
+  if (gaps && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--gaps: the file has a value >= 2^32, its columns are rebased: gaps of 64-bit columns are not supported");
+  }
   const std::string out_path = output_file.empty() ? "-" : output_file;
   const swg_records* r = swg_paf_records(paf);
   uint64_t n = r->n;
@@ -924,6 +972,10 @@ int main(int argc, char** argv) {
     if (!blocks_path.empty()) {  // no filter, no chains
       std::fflush(out);
       write_blocks(blocks_path, nullptr, paf, nullptr, nullptr);
+    }
+    if (gaps) {  // no filter, no chains: the header lines
+      std::fflush(out);
+      write_gaps(gaps_path, gaps_summary_path, nullptr, paf, nullptr, nullptr, (uint32_t)gaps_min_size);
     }
     if (!components_path.empty()) {  // nothing is dropped: every record takes part
       std::fflush(out);
@@ -1075,6 +1127,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_blocks(blocks_path, ctx, paf, status.data(), chain.data());
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --blocks: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --gaps / --gaps-summary: likewise, both from one device call
+  if (gaps) {
+    const auto tb = clk::now();
+    write_gaps(gaps_path, gaps_summary_path, ctx, paf, status.data(), chain.data(), (uint32_t)gaps_min_size);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --gaps: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --components: on the first context, from the (merged) status the filter left
   if (!components_path.empty()) {
