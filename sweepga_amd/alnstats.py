@@ -6,7 +6,8 @@ import os
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgAlnstatsCounts, SwgAlnstatsPairCounts, SwgError, load
+from ._lib import SwgAlnstatsCounts, SwgAlnstatsPairCounts, load
+from ._marshal import addr, host_column, raise_alnstats, take_texts
 
 
 # swg_alnstats_pair_counts as a numpy record
@@ -109,8 +110,7 @@ class AlnStats:
             rc = lib.swg_alnstats_open_buffer(data, len(data), threads, C.byref(h))
         else:
             rc = lib.swg_alnstats_open(os.fsencode(path), threads, C.byref(h))
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
+        raise_alnstats(lib, rc)
         self.handle = h
         self.summary = lib.swg_alnstats_get(h).contents
 
@@ -121,19 +121,10 @@ class AlnStats:
         file PafFile.write(..., status) writes, else None.  ctx_or_filter: a Context, or anything with a `.ctx` (PafFilter)."""
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = None
-        if status is not None:
-            st = np.ascontiguousarray(status, dtype=np.uint8)
-            if st.size < paf.n:
-                raise ValueError("status has fewer entries than records")
-            if st.size == 0:
-                st = np.zeros(1, dtype=np.uint8)
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
         a, k = C.c_void_p(), C.c_void_p()
-        rc = lib.swg_paf_alnstats(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                  C.byref(a), C.byref(k) if st is not None else None)
-        if rc != SWG_OK:
-            lib.swg_alnstats_last_error.restype = C.c_char_p
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
+        rc = lib.swg_paf_alnstats(ctx.handle if ctx is not None else None, paf.handle, addr(st), C.byref(a), C.byref(k) if st is not None else None)
+        raise_alnstats(lib, rc)
         return cls(_handle=a), (cls(_handle=k) if st is not None else None)
 
     @property
@@ -147,11 +138,8 @@ class AlnStats:
         return out
 
     def _text(self, rc, p, n):
-        if rc != SWG_OK:
-            raise SwgError(rc, (self.lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        s = C.string_at(p.value, n.value)
-        self.lib.swg_free(p)
-        return s
+        raise_alnstats(self.lib, rc)
+        return take_texts(self.lib, [p], [n], [True])[0]
 
     def report(self, label, detailed=False):
         """print_stats (:166-228) as bytes."""

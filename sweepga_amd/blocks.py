@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgBlock, SwgBlockTable, SwgError, SwgRecords, load
+from ._lib import SwgBlock, SwgBlockTable, load
+from ._marshal import host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts
 
 # swg_block as a numpy record
 BLOCK_DTYPE = np.dtype([(k, "<u4") for k in ("chain", "q_id", "t_id", "strand", "q_start", "q_end", "t_start", "t_end", "n_core",
@@ -29,35 +30,13 @@ def _call(ctx, fn, rec, status_addr, chain_addr):
         cap = int(t.n_blocks)
 
 
-def _host(a, dtype, n, what):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    if a.size < n:
-        raise ValueError(f"{what} has fewer entries than records")
-    return a if a.size else np.zeros(1, dtype=dtype)
-
-
 def blocks_records(ctx, records, status, chain, n_seq=None):
     """swg_blocks_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end, matches, block_len, strand; n_seq = the largest id + 1 unless given).  status: uint8 [n], chain: uint32 [n]
     as a filter call wrote them.  Returns a structured array of BLOCK_DTYPE in ascending chain number."""
-    keep = []
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        s = np.ascontiguousarray(records["strand"], dtype=np.uint8)
-        keep.append(s)
-        rec.strand = s.ctypes.data
-        if n_seq is None:
-            n_seq = int(max(keep[0].max(), keep[1].max())) + 1 if rec.n else 1
-        rec.n_seq = int(n_seq)
-    else:
-        rec = records
-    st = _host(status, np.uint8, int(rec.n), "status")
-    ch = _host(chain, np.uint32, int(rec.n), "chain")
+    rec, keep = records_from_numpy(records, COLUMNS + ("strand",), n_seq)   # (keep: alive until the call is over)
+    st = host_column(status, np.uint8, int(rec.n), "status")
+    ch = host_column(chain, np.uint32, int(rec.n), "chain")
     return _call(ctx, ctx.lib.swg_blocks_records, rec, st.ctypes.data, ch.ctypes.data)
 
 
@@ -66,14 +45,7 @@ def blocks_records_device(ctx, columns, status, chain, n_seq):
     matches, block_len to contiguous int32 / uint32 tensors of one length and strand to a uint8 one; status is a uint8 tensor and
     chain a 4-byte one, as swg_filter_device left them.  (Anything with .data_ptr() and .numel() works; the caller keeps the
     tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k, size in [(k, 4) for k in COLUMNS] + [("strand", 1)]:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != size or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous {size}-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(n_seq)
+    rec = records_from_tensors(columns, {**{k: 4 for k in COLUMNS}, "strand": 1}, n_seq)
     if status.element_size() != 1 or chain.element_size() != 4 or min(int(status.numel()), int(chain.numel())) < int(rec.n):
         raise ValueError("status must be 1-byte and chain 4-byte, with an entry per record")
     return _call(ctx, ctx.lib.swg_blocks_records_device, rec, int(status.data_ptr()), int(chain.data_ptr()))
@@ -93,14 +65,12 @@ class Blocks:
         and once for the array: a convenience for tests and notebooks."""
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = _host(status, np.uint8, paf.n, "status")
-        ch = _host(chain, np.uint32, paf.n, "chain")
+        st = host_column(status, np.uint8, paf.n, "status")
+        ch = host_column(chain, np.uint32, paf.n, "chain")
         p, n = C.c_void_p(), C.c_uint64()
         rc = lib.swg_paf_blocks(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data, ch.ctypes.data, C.byref(p), C.byref(n))
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = C.string_at(p.value, n.value)
-        lib.swg_free(p)
+        raise_alnstats(lib, rc)
+        text, = take_texts(lib, [p], [n], [True])
         if not text:
             return cls(text, np.zeros(0, dtype=BLOCK_DTYPE))
         return cls(text, blocks_records(ctx, paf.records, st, ch))

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgBreadthCounts, SwgBreadthPair, SwgError, SwgRecords, load
+from ._lib import SwgBreadthCounts, SwgBreadthPair, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts
 
 # swg_breadth_pair as a numpy record
 BREADTH_PAIR_DTYPE = np.dtype([("q_genome", "<u4"), ("t_genome", "<u4"), ("q_bases", "<u8"), ("t_bases", "<u8"), ("q_union", "<u8"),
@@ -37,42 +38,19 @@ def breadth_records(ctx, records, seq_genome, status=None, n_genome=None):
     """swg_breadth_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end; n_seq = len(seq_genome)).  seq_genome: uint32 [n_seq].  Returns (all, kept) structured arrays of
     BREADTH_PAIR_DTYPE in order of first record; kept is None without status."""
-    keep = []
     seq_genome = np.ascontiguousarray(seq_genome, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        rec.n_seq = len(seq_genome)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS, len(seq_genome))   # (keep: alive until the call is over)
     if n_genome is None:
         n_genome = int(seq_genome.max()) + 1 if seq_genome.size else 1
-    st = None
-    if status is not None:
-        st = np.ascontiguousarray(status, dtype=np.uint8)
-        if st.size < int(rec.n):
-            raise ValueError("status has fewer entries than records")
-        if st.size == 0:
-            st = np.zeros(1, dtype=np.uint8)
-    return _call(ctx, ctx.lib.swg_breadth_records, rec, seq_genome.ctypes.data, n_genome, st.ctypes.data if st is not None else None)
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    return _call(ctx, ctx.lib.swg_breadth_records, rec, seq_genome.ctypes.data, n_genome, addr(st))
 
 
 def breadth_records_device(ctx, columns, seq_genome, n_genome, status=None):
     """swg_breadth_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end to
     contiguous int32 / uint32 tensors of one length, seq_genome is such a tensor of n_seq entries, status a uint8 tensor or None.
     (Anything with .data_ptr() and .numel() works; the caller keeps the tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(seq_genome.numel())
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, seq_genome.numel())
     if seq_genome.element_size() != 4 or (status is not None and (status.element_size() != 1 or int(status.numel()) < int(rec.n))):
         raise ValueError("seq_genome must be 4-byte, status 1-byte with an entry per record")
     return _call(ctx, ctx.lib.swg_breadth_records_device, rec, int(seq_genome.data_ptr()), n_genome,
@@ -95,20 +73,11 @@ class Breadth:
         from .alnstats import genome_last
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = None
-        if status is not None:
-            st = np.ascontiguousarray(status, dtype=np.uint8)
-            if st.size < paf.n:
-                raise ValueError("status has fewer entries than records")
-            if st.size == 0:
-                st = np.zeros(1, dtype=np.uint8)
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
         p, n = C.c_void_p(), C.c_uint64()
-        rc = lib.swg_paf_breadth(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                 int(bool(detailed)), C.byref(p), C.byref(n))
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = C.string_at(p.value, n.value)
-        lib.swg_free(p)
+        rc = lib.swg_paf_breadth(ctx.handle if ctx is not None else None, paf.handle, addr(st), int(bool(detailed)), C.byref(p), C.byref(n))
+        raise_alnstats(lib, rc)
+        text, = take_texts(lib, [p], [n], [True])
         genomes = {}
         for i, nm in enumerate(paf.names):
             genomes.setdefault(int(paf.seq_genome_last[i]), genome_last(nm))

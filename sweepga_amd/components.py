@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgComponent, SwgComponentParams, SwgComponentTable, SwgError, SwgLink, SwgRecords, load
+from ._lib import SwgComponent, SwgComponentParams, SwgComponentTable, SwgLink, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts
 
 # swg_link and swg_component as numpy records
 LINK_DTYPE = np.dtype([(k, "<u4") for k in ("a", "b", "n_records", "joined")] + [(k, "<u8") for k in ("a_bases", "b_bases", "first_record")])
@@ -38,15 +39,13 @@ class Components:
         notebooks."""
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = None if status is None else _host(status, np.uint8, paf.n, "status")
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
         par = params(min_bases, min_share)
         p, n = C.c_void_p(), C.c_uint64()
-        rc = lib.swg_paf_components(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                    C.byref(par), 1 if detailed else 0, C.byref(p), C.byref(n))
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = C.string_at(p.value, n.value)
-        lib.swg_free(p)
+        rc = lib.swg_paf_components(ctx.handle if ctx is not None else None, paf.handle, addr(st), C.byref(par), 1 if detailed else 0,
+                                    C.byref(p), C.byref(n))
+        raise_alnstats(lib, rc)
+        text, = take_texts(lib, [p], [n], [True])
         if paf.n == 0:
             return cls(np.zeros(0, dtype=COMPONENT_DTYPE), np.zeros(0, dtype=LINK_DTYPE), np.zeros(0, dtype=np.uint32), (0, 0, 0), text)
         rows = text.split(b"\n")[1:1 + int(paf.records.n_seq)]
@@ -54,13 +53,6 @@ class Components:
         r = components_records(ctx, paf.records, seq_len, st, par)
         r.text = text
         return r
-
-
-def _host(a, dtype, n, what):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    if a.size < n:
-        raise ValueError(f"{what} has fewer entries than records")
-    return a if a.size else np.zeros(1, dtype=dtype)
 
 
 def _call(ctx, fn, rec, seq_len_addr, status_addr, par):
@@ -86,39 +78,22 @@ def components_records(ctx, records, seq_len, status=None, par=None):
     """swg_components_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start,
     q_end, t_start, t_end).  seq_len: uint32 [n_seq], which also gives n_seq for a dict; status: uint8 [n] as a filter call
     wrote it, or None (every record takes part); par: SwgComponentParams (see params()) or None for 0, 0."""
-    keep = []
     seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data if a.size else None)
-        rec.n_seq = int(seq_len.size)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS, seq_len.size)   # (keep: alive until the call is over)
     if seq_len.size < int(rec.n_seq):
         raise ValueError("seq_len has fewer entries than sequences")
-    st = None if status is None else _host(status, np.uint8, int(rec.n), "status")
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
     sl = seq_len if seq_len.size else np.zeros(1, dtype=np.uint32)
-    return _call(ctx, ctx.lib.swg_components_records, rec, sl.ctypes.data, st.ctypes.data if st is not None else None, par)
+    return _call(ctx, ctx.lib.swg_components_records, rec, sl.ctypes.data, addr(st), par)
 
 
 def components_records_device(ctx, columns, seq_len, status=None, par=None):
     """swg_components_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end
     to contiguous int32 / uint32 tensors of one length, seq_len is a 4-byte tensor of n_seq entries, status a uint8 tensor or
     None.  (Anything with .data_ptr() and .numel() works; the caller keeps the tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, seq_len.numel())
     if seq_len.element_size() != 4 or not seq_len.is_contiguous():
         raise ValueError("seq_len must be a contiguous 4-byte tensor")
-    rec.n_seq = int(seq_len.numel())
     if status is not None and (status.element_size() != 1 or int(status.numel()) < int(rec.n)):
         raise ValueError("status must be 1-byte with an entry per record")
     return _call(ctx, ctx.lib.swg_components_records_device, rec, int(seq_len.data_ptr()), int(status.data_ptr()) if status is not None else None, par)

@@ -276,10 +276,8 @@ void row(std::string* o, const char* label, const std::string& value, size_t w) 
 std::string ratio(uint64_t a, uint64_t b) { return std::to_string(a) + "/" + std::to_string(b); }
 
 int hand_over(const std::string& s, char** out_text, uint64_t* out_len) {
-  char* p = static_cast<char*>(std::malloc(s.size() + 1));
+  char* p = text_copy(s);
   if (!p) return stats_error(SWG_ERR_OOM, "out of host memory");
-  std::memcpy(p, s.data(), s.size());
-  p[s.size()] = 0;
   *out_text = p;
   *out_len = s.size();
   return SWG_OK;

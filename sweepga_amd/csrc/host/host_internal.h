@@ -61,6 +61,24 @@ void swg_paf_stats_genome_names(const swg_paf* p, std::vector<std::string>* geno
 int swg_paf_stats_genome_sizes(const swg_paf* p, const swg_alnstats_result& r, std::vector<uint64_t>* genome_size);
 int swg_alnstats_error(int code, const char* fmt, ...);  // sets swg_alnstats_last_error()
 extern const char* const SWG_ALNSTATS_FIELD_ERR[6];      // "Invalid query length" ... for columns 2, 3, 4, 7, 10, 11
+// the wanted ones of `count` texts as the C ABI hands them out; all or nothing: on a failed allocation every text of this call is freed,
+// out_text / out_len of the wanted ones are zeroed and the result is swg_alnstats_error(SWG_ERR_OOM, "out of host memory")
+inline int texts_hand_over(const std::string* text, const bool* wanted, int count, char** out_text, uint64_t* out_len) {
+  for (int k = 0; k < count; ++k) {
+    if (!wanted[k]) continue;
+    out_text[k] = text_copy(text[k]);
+    out_len[k] = text[k].size();
+    if (out_text[k]) continue;
+    for (int j = 0; j <= k; ++j) {
+      if (!wanted[j]) continue;
+      std::free(out_text[j]);
+      out_text[j] = nullptr;
+      out_len[j] = 0;
+    }
+    return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
+  }
+  return SWG_OK;
+}
 
 // ---- breadth (swg_breadth.hip: kernels and seams; alnstats.cpp: the report) ----
 struct swg_breadth_result {

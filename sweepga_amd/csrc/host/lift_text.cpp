@@ -165,18 +165,7 @@ extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* statu
         }
       }
     }
-    for (int k = 0; k < 2; ++k) {
-      if (!wanted[k]) continue;
-      out_text[k] = text_copy(text[k]);
-      if (!out_text[k]) {
-        std::free(out_text[0]);
-        out_text[0] = out_text[1] = nullptr;
-        out_len[0] = out_len[1] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_len[k] = text[k].size();
-    }
-    return SWG_OK;
+    return texts_hand_over(text, wanted, 2, out_text, out_len);
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }
@@ -295,18 +284,7 @@ extern "C" int swg_paf_lift_closure(swg_ctx* ctx, const swg_paf* p, const uint8_
         }
       }
     }
-    for (int k = 0; k < 2; ++k) {
-      if (!wanted[k]) continue;
-      out_text[k] = text_copy(text[k]);
-      if (!out_text[k]) {
-        std::free(out_text[0]);
-        out_text[0] = out_text[1] = nullptr;
-        out_len[0] = out_len[1] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_len[k] = text[k].size();
-    }
-    return SWG_OK;
+    return texts_hand_over(text, wanted, 2, out_text, out_len);
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }

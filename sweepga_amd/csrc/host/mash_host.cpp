@@ -397,10 +397,8 @@ extern "C" int swg_joblist(swg_ctx* ctx, const char* const* paths, int n_paths, 
         text += std::string(" ") + paths[hap_file[p.second]];
       text += " > " + path_join(dir, sanitize(tg) + "_vs_" + sanitize(qy) + ".paf") + "\n";
     }
-    char* o = static_cast<char*>(std::malloc(text.size() + 1));
+    char* o = text_copy(text);
     if (!o) return host_error(ctx, SWG_ERR_OOM, "out of host memory writing the job list");
-    std::memcpy(o, text.data(), text.size());
-    o[text.size()] = 0;
     *out_text = o;
     *out_len = text.size();
   } catch (...) {

@@ -1004,10 +1004,8 @@ int swg_paf_blocks_text(const swg_paf* p, const std::vector<swg_block>& blocks, 
     std::snprintf(buf, sizeof buf, "\tid:f:%.6f\n", (double)b.matches / (double)(b.block_len ? b.block_len : 1));
     o += buf;
   }
-  char* t = static_cast<char*>(std::malloc(o.size() + 1));
+  char* t = text_copy(o);
   if (!t) return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-  std::memcpy(t, o.data(), o.size());
-  t[o.size()] = 0;
   *out_text = t;
   *out_len = o.size();
   return SWG_OK;

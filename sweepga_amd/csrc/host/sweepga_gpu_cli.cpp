@@ -230,6 +230,24 @@ int run_joblist(const std::vector<std::string>& inputs, const std::string& spars
   return 0;
 }
 
+// One report file: "-" = standard error (flushed), an empty path = not asked for, nothing is written.
+void write_bytes(const std::string& path, const char* data, uint64_t len) {
+  if (path.empty()) return;
+  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
+  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
+  if (len && std::fwrite(data, 1, len, f) != len) die(2, "write to " + path + " failed");
+  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
+  if (f == stderr) std::fflush(stderr);
+}
+// ... of a text the library handed out, which is released
+void write_text(const std::string& path, char* text, uint64_t len) {
+  write_bytes(path, text, len);
+  swg_free(text);
+}
+void write_texts(const std::string* const* paths, char* const* text, const uint64_t* len, int count) {
+  for (int k = 0; k < count; ++k) write_text(*paths[k], text[k], len[k]);
+}
+
 // --stats: the bytes `alnstats <input> <output>` prints for the two files (compare_stats), with --stats-detailed followed by
 // the two `alnstats <file> -d` reports (input, then output).  "-" = standard error: standard output may carry the PAF.
 void write_stats_report(const std::string& path, const swg_alnstats* before, const swg_alnstats* after, const std::string& in_label,
@@ -248,11 +266,7 @@ void write_stats_report(const std::string& path, const swg_alnstats* before, con
       all.append(text, len);
       swg_free(text);
     }
-  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-  if (!all.empty() && std::fwrite(all.data(), 1, all.size(), f) != all.size()) die(2, "write to " + path + " failed");
-  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-  if (f == stderr) std::fflush(stderr);
+  write_bytes(path, all.data(), all.size());
 }
 
 // --breadth: the report of swg_paf_breadth (merged-interval coverage per genome pair, all records and the kept ones).
@@ -261,12 +275,7 @@ void write_breadth_report(const std::string& path, swg_ctx* ctx, const swg_paf* 
   char* text = nullptr;
   uint64_t len = 0;
   if (swg_paf_breadth(ctx, paf, status, detailed ? 1 : 0, &text, &len) != SWG_OK) die(3, std::string("--breadth: ") + swg_alnstats_last_error());
-  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
-  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-  if (f == stderr) std::fflush(stderr);
-  swg_free(text);
+  write_text(path, text, len);
 }
 
 // --blocks: the text of swg_paf_blocks (one PAF line per kept scaffold chain).  "-" = standard error.  status == NULL: no filter
@@ -275,12 +284,7 @@ void write_blocks(const std::string& path, swg_ctx* ctx, const swg_paf* paf, con
   char* text = nullptr;
   uint64_t len = 0;
   if (status && swg_paf_blocks(ctx, paf, status, chain, &text, &len) != SWG_OK) die(3, std::string("--blocks: ") + swg_alnstats_last_error());
-  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
-  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-  if (f == stderr) std::fflush(stderr);
-  swg_free(text);
+  write_text(path, text, len);
 }
 
 // --components: the report of swg_paf_components (each sequence's component under the kept mappings).  "-" = standard error.
@@ -290,12 +294,7 @@ void write_components(const std::string& path, swg_ctx* ctx, const swg_paf* paf,
   uint64_t len = 0;
   if (swg_paf_components(ctx, paf, status, &par, detailed ? 1 : 0, &text, &len) != SWG_OK)
     die(3, std::string("--components: ") + swg_alnstats_last_error());
-  FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-  if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-  if (len && std::fwrite(text, 1, len, f) != len) die(2, "write to " + path + " failed");
-  if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-  if (f == stderr) std::fflush(stderr);
-  swg_free(text);
+  write_text(path, text, len);
 }
 
 // --lost / --covered: the LOST and KEPT texts of swg_paf_interval_texts (where coverage went, where it stayed), both from one
@@ -305,16 +304,8 @@ void write_intervals(const std::string& lost_path, const std::string& covered_pa
   uint64_t len[3] = {0, 0, 0};
   const uint32_t sets = (lost_path.empty() ? 0u : 1u << SWG_IV_LOST) | (covered_path.empty() ? 0u : 1u << SWG_IV_KEPT);
   if (swg_paf_interval_texts(ctx, paf, status, sets, text, len) != SWG_OK) die(3, std::string("--lost / --covered: ") + swg_alnstats_last_error());
-  for (int set : {SWG_IV_LOST, SWG_IV_KEPT}) {
-    const std::string& path = set == SWG_IV_LOST ? lost_path : covered_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[set] && std::fwrite(text[set], 1, len[set], f) != len[set]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[set]);
-  }
+  write_text(lost_path, text[SWG_IV_LOST], len[SWG_IV_LOST]);
+  write_text(covered_path, text[SWG_IV_KEPT], len[SWG_IV_KEPT]);
 }
 
 // --sharing / --sharing-bed: the table and the BED of swg_paf_sharing (how many genomes cover each base), both from one device call
@@ -324,16 +315,8 @@ void write_sharing(const std::string& table_path, const std::string& bed_path, s
   char* text[2] = {table_path.empty() ? nullptr : &marker, bed_path.empty() ? nullptr : &marker};
   uint64_t len[2] = {0, 0};
   if (swg_paf_sharing(ctx, paf, status, detailed ? 1 : 0, text, len) != SWG_OK) die(3, std::string("--sharing: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? table_path : bed_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&table_path, &bed_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --mosaic / --mosaic-share: the rows and the share table of swg_paf_mosaic (the best mapping at every base), both from one device
@@ -344,16 +327,8 @@ void write_mosaic(const std::string& rows_path, const std::string& share_path, s
   char* text[2] = {rows_path.empty() ? nullptr : &marker, share_path.empty() ? nullptr : &marker};
   uint64_t len[2] = {0, 0};
   if (swg_paf_mosaic(ctx, paf, status, axis, set, by_length ? 1 : 0, text, len) != SWG_OK) die(3, std::string("--mosaic: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? rows_path : share_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&rows_path, &share_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --gaps / --gaps-summary: the rows and the summary of swg_paf_gaps (the indel at every link of a kept chain, the captured
@@ -368,16 +343,8 @@ void write_gaps(const std::string& rows_path, const std::string& summary_path, s
   if (swg_paf_gaps(ctx, paf, status ? status : none.data(), status ? chain : zero.data(), min_size, rows_path.empty() ? nullptr : &text[0],
                    rows_path.empty() ? nullptr : &len[0], summary_path.empty() ? nullptr : &text[1], summary_path.empty() ? nullptr : &len[1]) != SWG_OK)
     die(3, std::string("--gaps: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? rows_path : summary_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --dotplot / --dotplot-layout: the image and the layout table of swg_paf_dotplot, both from one device call when both are asked
@@ -388,16 +355,8 @@ void write_dotplot(const std::string& image_path, const std::string& layout_path
   char* text[2] = {image_path.empty() ? nullptr : &marker, layout_path.empty() ? nullptr : &marker};
   uint64_t len[2] = {0, 0};
   if (swg_paf_dotplot(ctx, paf, status, &view, text, len) != SWG_OK) die(3, std::string("--dotplot: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? image_path : layout_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&image_path, &layout_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --lift / --lift-summary: the rows and the summary of swg_paf_lift (BED regions projected through the mappings), both from one
@@ -408,16 +367,8 @@ void write_lift(const std::string& rows_path, const std::string& summary_path, s
   char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
   uint64_t len[2] = {0, 0};
   if (swg_paf_lift(ctx, paf, status, bed.data(), bed.size(), set, axes, text, len) != SWG_OK) die(3, std::string("--lift: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? rows_path : summary_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --lift-closure / --lift-closure-summary: the two texts of swg_paf_lift_closure (the regions walked through the mappings for up to
@@ -429,16 +380,8 @@ void write_lift_closure(const std::string& rows_path, const std::string& summary
   uint64_t len[2] = {0, 0};
   if (swg_paf_lift_closure(ctx, paf, status, bed.data(), bed.size(), set, axes, hops, min_len, text, len) != SWG_OK)
     die(3, std::string("--lift-hops: ") + swg_alnstats_last_error());
-  for (int k = 0; k < 2; ++k) {
-    const std::string& path = k == 0 ? rows_path : summary_path;
-    if (path.empty()) continue;
-    FILE* f = path == "-" ? stderr : std::fopen(path.c_str(), "wb");
-    if (!f) die(2, "cannot open " + path + ": " + std::strerror(errno));
-    if (len[k] && std::fwrite(text[k], 1, len[k], f) != len[k]) die(2, "write to " + path + " failed");
-    if (f != stderr && std::fclose(f) != 0) die(2, "write to " + path + " failed");
-    if (f == stderr) std::fflush(stderr);
-    swg_free(text[k]);
-  }
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
 }
 
 // --dotplot-size: N or WxH, each side in 1 .. 16384

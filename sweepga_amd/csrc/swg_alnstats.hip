@@ -311,11 +311,11 @@ int swg_alnstats_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const
   return swg_run_with_arena(ctx, [&]() -> int {
     DevCols d{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches, seq_genome, status};
     if (!on_device) {
-      const uint32_t* col[5];
-      uint8_t* s8;
-      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->matches}, seq_genome, status != nullptr, status,
-                            col, &d.seq_genome, &s8));
-      d = DevCols{col[0], col[1], col[2], col[3], col[4], d.seq_genome, s8};
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&d.q_id, &d.t_id, &d.q_start, &d.q_end, &d.matches}) s.add(col, n);
+      s.add(&d.seq_genome, n_seq);
+      s.add(&d.status, n);
+      SWG_TRY(s.run());
     }
     return alnstats_device(ctx, n, n_seq, n_genome, d, all, kept);
   });

@@ -401,22 +401,6 @@ int blocks_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const Cols& d, swg_b
   return SWG_OK;
 }
 
-// the host seam's columns into the running arena frame
-int stage(swg_ctx* ctx, uint64_t n, const Cols& h, Cols* d) {
-  hipStream_t st = ctx->stream;
-  const uint32_t* src[9] = {h.q_id, h.t_id, h.start[0], h.start[1], h.end[0], h.end[1], h.matches, h.block_len, h.chain};
-  uint32_t* col[9];
-  for (auto& p : col) p = swg_alloc<uint32_t>(ctx, n);
-  uint8_t* strand = swg_alloc<uint8_t>(ctx, n);
-  uint8_t* status = swg_alloc<uint8_t>(ctx, n);
-  SWG_CHECK_ARENA(ctx);
-  for (int k = 0; k < 9; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  SWG_HIP(ctx, hipMemcpyAsync(strand, h.strand, n, hipMemcpyHostToDevice, st));
-  SWG_HIP(ctx, hipMemcpyAsync(status, h.status, n, hipMemcpyHostToDevice, st));
-  *d = Cols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, col[6], col[7], col[8], strand, status};
-  return SWG_OK;
-}
-
 int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const uint32_t* chain, swg_block_table* table) {
   if (!ctx) return SWG_ERR_INVALID;
   if (!table) return swg_set_error(ctx, SWG_ERR_INVALID, "blocks: NULL table");
@@ -448,7 +432,13 @@ int swg_blocks_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const u
   SWG_TRY(reserve_first(ctx, (size_t)n * 72 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     Cols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, rec->matches, rec->block_len, chain, rec->strand, status};
-    if (!on_device) SWG_TRY(stage(ctx, n, Cols(d), &d));
+    if (!on_device) {
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&d.q_id, &d.t_id, &d.start[0], &d.start[1], &d.end[0], &d.end[1], &d.matches, &d.block_len, &d.chain}) s.add(col, n);
+      s.add(&d.strand, n);
+      s.add(&d.status, n);
+      SWG_TRY(s.run());
+    }
     return blocks_device(ctx, n, rec->n_seq, d, res);
   });
 }

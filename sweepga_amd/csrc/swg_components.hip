@@ -370,22 +370,6 @@ int components_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const Cols& d, c
   return SWG_OK;
 }
 
-// the host seam's columns into the running arena frame
-int stage_host(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const Cols& h, Cols* d) {
-  hipStream_t st = ctx->stream;
-  const uint32_t* src[6] = {h.q_id, h.t_id, h.start[0], h.start[1], h.end[0], h.end[1]};
-  uint32_t* col[6];
-  for (auto& p : col) p = swg_alloc<uint32_t>(ctx, n);
-  uint32_t* len = swg_alloc<uint32_t>(ctx, n_seq);
-  uint8_t* status = h.status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-  SWG_CHECK_ARENA(ctx);
-  for (int k = 0; k < 6 && n; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  SWG_HIP(ctx, hipMemcpyAsync(len, h.seq_len, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (status && n) SWG_HIP(ctx, hipMemcpyAsync(status, h.status, n, hipMemcpyHostToDevice, st));
-  *d = Cols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, len, status};
-  return SWG_OK;
-}
-
 int records_abi(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_len, const uint8_t* status,
                 const swg_component_params* params, swg_component_table* table) {
   if (!ctx) return SWG_ERR_INVALID;
@@ -429,7 +413,13 @@ int swg_components_run(swg_ctx* ctx, const swg_records* rec, bool on_device, con
   SWG_TRY(reserve_first(ctx, (size_t)n * (on_device ? 8 : 32) + (size_t)n_seq * 64 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     Cols d{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_len, status};
-    if (!on_device) SWG_TRY(stage_host(ctx, n, n_seq, Cols(d), &d));
+    if (!on_device) {  // (n == 0 with sequences: the record columns may be NULL and stay so)
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&d.q_id, &d.t_id, &d.start[0], &d.start[1], &d.end[0], &d.end[1]}) s.add(col, n);
+      s.add(&d.seq_len, n_seq);
+      s.add(&d.status, n);
+      SWG_TRY(s.run());
+    }
     return components_device(ctx, n, n_seq, d, P, want_links, want_seq, res);
   });
 }
@@ -503,10 +493,8 @@ extern "C" int swg_paf_components(swg_ctx* ctx, const swg_paf* p, const uint8_t*
     append_u64(o, r.cross_links, '\t');
     append_u64(o, r.cross_records, '\t');
     append_u64(o, r.cross_bases, '\n');
-    char* t = static_cast<char*>(std::malloc(o.size() + 1));
+    char* t = text_copy(o);
     if (!t) return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-    std::memcpy(t, o.data(), o.size());
-    t[o.size()] = 0;
     *out_text = t;
     *out_len = o.size();
     return SWG_OK;

@@ -248,25 +248,16 @@ int dotplot_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const swg_
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * (on_device ? 4 : 30) + (size_t)n_seq * 16 + (size_t)size * 4 * __builtin_popcount(want) + (size_t(1) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
-    hipStream_t st = ctx->stream;
     DotCols c{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->t_start, rec->t_end, rec->strand, status};
     DotAxes a{axes->width, axes->height, n_seq, axes->x_total, axes->y_total, axes->x_off, axes->y_off};
     if (!on_device && n) {
-      const uint32_t* src[6] = {rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->t_start, rec->t_end};
-      uint32_t* col[6];
-      for (auto& p : col) p = swg_alloc<uint32_t>(ctx, n);
-      uint64_t* off[2] = {swg_alloc<uint64_t>(ctx, n_seq), swg_alloc<uint64_t>(ctx, n_seq)};
-      uint8_t* strand = swg_alloc<uint8_t>(ctx, n);
-      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-      SWG_CHECK_ARENA(ctx);
-      for (int k = 0; k < 6; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(off[0], axes->x_off, (size_t)n_seq * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(off[1], axes->y_off, (size_t)n_seq * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(strand, rec->strand, n, hipMemcpyHostToDevice, st));
-      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
-      c = DotCols{col[0], col[1], col[2], col[3], col[4], col[5], strand, s8};
-      a.x_off = off[0];
-      a.y_off = off[1];
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&c.q_id, &c.t_id, &c.q_start, &c.q_end, &c.t_start, &c.t_end}) s.add(col, n);
+      s.add(&a.x_off, n_seq);
+      s.add(&a.y_off, n_seq);
+      s.add(&c.strand, n);
+      s.add(&c.status, n);
+      SWG_TRY(s.run());
     }
     return dotplot_device(ctx, n, c, a, req);
   });
@@ -430,18 +421,7 @@ extern "C" int swg_paf_dotplot(swg_ctx* ctx, const swg_paf* p, const uint8_t* st
         }
       }
     }
-    for (int k = 0; k < 2; ++k) {
-      if (!wanted[k]) continue;
-      out[k] = text_copy(text[k]);
-      if (!out[k]) {
-        std::free(out[0]);
-        out[0] = out[1] = nullptr;
-        out_len[0] = out_len[1] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_len[k] = text[k].size();
-    }
-    return SWG_OK;
+    return texts_hand_over(text, wanted, 2, out, out_len);
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }

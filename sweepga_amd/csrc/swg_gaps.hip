@@ -405,19 +405,6 @@ int gaps_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, uint32_t G, const Cols
   return SWG_OK;
 }
 
-// the host seam's columns into the running arena frame
-int stage(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const Cols& h, Cols* d) {
-  const uint32_t* col[7];
-  const uint32_t* genome;
-  uint8_t* status;
-  SWG_TRY(stage_columns(ctx, n, n_seq, {h.q_id, h.t_id, h.qs, h.qe, h.ts, h.te, h.chain}, h.seq_genome, true, h.status, col, &genome, &status));
-  uint8_t* strand = swg_alloc<uint8_t>(ctx, n);
-  SWG_CHECK_ARENA(ctx);
-  SWG_HIP(ctx, hipMemcpyAsync(strand, h.strand, n, hipMemcpyHostToDevice, ctx->stream));
-  *d = Cols{col[0], col[1], col[2], col[3], col[4], col[5], col[6], genome, strand, status};
-  return SWG_OK;
-}
-
 // the seams' argument checks, then the device work inside an arena frame
 int gaps_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const uint32_t* chain, const uint32_t* seq_genome,
              uint32_t n_genome, swg_gaps_request* req, std::vector<swg_gap_row>* vec_rows, std::vector<swg_gap_pair>* vec_pairs) {
@@ -447,7 +434,14 @@ int gaps_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t
   SWG_TRY(reserve_first(ctx, (size_t)n * 64 + (size_t)rec->n_seq * 4 + (size_t(8) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
     Cols d{rec->q_id, rec->t_id, rec->q_start, rec->q_end, rec->t_start, rec->t_end, chain, seq_genome, rec->strand, status};
-    if (!on_device) SWG_TRY(stage(ctx, n, rec->n_seq, Cols(d), &d));
+    if (!on_device) {
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&d.q_id, &d.t_id, &d.qs, &d.qe, &d.ts, &d.te, &d.chain}) s.add(col, n);
+      s.add(&d.seq_genome, rec->n_seq);
+      s.add(&d.status, n);
+      s.add(&d.strand, n);
+      SWG_TRY(s.run());
+    }
     return gaps_device(ctx, n, rec->n_seq, n_genome, d, req, vec_rows, vec_pairs);
   });
 }
@@ -507,14 +501,12 @@ extern "C" int swg_paf_gaps(swg_ctx* ctx, const swg_paf* p, const uint8_t* statu
     }
     const std::string text[2] = {rows_text ? swg_gaps_rows_text(p, rec, rows) : std::string(),
                                  summary_text ? swg_gaps_summary_text(gname, pairs, spectrum) : std::string()};
-    char* out[2] = {rows_text ? text_copy(text[0]) : nullptr, summary_text ? text_copy(text[1]) : nullptr};
-    if ((rows_text && !out[0]) || (summary_text && !out[1])) {
-      std::free(out[0]);
-      std::free(out[1]);
-      return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-    }
-    if (rows_text) *rows_text = out[0], *rows_len = text[0].size();
-    if (summary_text) *summary_text = out[1], *summary_len = text[1].size();
+    const bool wanted[2] = {rows_text != nullptr, summary_text != nullptr};
+    char* out[2] = {nullptr, nullptr};
+    uint64_t len[2] = {0, 0};
+    SWG_TRY(texts_hand_over(text, wanted, 2, out, len));
+    if (rows_text) *rows_text = out[0], *rows_len = len[0];
+    if (summary_text) *summary_text = out[1], *summary_len = len[1];
     return SWG_OK;
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 #include <vector>
@@ -185,6 +186,38 @@ static inline int swg_run_with_arena(swg_ctx* ctx, F&& body) {
   do {                                                                \
     if ((ctx)->arena_overflow) return SWG_ERR_OOM;                    \
   } while (0)
+
+// Host arrays into the running arena frame, in two phases as the arena wants them: add() takes the room of every item (in call
+// order), run() checks the arena once -- SWG_ERR_OOM before any copy, swg_run_with_arena grows and reruns -- and then copies on the
+// context's stream in the order of add(), each *p replaced by its device address.  A NULL *p (an optional column) stays NULL
+// and takes no room; an item of 0 bytes takes its (empty) allocation and no copy.
+struct swg_stager {
+  static constexpr int CAP = 16;
+  struct item {
+    const void** p;
+    void* dev;
+    size_t bytes;
+  };
+  swg_ctx* ctx;
+  item items[CAP];
+  int count = 0;
+  explicit swg_stager(swg_ctx* c) : ctx(c) {}
+  template <class T>
+  void add(const T** p, size_t n) {
+    if (!*p) return;
+    if (count == CAP) abort();  // a programming error: raise CAP
+    items[count++] = item{reinterpret_cast<const void**>(p), swg_alloc<T>(ctx, n), n * sizeof(T)};
+  }
+  int run() {
+    SWG_CHECK_ARENA(ctx);
+    for (int k = 0; k < count; ++k) {
+      const item& it = items[k];
+      if (it.bytes) SWG_HIP(ctx, hipMemcpyAsync(it.dev, *it.p, it.bytes, hipMemcpyHostToDevice, ctx->stream));
+      *it.p = it.dev;
+    }
+    return SWG_OK;
+  }
+};
 
 // ---- primitives (swg_sort.hip) ---------------------------------------------------------------
 // Exclusive prefix sum of n u32 values, in place allowed (out may equal in).  The sums are taken in 32 bits: every

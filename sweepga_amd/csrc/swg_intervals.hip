@@ -372,9 +372,11 @@ extern "C" int swg_paf_interval_texts(swg_ctx* ctx, const swg_paf* p, const uint
       if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
       swg_paf_stats_genome_names(p, &gname);
     }
+    std::string text[3];
+    const bool wanted[3] = {(sets & 1u) != 0, (sets & 2u) != 0, (sets & 4u) != 0};
     for (int s = 0; s < 3; ++s) {
-      if (!(sets >> s & 1u)) continue;
-      std::string o;
+      if (!wanted[s]) continue;
+      std::string& o = text[s];
       for (int axis = 0; axis < 2; ++axis)
         for (const swg_interval& r : rows[s][axis]) {
           o += swg_paf_sequence_name(p, r.seq);
@@ -384,19 +386,9 @@ extern "C" int swg_paf_interval_texts(swg_ctx* ctx, const swg_paf* p, const uint
           o += gname[r.other_genome];
           o += axis ? "\tt\n" : "\tq\n";
         }
-      char* t = text_copy(o);
-      if (!t) {
-        for (int b = 0; b < s; ++b)
-          if (sets >> b & 1u) std::free(out_text[b]), out_text[b] = nullptr, out_len[b] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_text[s] = t;
-      out_len[s] = o.size();
     }
-    return SWG_OK;
-  } catch (const std::bad_alloc&) {
-    for (int s = 0; s < 3; ++s)
-      if (sets >> s & 1u) std::free(out_text[s]), out_text[s] = nullptr, out_len[s] = 0;
+    return texts_hand_over(text, wanted, 3, out_text, out_len);
+  } catch (const std::bad_alloc&) {  // (no text has been handed over yet: the outputs are as zeroed above)
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }
 }

@@ -414,23 +414,15 @@ int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uin
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * (24 * n_axes + (on_device ? 0 : 26)) + (size_t)m * (12 * n_axes + 48) + (size_t(4) << 20)));
   return swg_run_with_arena(ctx, [&]() -> int {
-    hipStream_t st = ctx->stream;
     LiftCols c{{rec->q_id, rec->t_id}, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, rec->strand, status};
     const swg_lift_region* d_regions = regions;
     if (!on_device) {
-      const uint32_t* src[6] = {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end};
-      uint32_t* col[6];
-      for (auto& p : col) p = swg_alloc<uint32_t>(ctx, n);
-      uint8_t* strand = swg_alloc<uint8_t>(ctx, n);
-      uint8_t* s8 = status ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-      swg_lift_region* regs = swg_alloc<swg_lift_region>(ctx, m);
-      SWG_CHECK_ARENA(ctx);
-      for (int k = 0; k < 6; ++k) SWG_HIP(ctx, hipMemcpyAsync(col[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(strand, rec->strand, n, hipMemcpyHostToDevice, st));
-      if (status) SWG_HIP(ctx, hipMemcpyAsync(s8, status, n, hipMemcpyHostToDevice, st));
-      SWG_HIP(ctx, hipMemcpyAsync(regs, regions, m * sizeof(swg_lift_region), hipMemcpyHostToDevice, st));
-      c = LiftCols{{col[0], col[1]}, {col[2], col[3]}, {col[4], col[5]}, strand, s8};
-      d_regions = regs;
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&c.id[0], &c.id[1], &c.start[0], &c.start[1], &c.end[0], &c.end[1]}) s.add(col, n);
+      s.add(&c.strand, n);
+      s.add(&c.status, n);
+      s.add(&d_regions, m);
+      SWG_TRY(s.run());
     }
     return lift_device(ctx, n, n_seq, c, d_regions, m, req);
   });

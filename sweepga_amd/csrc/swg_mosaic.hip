@@ -439,11 +439,10 @@ int mosaic_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint3
     SegCols d;
     SWG_TRY(swg_union_tiles::seg_stage(ctx, rec, on_device, seq_genome, status, &d));
     const uint32_t* d_weight = weight;
-    if (!on_device && weight) {
-      uint32_t* w = swg_alloc<uint32_t>(ctx, n);
-      SWG_CHECK_ARENA(ctx);
-      SWG_HIP(ctx, hipMemcpyAsync(w, weight, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-      d_weight = w;
+    if (!on_device) {
+      swg_stager s(ctx);
+      s.add(&d_weight, n);
+      SWG_TRY(s.run());
     }
     return mosaic_device(ctx, n, n_seq, n_genome, d, d_weight, req, vec);
   });
@@ -514,18 +513,7 @@ extern "C" int swg_paf_mosaic(swg_ctx* ctx, const swg_paf* p, const uint8_t* sta
     }
     const std::string text[2] = {wanted[0] ? swg_mosaic_rows_text(p, &rec, rows, axis, by_length != 0) : std::string(),
                                  wanted[1] ? swg_mosaic_share_text(gname, share, bases) : std::string()};
-    for (int k = 0; k < 2; ++k) {
-      if (!wanted[k]) continue;
-      out_text[k] = text_copy(text[k]);
-      if (!out_text[k]) {
-        std::free(out_text[0]);
-        out_text[0] = out_text[1] = nullptr;
-        out_len[0] = out_len[1] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_len[k] = text[k].size();
-    }
-    return SWG_OK;
+    return texts_hand_over(text, wanted, 2, out_text, out_len);
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }

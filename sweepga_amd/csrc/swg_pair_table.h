@@ -12,7 +12,7 @@
 //
 // A kernel keeps its own per-record loop and its own __global__ entry for the listing (the profile's launch labels are kernel
 // names); everything it does to a table goes through here.  Integer atomics only.  Below the scheme: what the host entries of
-// the three users share (grid_for, share_for, reserve_first, stage_columns).  swg_blocks.hip reduces per chain into a dense table
+// the three users share (grid_for, share_for, reserve_first).  swg_blocks.hip reduces per chain into a dense table
 // of its own and borrows the run and wavefront helpers only.  swg_components.hip keys the same table by SEQUENCE pair: three
 // sums (bases of either end, records) and the ALL first record; it lists the slots itself, as swg_link (table_alloc, table_clear).
 #pragma once
@@ -309,28 +309,6 @@ inline Share share_for(const swg_ctx* ctx, uint64_t n) {
 inline int reserve_first(swg_ctx* ctx, size_t want) {
   if (ctx->arena_cap) return SWG_OK;
   return swg_arena_reserve(ctx, std::min(want, swg_arena_budget(ctx)));
-}
-
-// Host columns into the running arena frame: K u32 columns of n records, seq_genome [n_seq] and, when `bytes`, one byte per
-// record -- the copy of bytes_src (a status column) or, without one, room that a kernel fills.
-template <int K>
-int stage_columns(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const uint32_t* const (&src)[K], const uint32_t* seq_genome, bool bytes,
-                  const uint8_t* bytes_src, const uint32_t* (&col)[K], const uint32_t** d_seq_genome, uint8_t** d_bytes) {
-  hipStream_t st = ctx->stream;
-  uint32_t* c[K];
-  for (auto& p : c) p = swg_alloc<uint32_t>(ctx, n);
-  uint32_t* g = swg_alloc<uint32_t>(ctx, n_seq);
-  uint8_t* b = bytes ? swg_alloc<uint8_t>(ctx, n) : nullptr;
-  SWG_CHECK_ARENA(ctx);
-  for (int k = 0; k < K; ++k) {
-    SWG_HIP(ctx, hipMemcpyAsync(c[k], src[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    col[k] = c[k];
-  }
-  SWG_HIP(ctx, hipMemcpyAsync(g, seq_genome, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (bytes_src) SWG_HIP(ctx, hipMemcpyAsync(b, bytes_src, n, hipMemcpyHostToDevice, st));
-  *d_seq_genome = g;
-  *d_bytes = b;
-  return SWG_OK;
 }
 
 }  // namespace swg_pair_table

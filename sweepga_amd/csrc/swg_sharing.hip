@@ -437,11 +437,10 @@ int sharing_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint
     SegCols d;
     SWG_TRY(seg_stage(ctx, rec, on_device, seq_genome, status, &d));
     d.seq_len = seq_len;
-    if (!on_device && seq_len) {
-      uint32_t* len = swg_alloc<uint32_t>(ctx, n_seq);
-      SWG_CHECK_ARENA(ctx);
-      SWG_HIP(ctx, hipMemcpyAsync(len, seq_len, (size_t)n_seq * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-      d.seq_len = len;
+    if (!on_device) {
+      swg_stager s(ctx);
+      s.add(&d.seq_len, n_seq);
+      SWG_TRY(s.run());
     }
     return sharing_device(ctx, n, n_seq, n_genome, d, req, vecs);
   });
@@ -592,18 +591,7 @@ extern "C" int swg_paf_sharing(swg_ctx* ctx, const swg_paf* p, const uint8_t* st
     }
     const std::string text[2] = {wanted[0] ? table_text(gname, spectrum, detailed != 0) : std::string(),
                                  wanted[1] ? bed_text(p, rows[0], rows[1]) : std::string()};
-    for (int k = 0; k < 2; ++k) {
-      if (!wanted[k]) continue;
-      out_text[k] = text_copy(text[k]);
-      if (!out_text[k]) {
-        std::free(out_text[0]);
-        out_text[0] = out_text[1] = nullptr;
-        out_len[0] = out_len[1] = 0;
-        return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
-      }
-      out_len[k] = text[k].size();
-    }
-    return SWG_OK;
+    return texts_hand_over(text, wanted, 2, out_text, out_len);
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }

@@ -258,10 +258,11 @@ int select_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint3
     SelCols d{rec->q_id, rec->t_id, rec->matches, rec->block_len, seq_genome};
     uint8_t* d_keep = keep;
     if (!on_device) {
-      const uint32_t* col[4];
-      SWG_TRY(stage_columns(ctx, n, n_seq, {rec->q_id, rec->t_id, rec->matches, rec->block_len}, seq_genome, true, nullptr, col, &d.seq_genome,
-                            &d_keep));
-      d = SelCols{col[0], col[1], col[2], col[3], d.seq_genome};
+      swg_stager s(ctx);
+      for (const uint32_t** col : {&d.q_id, &d.t_id, &d.matches, &d.block_len}) s.add(col, n);
+      s.add(&d.seq_genome, n_seq);
+      d_keep = swg_alloc<uint8_t>(ctx, n);  // (a kernel fills it)
+      SWG_TRY(s.run());
     }
     SWG_TRY(select_device(ctx, n, n_seq, n_genome, d, prefix, k_nearest, k_farthest, random_fraction, d_keep, n_kept, too_big));
     if (!on_device && !*too_big) {

@@ -98,12 +98,11 @@ inline int seg_check_args(swg_ctx* ctx, const char* who, uint32_t which, const s
 inline int seg_stage(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, const uint8_t* status, SegCols* d) {
   *d = SegCols{rec->q_id, rec->t_id, {rec->q_start, rec->t_start}, {rec->q_end, rec->t_end}, seq_genome, status};
   if (on_device) return SWG_OK;
-  const uint32_t* col[6];
-  uint8_t* s8;
-  SWG_TRY(swg_pair_table::stage_columns(ctx, rec->n, rec->n_seq, {rec->q_id, rec->t_id, rec->q_start, rec->t_start, rec->q_end, rec->t_end}, seq_genome,
-                                        status != nullptr, status, col, &d->seq_genome, &s8));
-  *d = SegCols{col[0], col[1], {col[2], col[3]}, {col[4], col[5]}, d->seq_genome, s8};
-  return SWG_OK;
+  swg_stager s(ctx);
+  for (const uint32_t** col : {&d->q_id, &d->t_id, &d->start[0], &d->start[1], &d->end[0], &d->end[1]}) s.add(col, rec->n);
+  s.add(&d->seq_genome, rec->n_seq);
+  s.add(&d->status, rec->n);
+  return s.run();
 }
 
 // a list's rows from the device to where the caller wants them: `vec` (internal callers), else `rows` when they fit `capacity`.

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgDotAxes, SwgDotRequest, SwgDotView, SwgError, SwgRecords, default_context, load
+from ._lib import SwgDotAxes, SwgDotRequest, SwgDotView, default_context, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
 ABSENT = 2**64 - 1
@@ -37,15 +38,6 @@ def _call(ctx, fn, rec, width, height, x_total, y_total, x_addr, y_addr, status_
     return DotplotResult(planes, hits, (int(req.drawn[0]), int(req.drawn[1])))
 
 
-def _status(status, n):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.uint8)
-    if st.size < n:
-        raise ValueError("status has fewer entries than records")
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def dotplot_records(ctx, records, strand, x_off, y_off, x_total, y_total, width, height, status=None, want=None):
     """swg_dotplot_records.  `records`: a dict of numpy columns (q_id, t_id, q_start, q_end, t_start, t_end); strand: uint8 per
     record (0 = '+'); x_off / y_off: uint64 per sequence id (ABSENT = not on the axis).  want: the bit mask (ALL_PLUS | ALL_MINUS |
@@ -54,19 +46,14 @@ def dotplot_records(ctx, records, strand, x_off, y_off, x_total, y_total, width,
     y_off = np.ascontiguousarray(y_off, dtype=np.uint64)
     if x_off.size != y_off.size:
         raise ValueError("x_off and y_off differ in length")
-    rec = SwgRecords()
-    rec.n = len(records["q_id"])
-    keep = [np.ascontiguousarray(records[k], dtype=np.uint32) for k in COLUMNS] + [np.ascontiguousarray(strand, dtype=np.uint8)]
+    rec, keep = records_from_numpy(records, COLUMNS, x_off.size, strand=strand)   # (keep: alive until the call is over)
     if any(a.size != int(rec.n) for a in keep):
         raise ValueError("the columns and strand differ in length")
-    for k, a in zip(COLUMNS + ("strand",), keep):
-        setattr(rec, k, a.ctypes.data if a.size else None)
-    rec.n_seq = x_off.size
-    st = _status(status, int(rec.n))
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
     if want is None:
         want = 0xf if st is not None else ALL_PLUS | ALL_MINUS
     return _call(ctx, ctx.lib.swg_dotplot_records, rec, width, height, x_total, y_total, x_off.ctypes.data if x_off.size else None,
-                 y_off.ctypes.data if y_off.size else None, st.ctypes.data if st is not None else None, want)
+                 y_off.ctypes.data if y_off.size else None, addr(st), want)
 
 
 def dotplot_records_device(ctx, columns, strand, x_off, y_off, x_total, y_total, width, height, status=None, want=None):
@@ -74,20 +61,13 @@ def dotplot_records_device(ctx, columns, strand, x_off, y_off, x_total, y_total,
     contiguous 4-byte tensors of one length, strand and status (or None) are 1-byte tensors with an entry per record, x_off and
     y_off 8-byte tensors of n_seq entries.  (Anything with .data_ptr(), .numel() and .element_size() works; the caller keeps the
     tensors alive and their work finished.)  The planes come back as numpy arrays on the host."""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, x_off.numel())
     for name, t in (("strand", strand), ("status", status)):
         if t is not None and (t.element_size() != 1 or int(t.numel()) < int(rec.n)):
             raise ValueError(f"{name} must be 1-byte with an entry per record")
     if x_off.element_size() != 8 or y_off.element_size() != 8 or int(x_off.numel()) != int(y_off.numel()):
         raise ValueError("x_off and y_off must be 8-byte tensors of one length")
     rec.strand = int(strand.data_ptr())
-    rec.n_seq = int(x_off.numel())
     if want is None:
         want = 0xf if status is not None else ALL_PLUS | ALL_MINUS
     return _call(ctx, ctx.lib.swg_dotplot_records_device, rec, width, height, x_total, y_total, int(x_off.data_ptr()), int(y_off.data_ptr()),
@@ -118,19 +98,10 @@ class Dotplot:
         height = width if height is None else height
         if ctx is None and image and paf.n:
             ctx = default_context()
-        st = _status(status, paf.n)
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
         view = SwgDotView(int(width), int(height), query_prefix.encode() if query_prefix else None, target_prefix.encode() if target_prefix else None)
-        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
-        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
-        for k, wanted in enumerate((image, layout)):
-            p[k] = C.addressof(marker) if wanted else None
-        rc = lib.swg_paf_dotplot(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                 C.byref(view), p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((image, layout)):
-            if wanted:
-                text[k] = C.string_at(p[k], n[k])
-                lib.swg_free(C.c_void_p(p[k]))
+        p, n = text_slots((image, layout))
+        rc = lib.swg_paf_dotplot(ctx.handle if ctx is not None else None, paf.handle, addr(st), C.byref(view), p, n)
+        raise_alnstats(lib, rc)
+        text = take_texts(lib, p, n, (image, layout))
         return cls(text[0], text[1].decode("utf-8", errors="surrogateescape") if text[1] is not None else None, int(width), int(height))

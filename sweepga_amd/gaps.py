@@ -7,7 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgError, SwgGapPair, SwgGapRow, SwgGapsRequest, SwgRecords, load
+from ._lib import SwgGapPair, SwgGapRow, SwgGapsRequest, load
+from ._marshal import host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts
 
 # swg_gap_row and swg_gap_pair as numpy records
 ROW_DTYPE = np.dtype([(k, "<u4") for k in ("chain", "left", "right", "q_lo", "q_hi", "t_lo", "t_hi")] +
@@ -56,36 +57,16 @@ def _call(ctx, fn, rec, status_addr, chain_addr, genome_addr, n_genome, min_size
         cap, pair_cap = max(cap, n_rows), max(pair_cap, n_pairs)
 
 
-def _host(a, dtype, n, what):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    if a.size < n:
-        raise ValueError(f"{what} has fewer entries than records")
-    return a if a.size else np.zeros(1, dtype=dtype)
-
-
 def gaps_records(ctx, records, status, chain, seq_genome, min_size=50, n_genome=None, want=ROWS | SUMMARY):
     """swg_gaps_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end, strand; n_seq = len(seq_genome)).  status: uint8 [n], chain: uint32 [n] as a filter call wrote them;
     seq_genome: uint32 [n_seq] (n_genome = its largest value + 1 unless given).  Returns a GapsResult."""
-    keep = []
     seq_genome = np.ascontiguousarray(seq_genome, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        s = np.ascontiguousarray(records["strand"], dtype=np.uint8)
-        keep.append(s)
-        rec.strand = s.ctypes.data
-        rec.n_seq = len(seq_genome)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS + ("strand",), len(seq_genome))   # (keep: alive until the call is over)
     if n_genome is None:
         n_genome = int(seq_genome.max()) + 1 if seq_genome.size else 1
-    st = _host(status, np.uint8, int(rec.n), "status")
-    ch = _host(chain, np.uint32, int(rec.n), "chain")
+    st = host_column(status, np.uint8, int(rec.n), "status")
+    ch = host_column(chain, np.uint32, int(rec.n), "chain")
     return _call(ctx, ctx.lib.swg_gaps_records, rec, st.ctypes.data, ch.ctypes.data, seq_genome.ctypes.data if seq_genome.size else None,
                  n_genome, min_size, want)
 
@@ -95,14 +76,7 @@ def gaps_records_device(ctx, columns, status, chain, seq_genome, n_genome, min_s
     contiguous int32 / uint32 tensors of one length and strand to a uint8 one; status is a uint8 tensor and chain a 4-byte one, as
     swg_filter_device left them; seq_genome a 4-byte tensor of n_seq entries.  (Anything with .data_ptr() and .numel() works; the
     caller keeps the tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k, size in [(k, 4) for k in COLUMNS] + [("strand", 1)]:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != size or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous {size}-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(seq_genome.numel())
+    rec = records_from_tensors(columns, {**{k: 4 for k in COLUMNS}, "strand": 1}, seq_genome.numel())
     if status.element_size() != 1 or chain.element_size() != 4 or min(int(status.numel()), int(chain.numel())) < int(rec.n):
         raise ValueError("status must be 1-byte and chain 4-byte, with an entry per record")
     if seq_genome.element_size() != 4:
@@ -125,20 +99,15 @@ class Gaps:
         (PafFilter); may be None when no record takes part."""
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = _host(status, np.uint8, paf.n, "status")
-        ch = _host(chain, np.uint32, paf.n, "chain")
+        st = host_column(status, np.uint8, paf.n, "status")
+        ch = host_column(chain, np.uint32, paf.n, "chain")
         p, n = [C.c_void_p(), C.c_void_p()], [C.c_uint64(), C.c_uint64()]
         args = []
         for k, wanted in enumerate((rows, summary)):
             args += [C.byref(p[k]), C.byref(n[k])] if wanted else [None, None]
         rc = lib.swg_paf_gaps(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data, ch.ctypes.data, C.c_uint32(int(min_size)), *args)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((rows, summary)):
-            if wanted:
-                text[k] = C.string_at(p[k].value, n[k].value)
-                lib.swg_free(p[k])
+        raise_alnstats(lib, rc)
+        text = take_texts(lib, p, n, (rows, summary))
         result = None
         if table and ctx is not None and paf.n:
             r = paf.records

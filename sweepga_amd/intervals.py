@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgError, SwgInterval, SwgIntervalRequest, SwgRecords, load
+from ._lib import SwgError, SwgInterval, SwgIntervalRequest, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts
 
 # swg_interval as a numpy record
 INTERVAL_DTYPE = np.dtype([("seq", "<u4"), ("other_genome", "<u4"), ("start", "<u4"), ("end", "<u4")])
@@ -56,51 +57,25 @@ def _call(ctx, fn, rec, genome_addr, n_genome, status_addr, want):
     return out
 
 
-def _status(status, n):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.uint8)
-    if st.size < n:
-        raise ValueError("status has fewer entries than records")
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def intervals_records(ctx, records, seq_genome, status=None, n_genome=None, want=None):
     """swg_intervals_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end; n_seq = len(seq_genome)).  seq_genome: uint32 [n_seq].  want: the bit mask (set * 2 + axis) or None = every list
     the status allows.  Returns an IntervalLists."""
-    keep = []
     seq_genome = np.ascontiguousarray(seq_genome, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        rec.n_seq = len(seq_genome)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS, len(seq_genome))   # (keep: alive until the call is over)
     if n_genome is None:
         n_genome = int(seq_genome.max()) + 1 if seq_genome.size else 1
-    st = _status(status, int(rec.n))
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
     if want is None:
         want = WANT_EVERYTHING if st is not None else 0x3
-    return _call(ctx, ctx.lib.swg_intervals_records, rec, seq_genome.ctypes.data, n_genome, st.ctypes.data if st is not None else None, want)
+    return _call(ctx, ctx.lib.swg_intervals_records, rec, seq_genome.ctypes.data, n_genome, addr(st), want)
 
 
 def intervals_records_device(ctx, columns, seq_genome, n_genome, status=None, want=None):
     """swg_intervals_records_device over torch tensors on ctx's GPU: `columns` maps q_id, t_id, q_start, q_end, t_start, t_end to
     contiguous int32 / uint32 tensors of one length, seq_genome is such a tensor of n_seq entries, status a uint8 tensor or None.
     (Anything with .data_ptr() and .numel() works; the caller keeps the tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(seq_genome.numel())
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, seq_genome.numel())
     if seq_genome.element_size() != 4 or (status is not None and (status.element_size() != 1 or int(status.numel()) < int(rec.n))):
         raise ValueError("seq_genome must be 4-byte, status 1-byte with an entry per record")
     if want is None:
@@ -123,20 +98,15 @@ class Intervals:
         from .alnstats import genome_last
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = _status(status, paf.n)
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
         if sets is None:
             sets = SETS if st is not None else ("all",)
         mask = sum(1 << SETS.index(s) for s in sets)
         p, n = (C.c_void_p * 3)(), (C.c_uint64 * 3)()
-        rc = lib.swg_paf_interval_texts(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                        mask, p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = {}
-        for s in sets:
-            k = SETS.index(s)
-            text[s] = C.string_at(p[k], n[k])
-            lib.swg_free(C.c_void_p(p[k]))
+        rc = lib.swg_paf_interval_texts(ctx.handle if ctx is not None else None, paf.handle, addr(st), mask, p, n)
+        raise_alnstats(lib, rc)
+        texts = take_texts(lib, p, n, [mask >> k & 1 for k in range(3)])
+        text = {s: texts[SETS.index(s)] for s in sets}
         genomes = {}
         for i, nm in enumerate(paf.names):
             genomes.setdefault(int(paf.seq_genome_last[i]), genome_last(nm))

@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgClosureRequest, SwgError, SwgLiftRequest, SwgRecords, default_context, load
+from ._lib import SwgClosureRequest, SwgLiftRequest, default_context, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
 REGION_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32)])
@@ -63,43 +64,22 @@ def _call(ctx, fn, rec, status_addr, regions_addr, m, set_, axes, capacity):
     return LiftResult(rows, int(req.n), summary, (int(req.candidates[0]), int(req.candidates[1])))
 
 
-def _status(status, n):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.uint8)
-    if st.size < n:
-        raise ValueError("status has fewer entries than records")
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def _host_records(records, strand, n_seq):
     """(SwgRecords over the caller's numpy columns, the arrays that must stay alive)"""
-    rec = SwgRecords()
-    rec.n = len(records["q_id"])
-    keep = [np.ascontiguousarray(records[k], dtype=np.uint32) for k in COLUMNS] + [np.ascontiguousarray(strand, dtype=np.uint8)]
+    rec, keep = records_from_numpy(records, COLUMNS, n_seq, strand=strand)
     if any(a.size != int(rec.n) for a in keep):
         raise ValueError("the columns and strand differ in length")
-    for k, a in zip(COLUMNS + ("strand",), keep):
-        setattr(rec, k, a.ctypes.data if a.size else None)
-    rec.n_seq = int(n_seq)
     return rec, keep
 
 
 def _device_records(columns, strand, n_seq, regions, n_regions, status):
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, n_seq)
     for name, t in (("strand", strand), ("status", status)):
         if t is not None and (t.element_size() != 1 or int(t.numel()) < int(rec.n)):
             raise ValueError(f"{name} must be 1-byte with an entry per record")
     if int(regions.numel()) * regions.element_size() < 16 * int(n_regions):
         raise ValueError("regions holds fewer than 16 bytes per region")
     rec.strand = int(strand.data_ptr())
-    rec.n_seq = int(n_seq)
     return rec
 
 
@@ -109,8 +89,8 @@ def lift_records(ctx, records, strand, n_seq, regions, status=None, set="all", a
     set: "all" / "kept" (or 0 / 1), axes: "query" / "target" / "both" (or the bit mask).  Returns a LiftResult."""
     regs = regions_array(regions)
     rec, keep = _host_records(records, strand, n_seq)
-    st = _status(status, int(rec.n))
-    return _call(ctx, ctx.lib.swg_lift_records, rec, st.ctypes.data if st is not None else None, regs.ctypes.data if regs.size else None,
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    return _call(ctx, ctx.lib.swg_lift_records, rec, addr(st), regs.ctypes.data if regs.size else None,
                  regs.size, SETS.get(set, set), AXES.get(axes, axes), capacity)
 
 
@@ -160,8 +140,8 @@ def lift_closure_records(ctx, records, strand, n_seq, regions, max_hops, min_len
     which a piece is reported but not walked on.  Returns a LiftClosureResult."""
     regs = regions_array(regions)
     rec, keep = _host_records(records, strand, n_seq)
-    st = _status(status, int(rec.n))
-    return _closure_call(ctx, ctx.lib.swg_lift_closure_records, rec, st.ctypes.data if st is not None else None,
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    return _closure_call(ctx, ctx.lib.swg_lift_closure_records, rec, addr(st),
                          regs.ctypes.data if regs.size else None, regs.size, SETS.get(set, set), AXES.get(axes, axes), max_hops, min_len, capacity)
 
 
@@ -219,20 +199,12 @@ class Lift:
         rebased = bool(lib.swg_paf_seq_offsets(paf.handle)) or bool(lib.swg_paf_record_offsets(paf.handle, 0))   # (refused by the library)
         if ctx is None and paf.n and bed.strip() and not rebased:
             ctx = default_context()
-        st = _status(status, paf.n)
-        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
-        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
-        for k, wanted in enumerate((rows, summary)):
-            p[k] = C.addressof(marker) if wanted else None
-        rc = lib.swg_paf_lift(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None, bed, len(bed),
-                              SETS.get(set, set), AXES.get(axes, axes), p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((rows, summary)):
-            if wanted:
-                text[k] = C.string_at(p[k], n[k]).decode("utf-8", errors="surrogateescape")
-                lib.swg_free(C.c_void_p(p[k]))
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
+        p, n = text_slots((rows, summary))
+        rc = lib.swg_paf_lift(ctx.handle if ctx is not None else None, paf.handle, addr(st), bed, len(bed), SETS.get(set, set),
+                              AXES.get(axes, axes), p, n)
+        raise_alnstats(lib, rc)
+        text = [t.decode("utf-8", errors="surrogateescape") if t is not None else None for t in take_texts(lib, p, n, (rows, summary))]
         return cls(text[0], text[1])
 
 
@@ -276,18 +248,10 @@ class LiftClosure:
         rebased = bool(lib.swg_paf_seq_offsets(paf.handle)) or bool(lib.swg_paf_record_offsets(paf.handle, 0))   # (refused by the library)
         if ctx is None and paf.n and bed.strip() and not rebased and 0 < int(max_hops) <= 65535:
             ctx = default_context()
-        st = _status(status, paf.n)
-        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
-        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
-        for k, wanted in enumerate((rows, summary)):
-            p[k] = C.addressof(marker) if wanted else None
-        rc = lib.swg_paf_lift_closure(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None, bed,
-                                      len(bed), SETS.get(set, set), AXES.get(axes, axes), int(max_hops), int(min_len), p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((rows, summary)):
-            if wanted:
-                text[k] = C.string_at(p[k], n[k]).decode("utf-8", errors="surrogateescape")
-                lib.swg_free(C.c_void_p(p[k]))
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
+        p, n = text_slots((rows, summary))
+        rc = lib.swg_paf_lift_closure(ctx.handle if ctx is not None else None, paf.handle, addr(st), bed, len(bed), SETS.get(set, set),
+                                      AXES.get(axes, axes), int(max_hops), int(min_len), p, n)
+        raise_alnstats(lib, rc)
+        text = [t.decode("utf-8", errors="surrogateescape") if t is not None else None for t in take_texts(lib, p, n, (rows, summary))]
         return cls(text[0], text[1])

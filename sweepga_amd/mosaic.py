@@ -8,7 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgError, SwgMosaicRequest, SwgMosaicRow, SwgRecords, load
+from ._lib import SwgError, SwgMosaicRequest, SwgMosaicRow, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 # swg_mosaic_row as a numpy record
 ROW_DTYPE = np.dtype([("seq", "<u4"), ("start", "<u4"), ("end", "<u4"), ("record", "<u4")])
@@ -53,34 +54,15 @@ def _call(ctx, fn, rec, genome_addr, n_genome, status_addr, weight_addr, axis, s
     return out
 
 
-def _status(status, n):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.uint8)
-    if st.size < n:
-        raise ValueError("status has fewer entries than records")
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def mosaic_records(ctx, records, seq_genome, status=None, weight=None, axis="query", set=None, n_genome=None, want=ROWS | SHARE):
     """swg_mosaic_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end and, when weight is None, matches; n_seq = len(seq_genome)).  seq_genome: uint32 [n_seq]; weight: uint32 [n] or
     None = the matches column; set: "all" / "kept" (default: kept when a status is given).  Returns a MosaicResult."""
-    keep = []
     seq_genome = np.ascontiguousarray(seq_genome, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS + (("matches",) if "matches" in records else ()):
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        rec.n_seq = len(seq_genome)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS, len(seq_genome), optional=("matches",))   # (keep: alive until the call is over)
     if n_genome is None:
         n_genome = int(seq_genome.max()) + 1 if seq_genome.size else 1
-    st = _status(status, int(rec.n))
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
     if set is None:
         set = "kept" if st is not None else "all"
     w = None
@@ -88,7 +70,7 @@ def mosaic_records(ctx, records, seq_genome, status=None, weight=None, axis="que
         w = np.ascontiguousarray(weight, dtype=np.uint32)
         if w.size < int(rec.n):
             raise ValueError("weight has fewer entries than records")
-    return _call(ctx, ctx.lib.swg_mosaic_records, rec, seq_genome.ctypes.data, n_genome, st.ctypes.data if st is not None else None,
+    return _call(ctx, ctx.lib.swg_mosaic_records, rec, seq_genome.ctypes.data, n_genome, addr(st),
                  w.ctypes.data if w is not None and w.size else None, axis, set, want)
 
 
@@ -97,14 +79,7 @@ def mosaic_records_device(ctx, columns, seq_genome, n_genome, status=None, weigh
     matches, read when weight is None) to contiguous int32 / uint32 tensors of one length, seq_genome is such a tensor of n_seq
     entries, status a uint8 tensor or None, weight a 4-byte tensor or None.  (Anything with .data_ptr() and .numel() works; the
     caller keeps the tensors alive and their work finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS + (("matches",) if "matches" in columns else ()):
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(seq_genome.numel())
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS + (("matches",) if "matches" in columns else ())}, seq_genome.numel())
     if seq_genome.element_size() != 4 or (status is not None and (status.element_size() != 1 or int(status.numel()) < int(rec.n))):
         raise ValueError("seq_genome must be 4-byte, status 1-byte with an entry per record")
     if weight is not None and (weight.element_size() != 4 or int(weight.numel()) < int(rec.n)):
@@ -131,18 +106,10 @@ class Mosaic:
             raise ValueError("by: matches or length")
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = _status(status, paf.n)
-        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
-        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
-        for k, wanted in enumerate((rows, share)):
-            p[k] = C.addressof(marker) if wanted else None
-        rc = lib.swg_paf_mosaic(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                AXES[axis], SETS[set], 1 if by == "length" else 0, p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((rows, share)):
-            if wanted:
-                text[k] = C.string_at(p[k], n[k])
-                lib.swg_free(C.c_void_p(p[k]))
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
+        p, n = text_slots((rows, share))
+        rc = lib.swg_paf_mosaic(ctx.handle if ctx is not None else None, paf.handle, addr(st), AXES[axis], SETS[set],
+                                1 if by == "length" else 0, p, n)
+        raise_alnstats(lib, rc)
+        text = take_texts(lib, p, n, (rows, share))
         return cls(text[0], text[1])

@@ -7,7 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SWG_OK, SwgDepthRun, SwgError, SwgRecords, SwgSharingRequest, load
+from ._lib import SwgDepthRun, SwgError, SwgSharingRequest, load
+from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 # swg_depth_run as a numpy record
 RUN_DTYPE = np.dtype([("seq", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])
@@ -58,43 +59,24 @@ def _call(ctx, fn, rec, genome_addr, n_genome, len_addr, status_addr, want):
     return out
 
 
-def _status(status, n):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.uint8)
-    if st.size < n:
-        raise ValueError("status has fewer entries than records")
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def sharing_records(ctx, records, seq_genome, seq_len=None, status=None, n_genome=None, want=None):
     """swg_sharing_records.  `records`: an SwgRecords with host pointers, or a dict of numpy columns (q_id, t_id, q_start, q_end,
     t_start, t_end; n_seq = len(seq_genome)).  seq_genome: uint32 [n_seq]; seq_len: uint32 [n_seq] or None (column 0 of a spectrum
     then stays 0).  want: the bit mask (RUNS_ALL | RUNS_KEPT | SPECTRUM_ALL | SPECTRUM_KEPT) or None = everything the status
     allows.  Returns a SharingResult."""
-    keep = []
     seq_genome = np.ascontiguousarray(seq_genome, dtype=np.uint32)
-    if isinstance(records, dict):
-        rec = SwgRecords()
-        rec.n = len(records["q_id"])
-        for k in COLUMNS:
-            a = np.ascontiguousarray(records[k], dtype=np.uint32)
-            keep.append(a)
-            setattr(rec, k, a.ctypes.data)
-        rec.n_seq = len(seq_genome)
-    else:
-        rec = records
+    rec, keep = records_from_numpy(records, COLUMNS, len(seq_genome))   # (keep: alive until the call is over)
     if n_genome is None:
         n_genome = int(seq_genome.max()) + 1 if seq_genome.size else 1
     if seq_len is not None:
         seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
         if seq_len.size != seq_genome.size:
             raise ValueError("seq_len and seq_genome differ in length")
-    st = _status(status, int(rec.n))
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
     if want is None:
         want = WANT_EVERYTHING if st is not None else RUNS_ALL | SPECTRUM_ALL
     return _call(ctx, ctx.lib.swg_sharing_records, rec, seq_genome.ctypes.data, n_genome,
-                 seq_len.ctypes.data if seq_len is not None and seq_len.size else None, st.ctypes.data if st is not None else None, want)
+                 seq_len.ctypes.data if seq_len is not None and seq_len.size else None, addr(st), want)
 
 
 def sharing_records_device(ctx, columns, seq_genome, n_genome, seq_len=None, status=None, want=None):
@@ -102,14 +84,7 @@ def sharing_records_device(ctx, columns, seq_genome, n_genome, seq_len=None, sta
     contiguous int32 / uint32 tensors of one length, seq_genome and seq_len (or None) are such tensors of n_seq entries, status a
     uint8 tensor or None.  (Anything with .data_ptr() and .numel() works; the caller keeps the tensors alive and their work
     finished.)"""
-    rec = SwgRecords()
-    rec.n = int(columns["q_id"].numel())
-    for k in COLUMNS:
-        t = columns[k]
-        if int(t.numel()) != int(rec.n) or t.element_size() != 4 or not t.is_contiguous():
-            raise ValueError(f"column {k}: a contiguous 4-byte tensor of {int(rec.n)} entries is needed")
-        setattr(rec, k, int(t.data_ptr()))
-    rec.n_seq = int(seq_genome.numel())
+    rec = records_from_tensors(columns, {k: 4 for k in COLUMNS}, seq_genome.numel())
     if seq_genome.element_size() != 4 or (status is not None and (status.element_size() != 1 or int(status.numel()) < int(rec.n))):
         raise ValueError("seq_genome must be 4-byte, status 1-byte with an entry per record")
     if seq_len is not None and (seq_len.element_size() != 4 or int(seq_len.numel()) != int(rec.n_seq)):
@@ -133,18 +108,9 @@ class Sharing:
         be None for a PAF without records."""
         ctx = getattr(ctx_or_filter, "ctx", ctx_or_filter)
         lib = load()
-        st = _status(status, paf.n)
-        marker = C.create_string_buffer(1)   # a text is asked for by a non-NULL entry
-        p, n = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
-        for k, wanted in enumerate((table, bed)):
-            p[k] = C.addressof(marker) if wanted else None
-        rc = lib.swg_paf_sharing(ctx.handle if ctx is not None else None, paf.handle, st.ctypes.data if st is not None else None,
-                                 1 if detailed else 0, p, n)
-        if rc != SWG_OK:
-            raise SwgError(rc, (lib.swg_alnstats_last_error() or b"").decode(errors="replace"))
-        text = [None, None]
-        for k, wanted in enumerate((table, bed)):
-            if wanted:
-                text[k] = C.string_at(p[k], n[k])
-                lib.swg_free(C.c_void_p(p[k]))
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
+        p, n = text_slots((table, bed))
+        rc = lib.swg_paf_sharing(ctx.handle if ctx is not None else None, paf.handle, addr(st), 1 if detailed else 0, p, n)
+        raise_alnstats(lib, rc)
+        text = take_texts(lib, p, n, (table, bed))
         return cls(text[0], text[1])

@@ -289,3 +289,17 @@ def test_cli_blocks(sw, tmp_path):
     blk.write_bytes(b"stale")
     r = subprocess.run([build.CLI, str(inp), "--output-file", str(out), "--scaffold-jump", "0", "--blocks", str(blk), "--quiet"], capture_output=True)
     assert r.returncode == 0 and out.stat().st_size > 0 and blk.read_bytes() == b""
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    rec = [(0, 1, 10, 110, 20, 125, 90, 105, 0), (0, 1, 200, 300, 210, 310, 80, 100, 0), (0, 1, 400, 450, 420, 470, 50, 50, 0)]
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            got = check(sw, columns(rec[:n]), np.full(n, S, dtype=np.uint8), np.ones(n, dtype=np.uint32), f"n = {n}", ctx=ctx, n_seq=2)
+            assert len(got) == 1 and int(got["n_core"][0]) == n
+    finally:
+        ctx.close()

@@ -331,3 +331,20 @@ def test_cli_breadth(sw, tmp_path):
                        capture_output=True)
     assert r.returncode == 0, r.stderr
     assert out.stat().st_size > 0 and rep.read_bytes() == model_report(text, out.read_bytes().decode(), True)
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    a = np.array([(0, 1, 10, 110, 20, 125), (0, 1, 200, 300, 210, 310), (0, 1, 400, 450, 420, 470)], dtype=np.uint32)
+    seq_genome = np.array([0, 1], dtype=np.uint32)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols = {c: a[:n, j].copy() for j, c in enumerate(COLS)}
+            for status in (None, np.ones(n, dtype=np.uint8)):   # (None: the optional column stays NULL on its way to the device)
+                got, _ = check(sw, cols, seq_genome, status, f"n = {n}", ctx=ctx)
+                assert len(got) == 1 and int(got["q_union"][0]) == int((a[:n, 3] - a[:n, 2]).sum())
+    finally:
+        ctx.close()

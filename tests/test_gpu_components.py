@@ -350,3 +350,20 @@ def test_a_million_records_pair_major_and_shuffled(sw):
     np.minimum.at(first, key[part], where[part])
     want_shuffled = dict(want, links=[l[:6] + (int(first[l[0] * n_seq + l[1]]),) for l in want["links"]])
     check(sw, {k: v[perm] for k, v in cols.items()}, status[perm], seq_len, 700_000, 100_000, what="shuffled", want=want_shuffled)
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    a = np.array([(0, 1, 10, 110, 20, 125), (0, 1, 200, 300, 210, 310), (0, 1, 400, 450, 420, 470)], dtype=np.uint32)
+    seq_len = np.array([1000, 1000], dtype=np.uint32)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols = {c: a[:n, j].copy() for j, c in enumerate(("q_id", "t_id", "q_start", "q_end", "t_start", "t_end"))}
+            for status in (None, np.ones(n, dtype=np.uint8)):   # (None: the optional column stays NULL on its way to the device)
+                got = check(sw, cols, status, seq_len, what=f"n = {n}", ctx=ctx)
+                assert len(got.components) == 1 and len(got.links) == 1 and int(got.links["n_records"][0]) == n
+    finally:
+        ctx.close()

@@ -393,3 +393,20 @@ def test_cli_dotplot(sw, tmp_path):
     img.unlink()
     r = subprocess.run([build.CLI, str(wide), "--output-file", str(out), "--dotplot", str(img)], capture_output=True, text=True)
     assert r.returncode == 3 and "2^32" in r.stderr and not img.exists()
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    rows = [(0, 1, 10, 110, 20, 125, 0, 1), (0, 1, 200, 300, 210, 310, 1, 1), (0, 1, 400, 450, 420, 470, 0, 1)]
+    x_off, y_off = np.array([0, 1000], dtype=np.uint64), np.array([0, 1000], dtype=np.uint64)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols, strand, kept = columns(rows[:n])
+            for status in (None, kept):   # (None: the optional column stays NULL on its way to the device)
+                got = check(sw, cols, strand, status, x_off, y_off, 2000, 2000, 8, 6, f"n = {n}", ctx=ctx)
+                assert list(got.drawn) == [n, n if status is not None else 0]
+    finally:
+        ctx.close()

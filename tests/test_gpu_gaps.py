@@ -394,3 +394,18 @@ def test_cli_gaps(sw, tmp_path):
     r = subprocess.run([build.CLI, str(inp), "--output-file", str(out), "--scaffold-jump", "0", "--gaps", str(rows), "--gaps-summary", str(summ), "--quiet"],
                        capture_output=True)
     assert r.returncode == 0 and out.stat().st_size > 0 and rows.read_bytes() == gm.ROWS_HEADER.encode() and summ.read_bytes() == gm.SUMMARY_HEADER.encode()
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    rec = [(0, 1, 10, 110, 20, 125, 0), (0, 1, 200, 300, 210, 310, 0), (0, 1, 400, 450, 520, 570, 0)]
+    genome = np.array([0, 1], dtype=np.uint32)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            got, _ = check(sw, columns(rec[:n]), np.full(n, S, dtype=np.uint8), np.ones(n, dtype=np.uint32), genome, min_sizes=(0,), what=f"n = {n}", ctx=ctx)
+            assert len(got.rows) == n - 1 and int(got.pairs["links"].sum()) == n - 1
+    finally:
+        ctx.close()

@@ -392,3 +392,20 @@ def test_cli_lost_and_covered(sw, tmp_path):
     assert r.returncode == 0 and out.stat().st_size > 0, r.stderr
     want = model_texts(text, kept_mask(text, out.read_bytes().decode()))
     assert lost.read_bytes() == want["lost"] and covered.read_bytes() == want["kept"]
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    a = np.array([(0, 1, 10, 110, 20, 125), (0, 1, 200, 300, 210, 310), (0, 1, 400, 450, 420, 470)], dtype=np.uint32)
+    seq_genome = np.array([0, 1], dtype=np.uint32)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols = {c: a[:n, j].copy() for j, c in enumerate(("q_id", "t_id", "q_start", "q_end", "t_start", "t_end"))}
+            for status in (None, np.ones(n, dtype=np.uint8)):   # (None: the optional column stays NULL on its way to the device)
+                got = check(sw, cols, seq_genome, status, f"n = {n}", ctx=ctx)
+                assert len(got["all", "q"]) == n == len(got["all", "t"])
+    finally:
+        ctx.close()

@@ -401,3 +401,20 @@ def test_cli_lift_hops(sw, tmp_path):
                         "--lift-closure-summary", str(summ)], capture_output=True)
     every = cm.paf_texts(text, np.ones(len(kept), dtype=bool), bed_text, 2, 100, 1, 3)
     assert r.returncode == 0 and r.stdout == text.encode() and rows.read_text() == every[0] and summ.read_text() == every[1]
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    rows = [(0, 1, 10, 110, 20, 125, 0, 1), (0, 1, 200, 300, 210, 310, 1, 1), (0, 1, 400, 450, 420, 470, 0, 1)]
+    regions = [(0, 0, 500), (1, 100, 300)]
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols, strand, kept = columns(rows[:n])
+            for status in (None, kept):   # (None: the optional column stays NULL on its way to the device)
+                got = check(sw, cols, strand, 2, regions, status, 3, 10, 1 if status is not None else 0, 3, f"n = {n}", ctx=ctx)
+                assert got.n >= 2 and got.hops_run >= 1
+    finally:
+        ctx.close()

@@ -419,3 +419,22 @@ def test_cli_sharing(sw, tmp_path):
     assert r.returncode == 0 and out.stat().st_size > 0, r.stderr
     again = sm.paf_texts(text, kept_mask(text, out.read_bytes().decode()))
     assert table.read_bytes() == again[0] and bed.read_bytes() == again[1]
+
+
+def test_smallest_shapes_on_a_fresh_context(sw):
+    """The seams around the kernels at the smallest shapes -- one record; three records of one sequence pair in one chain -- on a
+    context of its own: its first call sizes the arena from the input, the later ones find it sized.  Each shape twice, host seam
+    against device seam byte for byte and both against the model."""
+    a = np.array([(0, 1, 10, 110, 20, 125), (0, 1, 200, 300, 210, 310), (0, 1, 400, 450, 420, 470)], dtype=np.uint32)
+    seq_genome, seq_len = np.array([0, 1], dtype=np.uint32), np.array([1000, 1000], dtype=np.uint32)
+    ctx = sw.Context(0)
+    try:
+        for n in (1, 3, 1, 3):
+            cols = {c: a[:n, j].copy() for j, c in enumerate(("q_id", "t_id", "q_start", "q_end", "t_start", "t_end"))}
+            for status in (None, np.ones(n, dtype=np.uint8)):   # (None: the optional columns stay NULL on their way to the device)
+                got = check(sw, cols, seq_genome, seq_len, status, f"n = {n}", ctx=ctx)
+                assert len(got.runs["all"]) == 2 * n
+            without = both_seams(sw, cols, seq_genome, None, None, ctx=ctx)
+            assert sm.same_rows(without.runs["all"], got.runs["all"]) and not without.spectrum["all"][:, 0].any()
+    finally:
+        ctx.close()
