@@ -1193,6 +1193,98 @@ int swg_gaps_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t*
 int swg_paf_gaps(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const uint32_t* chain, uint32_t min_size, char** rows_text,
                  uint64_t* rows_len, char** summary_text, uint64_t* summary_len);
 
+/* ---- place: every sequence ordered and oriented along its best partner (no reference counterpart) -------
+ * Which sequence of the other genome does this one belong to, in which orientation, and where along it?  A pure function of the
+ * record columns (q_id, t_id, the four coordinates and strand; 32-bit layout), seq_len[n_seq], seq_genome[n_seq], status[n] (for
+ * the KEPT set), the axis, the set and min_bases.  Every value is an integer, every comparison exact.
+ *   axis        on axis 0 (query) record r places sequence s = q_id[r] on partner p = t_id[r] with weight w = q_end - q_start; on
+ *               axis 1 (target) the roles and the columns swap (s = t_id, p = q_id, w = t_end - t_start).
+ *   anchor      off = the partner coordinate that base 0 of s extrapolates to.  Axis 0: '+' record off = t_start - q_start, '-'
+ *               record off = t_end + q_start; axis 1: q_start - t_start and q_end + t_start.  Signed 64-bit, within
+ *               -(2^32 - 1) .. 2 * (2^32 - 1).
+ *   takes part  a record of the set with seq_genome[s] != seq_genome[p] (breadth's and mosaic's counting rule).  SWG_IV_ALL:
+ *               every such record; SWG_IV_KEPT: those with status != 0.  A zero-length record takes part with weight 0.
+ *   candidate   (s, p): fwd, rev = sum of w over its '+' / '-' records that take part, n_records = their number, bases = fwd + rev.
+ *   winner      of (s, g), g = seq_genome[p]: the candidate with the largest bases, among equals the smaller p.  total_bases = sum
+ *               of bases over all candidates of (s, g); runner_bases = the bases of the second candidate under the same order, 0
+ *               when there is none.
+ *   orientation '+' (0) when fwd >= rev and the winner has a '+' record, else '-' (1).  (The second condition matters only for a
+ *               winner of weight 0 without '+' records: it is '-', so that the deciding records are never none.)  The deciding
+ *               records are the winner's records on that strand.
+ *   offset      the weighted median of off over the deciding records: ordered by (off, record index), W = sum of their weights,
+ *               half = max(1, ceil(W / 2)), offset = the off of the first record whose inclusive prefix sum of weights is >= half;
+ *               W == 0: the first record's off.  The VALUE does not depend on how equal off are ordered.
+ *   span        q_lo, q_hi = min of the starts / max of the ends of the deciding records on the placed axis, t_lo, t_hi on the
+ *               partner axis; start = offset for '+', offset - seq_len[s] for '-' (signed; seq_len is taken as given).
+ *   rows        one per (s, g) whose winner has bases >= min_bases, in layout order (seq_genome[s], g, p, start, s) ascending;
+ *               rank = the 0-based position of the row among the rows with its (seq_genome[s], p).
+ *   summary     one entry per ordered genome pair (seq_genome[s], g) that has a row, ascending: rows, reversed (the '-' rows),
+ *               length = sum of seq_len[s], bases = sum of the winners' bases, total_bases = sum of the rows' total_bases.
+ * Nothing depends on the order of the records or on a launch shape.  `want`: SWG_PLACE_ROWS writes n_rows and, under the capacity
+ * protocol of swg_breadth_counts, the rows (n_rows > capacity still returns SWG_OK and leaves `rows` alone); SWG_PLACE_SUMMARY
+ * writes n_pairs and the pairs under the same protocol, each array on its own.  Errors: a NULL context (there is no CPU path),
+ * reserved != 0, want == 0 or a bit beyond the two, axis > 1, set > 1, SWG_IV_KEPT with status == NULL, a NULL column, a
+ * sequence id >= n_seq or a genome id >= n_genome (found on the device before any gather trusts it): SWG_ERR_INVALID; n >= 2^31
+ * records, n_seq > 2^31 (sequence, partner and strand share one 64-bit sort key) or 2^30 rows or more (the median's sort key
+ * holds the row above the 34-bit anchor): SWG_ERR_RANGE.  Scratch comes from the context's arena, SWG_ERR_OOM when the memory
+ * limit does not hold it: 24 bytes per record for the sort plus the radix sort's histograms, 9 per record that takes part, 5 per
+ * (s, p, strand) run, 73 per candidate, 25 per (s, g), 32 per deciding record, 218 per row and 52 per genome pair (DESIGN.md
+ * section 28 has the formula).  swg_place_records stages its host columns there too: 26 more bytes per record and 8 per sequence. */
+typedef struct swg_placement {
+  uint32_t seq, partner;           /* s and p */
+  uint32_t genome, partner_genome; /* seq_genome[s] and g */
+  int64_t offset;                  /* the weighted median of the anchors */
+  int64_t start;                   /* where base 0 ('+') or the last base's far side ('-') of s falls: the layout coordinate */
+  uint64_t bases, fwd, rev;        /* of the winner; bases = fwd + rev */
+  uint64_t total_bases;            /* over all candidates of (s, g) */
+  uint64_t runner_bases;           /* of the second candidate, 0 = none */
+  uint64_t n_records;              /* of the winner, both strands */
+  uint32_t q_lo, q_hi;             /* span of the deciding records on s */
+  uint32_t t_lo, t_hi;             /* ... and on p */
+  uint32_t rank;                   /* among the rows of (genome, partner) */
+  uint8_t orient;                  /* 0 = '+', 1 = '-' */
+  uint8_t reserved[3];             /* 0 */
+} swg_placement; /* 104 bytes, no implicit padding */
+typedef struct swg_place_pair {
+  uint32_t genome, partner_genome; /* ORDERED pair: the genome of the placed sequences, the genome they are placed on */
+  uint64_t rows, reversed;
+  uint64_t length;                 /* sum of seq_len over the placed sequences */
+  uint64_t bases, total_bases;
+} swg_place_pair; /* 48 bytes, no implicit padding */
+#define SWG_PLACE_ROWS 1u
+#define SWG_PLACE_SUMMARY 2u
+typedef struct swg_place_request {
+  uint32_t want;           /* the two bits above */
+  uint32_t axis;           /* 0 = query, 1 = target */
+  uint32_t set;            /* SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t reserved;       /* 0 */
+  uint64_t min_bases;      /* a row needs a winner with at least this many bases */
+  uint64_t n_rows;         /* out (rows bit) */
+  uint64_t capacity;       /* in: entries `rows` can hold */
+  swg_placement* rows;     /* in: caller-owned [capacity] or NULL; written only when n_rows <= capacity */
+  uint64_t n_pairs;        /* out (summary bit) */
+  uint64_t pair_capacity;  /* in: entries `pairs` can hold */
+  swg_place_pair* pairs;   /* in: caller-owned [pair_capacity] or NULL; written only when n_pairs <= pair_capacity */
+} swg_place_request; /* 72 bytes, no implicit padding */
+/* rec: host pointers; seq_len[rec->n_seq], seq_genome[rec->n_seq] and status[n] (NULL: SWG_IV_ALL only) on the host. */
+int swg_place_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                      const uint8_t* status, swg_place_request* req);
+/* The same with the seven columns of rec, seq_len, seq_genome and status in device memory of ctx's GPU (as swg_filter_device
+ * leaves them: no copy in between); the request and its arrays stay on the host. */
+int swg_place_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                             const uint8_t* status, swg_place_request* req);
+/* Both texts of an open PAF from ONE device call (release each with swg_free) under its last-'#' genome map and the last-seen
+ * lengths of swg_paf_components; a text is asked for by a non-NULL out_text[k] on entry, as in swg_paf_mosaic.  Tab-separated:
+ *   text 0  header `#sequence length partner partner_length orient start end rank bases fwd rev total runner records q_lo q_hi
+ *           t_lo t_hi`, then one line per row: names and lengths from the handle, orient + | -, end = start + length, start and
+ *           end as signed decimals.
+ *   text 1  header `#genome partner_genome sequences reversed length bases total_bases`, one line per summary entry (names keep
+ *           their trailing '#').
+ * A PAF without records gives the header-only texts and needs no device (ctx may be NULL then).  axis > 1, set > 1, SWG_IV_KEPT
+ * with status == NULL: SWG_ERR_INVALID; a handle with rebased columns: SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+int swg_paf_place(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t set, uint64_t min_bases, char** out_text,
+                  uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

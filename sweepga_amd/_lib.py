@@ -44,7 +44,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_lift_records", "swg_lift_records_device", "swg_paf_lift",
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
-           "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps"]
+           "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
+           "swg_place_records", "swg_place_records_device", "swg_paf_place"]
 
 
 class SwgError(RuntimeError):
@@ -215,6 +216,24 @@ class SwgGapsRequest(C.Structure):
     _fields_ = [("want", C.c_uint32), ("min_size", C.c_uint32), ("n_rows", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgGapRow)),
                 ("n_pairs", C.c_uint64), ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgGapPair)), ("spectrum", C.POINTER(C.c_uint64)),
                 ("reserved", C.c_uint64)]
+
+
+class SwgPlacement(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("partner", C.c_uint32), ("genome", C.c_uint32), ("partner_genome", C.c_uint32), ("offset", C.c_int64),
+                ("start", C.c_int64), ("bases", C.c_uint64), ("fwd", C.c_uint64), ("rev", C.c_uint64), ("total_bases", C.c_uint64),
+                ("runner_bases", C.c_uint64), ("n_records", C.c_uint64), ("q_lo", C.c_uint32), ("q_hi", C.c_uint32), ("t_lo", C.c_uint32),
+                ("t_hi", C.c_uint32), ("rank", C.c_uint32), ("orient", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class SwgPlacePair(C.Structure):
+    _fields_ = [("genome", C.c_uint32), ("partner_genome", C.c_uint32), ("rows", C.c_uint64), ("reversed", C.c_uint64), ("length", C.c_uint64),
+                ("bases", C.c_uint64), ("total_bases", C.c_uint64)]
+
+
+class SwgPlaceRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("axis", C.c_uint32), ("set", C.c_uint32), ("reserved", C.c_uint32), ("min_bases", C.c_uint64),
+                ("n_rows", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgPlacement)), ("n_pairs", C.c_uint64),
+                ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgPlacePair))]
 
 
 class SwgMosaicRow(C.Structure):
@@ -489,6 +508,12 @@ def load():
     lib.swg_paf_gaps.restype = C.c_int
     lib.swg_paf_gaps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_place_records", "swg_place_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgPlaceRequest)]
+    lib.swg_paf_place.restype = C.c_int
+    lib.swg_paf_place.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_dotplot_records", "swg_dotplot_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

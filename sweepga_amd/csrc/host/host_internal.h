@@ -135,6 +135,13 @@ std::string swg_gaps_rows_text(const swg_paf* p, const swg_records* rec, const s
 // header, one line per genome pair (ascending), then `#spectrum KIND lo hi count` per non-empty bin of spectrum [2][SWG_GAPS_BINS]
 std::string swg_gaps_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_gap_pair>& pairs, const uint64_t* spectrum);
 
+// ---- place (swg_place.hip: kernels and seams; place_text.cpp: the two texts of swg_paf_place) ----
+// header, then one line per row: sequence length partner partner_length orient start end rank bases fwd rev total runner records
+// q_lo q_hi t_lo t_hi (seq_len: the lengths the device call read)
+std::string swg_place_rows_text(const swg_paf* p, const std::vector<uint32_t>& seq_len, const std::vector<swg_placement>& rows);
+// header, then one line per genome pair: genome partner_genome sequences reversed length bases total_bases
+std::string swg_place_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_place_pair>& pairs);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

@@ -331,6 +331,18 @@ void write_mosaic(const std::string& rows_path, const std::string& share_path, s
   write_texts(paths, text, len, 2);
 }
 
+// --place / --place-summary: the rows and the summary of swg_paf_place (every sequence ordered and oriented along its best partner),
+// both from one device call when both are asked for.  "-" = standard error.
+void write_place(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t axis,
+                 uint32_t set, uint64_t min_bases) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_place(ctx, paf, status, axis, set, min_bases, text, len) != SWG_OK) die(3, std::string("--place: ") + swg_alnstats_last_error());
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
+}
+
 // --gaps / --gaps-summary: the rows and the summary of swg_paf_gaps (the indel at every link of a kept chain, the captured
 // inversions), both from one device call when both are asked for.  "-" = standard error.  status == NULL: no filter ran, there
 // are no chains, the files hold their header lines.
@@ -432,6 +444,10 @@ int main(int argc, char** argv) {
   bool sharing_detailed = false;
   std::string mosaic_path, mosaic_share_path;  // --mosaic, --mosaic-share: empty = no file
   uint32_t mosaic_axis = 0, mosaic_set = SWG_IV_KEPT;
+  std::string place_path, place_summary_path;  // --place, --place-summary: empty = no file
+  uint32_t place_axis = 0, place_set = SWG_IV_KEPT;
+  uint64_t place_min_bases = 0;
+  bool place_flag = false;  // (one of --place-axis / --place-set / --place-min-bases was given)
   bool mosaic_by_length = false, mosaic_flag = false;  // (mosaic_flag: one of --mosaic-axis / --mosaic-set / --mosaic-by was given)
   std::string dotplot_path, dotplot_layout_path, dotplot_query, dotplot_target;  // --dotplot, --dotplot-layout: empty = no file
   swg_dot_view dot_view{2048, 2048, nullptr, nullptr};
@@ -542,6 +558,26 @@ int main(int argc, char** argv) {
       if (!parse_u64(value(), &lift_min_length) || lift_min_length > UINT32_MAX) die(2, "invalid value for --lift-min-length: 0 .. 2^32 - 1");
       lift_min_length_flag = true;
     }
+    else if (a == "--place") { place_path = value(); if (place_path.empty()) die(2, "empty value for --place"); }
+    else if (a == "--place-summary") { place_summary_path = value(); if (place_summary_path.empty()) die(2, "empty value for --place-summary"); }
+    else if (a == "--place-axis") {
+      const std::string v = value();
+      if (v == "query") place_axis = 0;
+      else if (v == "target") place_axis = 1;
+      else die(2, "invalid value for --place-axis: query or target");
+      place_flag = true;
+    }
+    else if (a == "--place-set") {
+      const std::string v = value();
+      if (v == "kept") place_set = SWG_IV_KEPT;
+      else if (v == "all") place_set = SWG_IV_ALL;
+      else die(2, "invalid value for --place-set: kept or all");
+      place_flag = true;
+    }
+    else if (a == "--place-min-bases") {
+      if (!parse_metric_number(value(), &place_min_bases)) die(2, "bad --place-min-bases");
+      place_flag = true;
+    }
     else if (a == "--mosaic") { mosaic_path = value(); if (mosaic_path.empty()) die(2, "empty value for --mosaic"); }
     else if (a == "--mosaic-share") { mosaic_share_path = value(); if (mosaic_share_path.empty()) die(2, "empty value for --mosaic-share"); }
     else if (a == "--mosaic-axis") {
@@ -603,6 +639,7 @@ int main(int argc, char** argv) {
                 "         [--stats REPORT|-] [--stats-detailed] [--breadth REPORT|-] [--breadth-detailed]\n"
                 "         [--blocks FILE|-]\n"
                 "         [--gaps FILE|-] [--gaps-summary FILE|-] [--gaps-min-size N]\n"
+                "         [--place FILE|-] [--place-summary FILE|-] [--place-axis query|target] [--place-set kept|all] [--place-min-bases N]\n"
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
@@ -631,6 +668,15 @@ int main(int argc, char** argv) {
                 "  --gaps-summary FILE per genome pair `links ins ins_bases del del_bases inv inv_bases`, then the size spectrum as\n"
                 "                      `#spectrum KIND lo hi count`; with --gaps, both come from one device call\n"
                 "  --gaps-min-size N   the smallest |size| (INV: query length) that gives a line; k/m/g suffixes (default 50)\n"
+                "  --place FILE        after the filter: every sequence ordered and oriented along its best partner of each other genome --\n"
+                "                      `sequence length partner partner_length orient start end rank bases fwd rev total runner records\n"
+                "                      q_lo q_hi t_lo t_hi`, in layout order (genome, partner genome, partner, start); start is the weighted\n"
+                "                      median of where the mappings put base 0 of the sequence (signed); '-' = standard error\n"
+                "  --place-summary FILE per genome pair `sequences reversed length bases total_bases`; with --place, both come from one\n"
+                "                      device call\n"
+                "  --place-axis query|target  the sequences that are placed (default query)\n"
+                "  --place-set kept|all  the mappings that vote (default kept; with --no-filter kept = all)\n"
+                "  --place-min-bases N a row needs a best partner with at least N aligned bases; k/m/g suffixes (default 0)\n"
                 "  --components REPORT after the filter: per sequence its component -- the connected sets of sequences over the links\n"
                 "                      between sequence pairs that the kept mappings make -- with the component's sequences and length\n"
                 "                      and the sequence's own links, records and bases, as a tab-separated table computed on the device\n"
@@ -700,6 +746,9 @@ int main(int argc, char** argv) {
   if (sharing_path.empty() && sharing_detailed) die(2, "--sharing-detailed needs --sharing");
   if (mosaic_path.empty() && mosaic_share_path.empty() && mosaic_flag) die(2, "--mosaic-axis, --mosaic-set and --mosaic-by need --mosaic or --mosaic-share");
   const bool mosaic = !mosaic_path.empty() || !mosaic_share_path.empty();
+  if (place_path.empty() && place_summary_path.empty() && place_flag)
+    die(2, "--place-axis, --place-set and --place-min-bases need --place or --place-summary");
+  const bool place = !place_path.empty() || !place_summary_path.empty();
   if (gaps_path.empty() && gaps_summary_path.empty() && gaps_flag) die(2, "--gaps-min-size needs --gaps or --gaps-summary");
   const bool gaps = !gaps_path.empty() || !gaps_summary_path.empty();
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
@@ -800,7 +849,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -862,6 +911,10 @@ int main(int argc, char** argv) {
   if (mosaic && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--mosaic: the file has a value >= 2^32, its columns are rebased: the mosaic of 64-bit columns is not supported");
+  }
+  if (place && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--place: the file has a value >= 2^32, its columns are rebased: the placement of 64-bit columns is not supported");
   }
   if ((!dotplot_path.empty() || !dotplot_layout_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
@@ -942,6 +995,12 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_mosaic(mosaic_path, mosaic_share_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), mosaic_axis, mosaic_set, mosaic_by_length);
+    }
+    if (place) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_place(place_path, place_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), place_axis, place_set, place_min_bases);
     }
     if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {  // nothing is dropped: the kept planes equal the all planes
       std::fflush(out);
@@ -1070,6 +1129,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_blocks(blocks_path, ctx, paf, status.data(), chain.data());
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --blocks: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --place / --place-summary: on the first context, under the merged status (with --sparsify, dropped records have status 0)
+  if (place) {
+    const auto tb = clk::now();
+    write_place(place_path, place_summary_path, ctx, paf, status.data(), place_axis, place_set, place_min_bases);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --place: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --gaps / --gaps-summary: likewise, both from one device call
   if (gaps) {
