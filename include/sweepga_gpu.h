@@ -1285,6 +1285,94 @@ int swg_place_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_
 int swg_paf_place(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t set, uint64_t min_bases, char** out_text,
                   uint64_t* out_len);
 
+/* ---- windows: depth, cover and identity per fixed window (no reference counterpart) -----------------------
+ * The track along a sequence: per window of W bases how deep the pile of mappings is, how much of the window is covered at all
+ * and how well it matches, for ALL records and for the records a filter call KEPT, from one device call.  A pure function of the
+ * record columns (q_id, t_id, the two coordinates of the axis, matches or `weight`; 32-bit layout), seq_len[n_seq],
+ * seq_genome[n_seq], status[n], the axis, W and other_genome.  Every value is an integer, every comparison exact.
+ *   axis        on axis 0 (query) record r lies on s = q_id[r] over [a, b) = [q_start, q_end) and its other sequence is
+ *               o = t_id[r]; on axis 1 (target) the roles and the columns swap.  m = weight[r]; weight == NULL: rec->matches[r].
+ *   takes part  (set ALL) seq_genome[s] != seq_genome[o] (breadth's counting rule), a < b (a zero-length or reversed record adds
+ *               nothing and lists nothing), and other_genome == SWG_WINDOWS_ANY or seq_genome[o] == other_genome.
+ *   set KEPT    the records of ALL with status != 0.  status == NULL: there is no KEPT set and every [1] entry below is 0.
+ *   windows     sequence s has K_s = ceil(seq_len[s] / W) windows, window k = [k W, min((k + 1) W, seq_len[s])).  A record that
+ *               takes part with b > seq_len[s] is an error (found on the device before any write trusts it; the message names the
+ *               record with the smallest index).  A sequence is LISTED when at least one record of ALL lies on it.
+ *   per window and set, with ov(r, k) = the length of [a, b) in window k:
+ *               n = the records with ov > 0; depth = sum of ov; covered = the bases of the window under at least one record (the
+ *               union); matches = sum of floor(ov * m / (b - a)) (the product is below 2^64; a record inside one window gives
+ *               exactly m, an interior window of a long record floor(W * m / (b - a))).  Mean depth is depth / (end - start),
+ *               identity matches / depth, breadth covered / (end - start): the caller divides.
+ *   rows        one per window of every listed sequence, empty windows included, (seq, index) ascending; sequences that are not
+ *               listed have none.
+ *   summary     one entry per listed sequence, ascending: windows = K_s; empty[set] = its windows with covered == 0 (status ==
+ *               NULL: empty[1] = 0 like every [1] entry); covered, depth and matches summed over its windows; records[set] = the
+ *               records that take part on it (one that spans five windows counts once).
+ * Nothing depends on the order of the records or on a launch shape: all updates are integer additions.  `want`:
+ * SWG_WINDOWS_ROWS writes n_rows and, under the capacity protocol of swg_breadth_counts, the rows (n_rows > capacity still returns
+ * SWG_OK and leaves `rows` alone); SWG_WINDOWS_SUMMARY writes n_seqs and the entries under the same protocol, each array on its
+ * own.  On an error found after the arguments were accepted the counts are 0.  Errors: a NULL context (there is no CPU path),
+ * reserved != 0, want == 0 or a bit beyond the two, axis > 1, window == 0, other_genome >= n_genome and not SWG_WINDOWS_ANY, a
+ * NULL column (seq_len and seq_genome included), weight == NULL with rec->matches == NULL, a sequence id >= n_seq or a genome id
+ * >= n_genome, a record that takes part and ends beyond its sequence: SWG_ERR_INVALID; n >= 2^31 records, n_seq > 2^31 or 2^31
+ * windows or more in the listed sequences (refused before anything of that size is allocated): SWG_ERR_RANGE.  Scratch comes
+ * from the context's arena, SWG_ERR_OOM when the memory limit does not hold it: 28 bytes per record (the union's sort: two 8-byte
+ * key and two 4-byte value buffers, and the ends in sorted order) plus the radix sort's histograms and 16 bytes per tile of 1,024
+ * records; 9 bytes per sequence (listed flag, window prefix) and 4 per listed one; 120 bytes per window (per set five 8-byte
+ * count / difference arrays, two 8-byte and one 4-byte edge accumulators) plus 64 for its row, and 80 per listed sequence with
+ * the summary.  swg_windows_records stages its host columns there too: 21 more bytes per record (the two ids, the
+ * axis' two coordinates, the weight, the status) and 8 per sequence. */
+#define SWG_WINDOWS_ANY 0xffffffffu
+typedef struct swg_window_row {
+  uint32_t seq, index;  /* s and k */
+  uint32_t start, end;  /* the window, half-open, clipped to seq_len */
+  uint32_t n[2];        /* [0] = ALL, [1] = KEPT */
+  uint32_t covered[2];
+  uint64_t depth[2];
+  uint64_t matches[2];
+} swg_window_row; /* 64 bytes, no implicit padding */
+typedef struct swg_window_seq {
+  uint32_t seq, windows;
+  uint32_t empty[2];
+  uint64_t covered[2], depth[2], matches[2], records[2];
+} swg_window_seq; /* 80 bytes, no implicit padding */
+#define SWG_WINDOWS_ROWS 1u
+#define SWG_WINDOWS_SUMMARY 2u
+typedef struct swg_windows_request {
+  uint32_t want;          /* the two bits above */
+  uint32_t axis;          /* 0 = query, 1 = target */
+  uint32_t window;        /* W >= 1 */
+  uint32_t other_genome;  /* a genome id or SWG_WINDOWS_ANY */
+  const uint32_t* weight; /* [n] or NULL = rec->matches; host / device as the columns */
+  uint64_t n_rows;        /* out (rows bit) */
+  uint64_t capacity;      /* in: entries `rows` can hold */
+  swg_window_row* rows;   /* in: caller-owned [capacity] or NULL; written only when n_rows <= capacity */
+  uint64_t n_seqs;        /* out (summary bit) */
+  uint64_t seq_capacity;  /* in: entries `seqs` can hold */
+  swg_window_seq* seqs;   /* in: caller-owned [seq_capacity] or NULL; written only when n_seqs <= seq_capacity */
+  uint64_t reserved;      /* 0 */
+} swg_windows_request; /* 80 bytes, no implicit padding */
+/* rec: host pointers; seq_len[rec->n_seq], seq_genome[rec->n_seq], status[n] (or NULL) and req->weight on the host. */
+int swg_windows_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                        const uint8_t* status, swg_windows_request* req);
+/* The same with the columns of rec, seq_len, seq_genome, status and req->weight in device memory of ctx's GPU (as
+ * swg_filter_device leaves them: no copy in between); the request and its arrays stay on the host. */
+int swg_windows_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                               const uint8_t* status, swg_windows_request* req);
+/* Both texts of an open PAF from ONE device call (release each with swg_free) under its last-'#' genome map and the last-seen
+ * lengths of swg_paf_components, m = column 10; a text is asked for by a non-NULL out_text[k] on entry, as in swg_paf_place.
+ * Tab-separated, integers only:
+ *   text 0  header `#sequence start end n_all depth_all covered_all matches_all n_kept depth_kept covered_kept matches_kept`, then
+ *           one line per row (the first three columns make it a BED / bedGraph source).
+ *   text 1  header `#sequence length windows empty_all empty_kept covered_all covered_kept depth_all depth_kept matches_all
+ *           matches_kept records_all records_kept`, one line per listed sequence.
+ * other_genome: a genome name as the other reports print it, with or without its trailing '#'; NULL = any.  An unknown name is
+ * SWG_ERR_INVALID with the name in the message.  A PAF without records gives the header-only texts and needs no device (ctx may
+ * be NULL then).  axis > 1, window == 0: SWG_ERR_INVALID; a handle with rebased columns: SWG_ERR_UNSUPPORTED.  Errors:
+ * swg_alnstats_last_error(). */
+int swg_paf_windows(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t window, const char* other_genome,
+                    char** out_text, uint64_t* out_len);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

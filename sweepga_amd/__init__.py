@@ -19,6 +19,7 @@ from .sharing import RUN_DTYPE, Sharing, sharing_records, sharing_records_device
 from .mosaic import ROW_DTYPE, Mosaic, mosaic_records, mosaic_records_device  # noqa: F401
 from .gaps import Gaps, GapsResult, gaps_records, gaps_records_device  # noqa: F401  (its ROW_DTYPE / PAIR_DTYPE: sweepga_amd.gaps)
 from .place import Place, PlaceResult, place_records, place_records_device  # noqa: F401  (its ROW_DTYPE / PAIR_DTYPE: sweepga_amd.place)
+from .windows import Windows, WindowsResult, windows_records, windows_records_device  # noqa: F401  (its ROW_DTYPE / SEQ_DTYPE: sweepga_amd.windows)
 from .dotplot import Dotplot, DotplotResult, dotplot_records, dotplot_records_device  # noqa: F401
 from .lift import Lift, LiftClosure, LiftClosureResult, LiftResult, lift_closure_records, lift_closure_records_device, lift_records, lift_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401

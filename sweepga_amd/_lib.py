@@ -45,7 +45,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
-           "swg_place_records", "swg_place_records_device", "swg_paf_place"]
+           "swg_place_records", "swg_place_records_device", "swg_paf_place",
+           "swg_windows_records", "swg_windows_records_device", "swg_paf_windows"]
 
 
 class SwgError(RuntimeError):
@@ -234,6 +235,22 @@ class SwgPlaceRequest(C.Structure):
     _fields_ = [("want", C.c_uint32), ("axis", C.c_uint32), ("set", C.c_uint32), ("reserved", C.c_uint32), ("min_bases", C.c_uint64),
                 ("n_rows", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgPlacement)), ("n_pairs", C.c_uint64),
                 ("pair_capacity", C.c_uint64), ("pairs", C.POINTER(SwgPlacePair))]
+
+
+class SwgWindowRow(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("index", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("n", C.c_uint32 * 2),
+                ("covered", C.c_uint32 * 2), ("depth", C.c_uint64 * 2), ("matches", C.c_uint64 * 2)]
+
+
+class SwgWindowSeq(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("windows", C.c_uint32), ("empty", C.c_uint32 * 2), ("covered", C.c_uint64 * 2), ("depth", C.c_uint64 * 2),
+                ("matches", C.c_uint64 * 2), ("records", C.c_uint64 * 2)]
+
+
+class SwgWindowsRequest(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("axis", C.c_uint32), ("window", C.c_uint32), ("other_genome", C.c_uint32), ("weight", C.c_void_p),
+                ("n_rows", C.c_uint64), ("capacity", C.c_uint64), ("rows", C.POINTER(SwgWindowRow)), ("n_seqs", C.c_uint64),
+                ("seq_capacity", C.c_uint64), ("seqs", C.POINTER(SwgWindowSeq)), ("reserved", C.c_uint64)]
 
 
 class SwgMosaicRow(C.Structure):
@@ -514,6 +531,12 @@ def load():
         f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgPlaceRequest)]
     lib.swg_paf_place.restype = C.c_int
     lib.swg_paf_place.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_windows_records", "swg_windows_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgWindowsRequest)]
+    lib.swg_paf_windows.restype = C.c_int
+    lib.swg_paf_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_dotplot_records", "swg_dotplot_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

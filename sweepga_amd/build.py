@@ -14,6 +14,7 @@ SOURCES = ["swg_context.hip", "swg_sort.hip", "swg_sweep.hip", "swg_filter.hip",
            "swg_mosaic.hip", os.path.join("host", "mosaic_text.cpp"),
            "swg_gaps.hip", os.path.join("host", "gaps_text.cpp"),
            "swg_place.hip", os.path.join("host", "place_text.cpp"),
+           "swg_windows.hip", os.path.join("host", "windows_text.cpp"),
            os.path.join("host", "fasta_io.cpp"), os.path.join("host", "mash_host.cpp")]
 
 

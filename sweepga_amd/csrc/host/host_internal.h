@@ -142,6 +142,13 @@ std::string swg_place_rows_text(const swg_paf* p, const std::vector<uint32_t>& s
 // header, then one line per genome pair: genome partner_genome sequences reversed length bases total_bases
 std::string swg_place_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_place_pair>& pairs);
 
+// ---- windows (swg_windows.hip: kernels and seams; windows_text.cpp: the two texts of swg_paf_windows) ----
+// header, then one line per row: sequence start end n_all depth_all covered_all matches_all n_kept depth_kept covered_kept matches_kept
+std::string swg_windows_rows_text(const swg_paf* p, const std::vector<swg_window_row>& rows);
+// header, then one line per listed sequence: sequence length windows empty_all empty_kept covered_all covered_kept depth_all depth_kept
+// matches_all matches_kept records_all records_kept (seq_len: the lengths the device call read)
+std::string swg_windows_summary_text(const swg_paf* p, const std::vector<uint32_t>& seq_len, const std::vector<swg_window_seq>& seqs);
+
 // ---- tree sparsification (tree_filter.cpp: text route and the selection; swg_sparsify.hip: record routes; paf_io.cpp: handles) ----
 // one unordered genome pair with its sums; prefix[a] < prefix[b].  The reference accumulates in f64: integer sums below 2^53
 // are the same numbers.

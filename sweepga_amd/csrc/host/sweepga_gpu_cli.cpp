@@ -331,6 +331,19 @@ void write_mosaic(const std::string& rows_path, const std::string& share_path, s
   write_texts(paths, text, len, 2);
 }
 
+// --windows / --windows-summary: the rows and the summary of swg_paf_windows (depth, cover and identity per fixed window), both from
+// one device call when both are asked for.  "-" = standard error.
+void write_windows(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t axis,
+                   uint32_t window, const std::string& genome) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  if (swg_paf_windows(ctx, paf, status, axis, window, genome.empty() ? nullptr : genome.c_str(), text, len) != SWG_OK)
+    die(3, std::string("--windows: ") + swg_alnstats_last_error());
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
+}
+
 // --place / --place-summary: the rows and the summary of swg_paf_place (every sequence ordered and oriented along its best partner),
 // both from one device call when both are asked for.  "-" = standard error.
 void write_place(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t axis,
@@ -448,6 +461,10 @@ int main(int argc, char** argv) {
   uint32_t place_axis = 0, place_set = SWG_IV_KEPT;
   uint64_t place_min_bases = 0;
   bool place_flag = false;  // (one of --place-axis / --place-set / --place-min-bases was given)
+  std::string windows_path, windows_summary_path, windows_genome;  // --windows, --windows-summary: empty = no file; --windows-genome: empty = any
+  uint32_t windows_axis = 0;
+  uint64_t window_size = 10000;
+  bool windows_flag = false;  // (one of --window-size / --windows-axis / --windows-genome was given)
   bool mosaic_by_length = false, mosaic_flag = false;  // (mosaic_flag: one of --mosaic-axis / --mosaic-set / --mosaic-by was given)
   std::string dotplot_path, dotplot_layout_path, dotplot_query, dotplot_target;  // --dotplot, --dotplot-layout: empty = no file
   swg_dot_view dot_view{2048, 2048, nullptr, nullptr};
@@ -578,6 +595,24 @@ int main(int argc, char** argv) {
       if (!parse_metric_number(value(), &place_min_bases)) die(2, "bad --place-min-bases");
       place_flag = true;
     }
+    else if (a == "--windows") { windows_path = value(); if (windows_path.empty()) die(2, "empty value for --windows"); }
+    else if (a == "--windows-summary") { windows_summary_path = value(); if (windows_summary_path.empty()) die(2, "empty value for --windows-summary"); }
+    else if (a == "--window-size") {
+      if (!parse_metric_number(value(), &window_size) || window_size == 0 || window_size > 0xffffffffull) die(2, "invalid value for --window-size: 1 .. 2^32 - 1");
+      windows_flag = true;
+    }
+    else if (a == "--windows-axis") {
+      const std::string v = value();
+      if (v == "query") windows_axis = 0;
+      else if (v == "target") windows_axis = 1;
+      else die(2, "invalid value for --windows-axis: query or target");
+      windows_flag = true;
+    }
+    else if (a == "--windows-genome") {
+      windows_genome = value();
+      if (windows_genome.empty()) die(2, "empty value for --windows-genome");
+      windows_flag = true;
+    }
     else if (a == "--mosaic") { mosaic_path = value(); if (mosaic_path.empty()) die(2, "empty value for --mosaic"); }
     else if (a == "--mosaic-share") { mosaic_share_path = value(); if (mosaic_share_path.empty()) die(2, "empty value for --mosaic-share"); }
     else if (a == "--mosaic-axis") {
@@ -640,6 +675,7 @@ int main(int argc, char** argv) {
                 "         [--blocks FILE|-]\n"
                 "         [--gaps FILE|-] [--gaps-summary FILE|-] [--gaps-min-size N]\n"
                 "         [--place FILE|-] [--place-summary FILE|-] [--place-axis query|target] [--place-set kept|all] [--place-min-bases N]\n"
+                "         [--windows FILE|-] [--windows-summary FILE|-] [--window-size N] [--windows-axis query|target] [--windows-genome NAME]\n"
                 "         [--components REPORT|-] [--components-detailed] [--component-min-bases N] [--component-min-share F]\n"
                 "         [--lost FILE|-] [--covered FILE|-]\n"
                 "         [--sharing REPORT|-] [--sharing-detailed] [--sharing-bed FILE|-]\n"
@@ -677,6 +713,15 @@ int main(int argc, char** argv) {
                 "  --place-axis query|target  the sequences that are placed (default query)\n"
                 "  --place-set kept|all  the mappings that vote (default kept; with --no-filter kept = all)\n"
                 "  --place-min-bases N a row needs a best partner with at least N aligned bases; k/m/g suffixes (default 0)\n"
+                "  --windows FILE      after the filter: one line per window of every sequence that carries an inter-genome mapping --\n"
+                "                      `sequence start end n_all depth_all covered_all matches_all n_kept depth_kept covered_kept matches_kept`\n"
+                "                      (a BED / bedGraph source; integers: mean depth = depth / (end - start), identity = matches / depth,\n"
+                "                      breadth = covered / (end - start)), before (all) and after (kept) the filter; '-' = standard error\n"
+                "  --windows-summary FILE per sequence `length windows empty covered depth matches records`, all and kept side by side; with\n"
+                "                      --windows, both come from one device call\n"
+                "  --window-size N     the window in bases, 1 .. 2^32 - 1; k/m/g suffixes (default 10k)\n"
+                "  --windows-axis query|target  the sequences the windows lie on (default query)\n"
+                "  --windows-genome NAME  only the mappings whose other side belongs to this genome (default: any other genome)\n"
                 "  --components REPORT after the filter: per sequence its component -- the connected sets of sequences over the links\n"
                 "                      between sequence pairs that the kept mappings make -- with the component's sequences and length\n"
                 "                      and the sequence's own links, records and bases, as a tab-separated table computed on the device\n"
@@ -749,6 +794,9 @@ int main(int argc, char** argv) {
   if (place_path.empty() && place_summary_path.empty() && place_flag)
     die(2, "--place-axis, --place-set and --place-min-bases need --place or --place-summary");
   const bool place = !place_path.empty() || !place_summary_path.empty();
+  if (windows_path.empty() && windows_summary_path.empty() && windows_flag)
+    die(2, "--window-size, --windows-axis and --windows-genome need --windows or --windows-summary");
+  const bool windows = !windows_path.empty() || !windows_summary_path.empty();
   if (gaps_path.empty() && gaps_summary_path.empty() && gaps_flag) die(2, "--gaps-min-size needs --gaps or --gaps-summary");
   const bool gaps = !gaps_path.empty() || !gaps_summary_path.empty();
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
@@ -849,7 +897,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -915,6 +963,10 @@ int main(int argc, char** argv) {
   if (place && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--place: the file has a value >= 2^32, its columns are rebased: the placement of 64-bit columns is not supported");
+  }
+  if (windows && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--windows: the file has a value >= 2^32, its columns are rebased: the windows of 64-bit columns are not supported");
   }
   if ((!dotplot_path.empty() || !dotplot_layout_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
@@ -1001,6 +1053,12 @@ int main(int argc, char** argv) {
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_place(place_path, place_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), place_axis, place_set, place_min_bases);
+    }
+    if (windows) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_windows(windows_path, windows_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), windows_axis, (uint32_t)window_size, windows_genome);
     }
     if (!dotplot_path.empty() || !dotplot_layout_path.empty()) {  // nothing is dropped: the kept planes equal the all planes
       std::fflush(out);
@@ -1135,6 +1193,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_place(place_path, place_summary_path, ctx, paf, status.data(), place_axis, place_set, place_min_bases);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --place: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --windows / --windows-summary: likewise, both from one device call
+  if (windows) {
+    const auto tb = clk::now();
+    write_windows(windows_path, windows_summary_path, ctx, paf, status.data(), windows_axis, (uint32_t)window_size, windows_genome);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --windows: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --gaps / --gaps-summary: likewise, both from one device call
   if (gaps) {
