@@ -1716,9 +1716,83 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- the packed-key loop of the fused walk (see "The windows' part inside the ring" in chain_walk_kernel) -----------------
+// Lane masks are kept as what they are on the device, 64-bit scalars: a compare's ballot IS the compare (no 0 / 1 value made
+// and tested again), the window's bookkeeping (`open`, "inside the ring", "passes") is scalar and/or, and the two places where a
+// mask picks a per-lane value name it as the instruction's mask operand.
+__device__ __forceinline__ uint32_t mask_select(uint64_t m, uint32_t if_clear, uint32_t if_set) {
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(if_clear), "v"(if_set), "s"(m));
+  return r;
+}
+__device__ __forceinline__ uint32_t mask_select_or_zero(uint64_t m, uint32_t if_set) {
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(if_set), "s"(m));
+  return r;
+}
+__device__ __forceinline__ uint32_t mask_count(uint32_t n, uint64_t m) {  // n + (the lane's bit of m): add with carry-in
+  asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(n) : "s"(m) : "vcc");
+  return n;
+}
+
+constexpr uint64_t WALK_KEY_INF = 0x7ff0000000000000ull, WALK_KEY_BIT = 1ull << 62;
+enum WalkStrand { STRAND_PLUS = 0, STRAND_MINUS = 1, STRAND_LANE = 2 };
+
+// One loop for the wavefront, as long as its longest window inside the ring.  `c` is the loop's one counter: the byte offset of
+// ring slot j, not wrapped -- 4 * (i % BIGW + (j - i)), in [4, 8 * BIGW) -- so it addresses the ring (one mask), tells whether j is
+// still inside the window's part of the ring (c < lim) and is the key's low 16 bits (it grows with j, which is all the (d, j)
+// order of a lane's keys needs; BIGW <= 4096 keeps it in 16 bits).  It advances in every lane: a lane outside its window
+// stays outside (c only grows, `open` only loses lanes) and what it reads there is a slot of the ring, its key +infinity.
+// STRAND: the wavefront's strand where the range has one (the pair-resident path), else per lane (`minus`).  rr: the ring's
+// target column of the strand, t_start for '+', t_end for '-'.
+template <int BIGW, int STRAND>
+__device__ __forceinline__ void walk_key_loop(const uint32_t* rq, const uint32_t* rr, bool minus, uint32_t c, uint32_t lim, uint64_t& open_m,
+                                              uint32_t qe_i, uint32_t bound, uint32_t r_i, uint32_t gap32, uint32_t fifth32,
+                                              double kb[KC], uint32_t& cnt) {
+  static_assert(BIGW * 8 <= 0x10000, "the key's low 16 bits hold the ring slot's unwrapped byte offset");
+  uint32_t gap_v = gap32, fifth_v = fifth32, key_hi = (uint32_t)(WALK_KEY_BIT >> 32), inf_hi = (uint32_t)(WALK_KEY_INF >> 32);
+  asm volatile("" : "+v"(gap_v), "+v"(fifth_v), "+v"(key_hi), "+v"(inf_hi));  // (the limits and the key's constants sit in vector registers)
+  const char* const rq_b = reinterpret_cast<const char*>(rq);
+  const char* const rr_b = reinterpret_cast<const char*>(rr);
+  const int32_t next_lim = (int32_t)lim - 4;                      // (c and lim are below 2^16)
+  uint64_t in_m = open_m & __builtin_amdgcn_ballot_w64(c < lim);  // the lanes with a j to look at
+  while (in_m != 0ull) {
+    const uint32_t sl = c & (BIGW * 4u - 1u);
+    uint32_t qs_j = *reinterpret_cast<const uint32_t*>(rq_b + sl), r_j = *reinterpret_cast<const uint32_t*>(rr_b + sl);
+    asm volatile("" : "+v"(qs_j), "+v"(r_j));  // both reads issued here, one wait
+    const uint64_t le_m = __builtin_amdgcn_ballot_w64(qs_j <= bound);  // sorted by q_start (paf_filter.rs:794-796)
+    open_m &= le_m | ~in_m;
+    const uint32_t q_gap = absdiff_vv(qs_j, qe_i), r_gap = absdiff_vv(r_j, r_i);
+    // (at q_gap == 0 / r_gap == 0 either limit passes: the sides need no "or equal")
+    const uint32_t lim_q = qs_j < qe_i ? fifth_v : gap_v;
+    const bool gap_side = STRAND == STRAND_PLUS ? r_j > r_i : STRAND == STRAND_MINUS ? r_j < r_i : (r_j > r_i) != minus;
+    const uint32_t lim_r = gap_side ? gap_v : fifth_v;
+    const uint64_t ok_m = in_m & le_m & __builtin_amdgcn_ballot_w64(q_gap <= lim_q) & __builtin_amdgcn_ballot_w64(r_gap <= lim_r);
+    const uint32_t qa = q_gap << 8, ra = r_gap << 8;  // (their squares: the gaps' squares << 16; garbage when !ok)
+    const uint64_t add = ((uint64_t)key_hi << 32) | c;
+    const uint64_t key = (uint64_t)qa * qa + ((uint64_t)ra * ra + add);
+    const uint64_t sel = ((uint64_t)mask_select(ok_m, inf_hi, (uint32_t)(key >> 32)) << 32) | mask_select_or_zero(ok_m, (uint32_t)key);
+    cnt = mask_count(cnt, ok_m);
+    // (one statement, the list entries updated in place: no register copies at the loop's back edge)
+    static_assert(KC == 4, "the insertion is written for four list entries");
+    double t = __longlong_as_double((long long)sel), u;
+    asm("v_max_f64 %5, %0, %4\n\tv_min_f64 %0, %0, %4\n\t"
+        "v_max_f64 %4, %1, %5\n\tv_min_f64 %1, %1, %5\n\t"
+        "v_max_f64 %5, %2, %4\n\tv_min_f64 %2, %2, %4\n\t"
+        "v_min_f64 %3, %3, %5"
+        : "+v"(kb[0]), "+v"(kb[1]), "+v"(kb[2]), "+v"(kb[3]), "+v"(t), "=&v"(u));
+    in_m = open_m & __builtin_amdgcn_ballot_w64((int32_t)c < next_lim);  // (c + 4 < lim on this step's c: no second counter)
+    c += 4u;
+  }
+}
+
 // SPEC: a block of a long unit, run speculatively (own / prev views); a template parameter so that the main walk and the
 // speculative rounds are different kernels to a profiler (rocprofv3 and the library's own table then name the same launches).
-template <int BIGW, bool FUSED, bool SPEC>
+// PAIR: the chunk list of the pair-resident path (swg_pair.hip): made on the device, so its length is read here (n_blocks is
+// then the list's capacity), and a chunk never leaves one (query, target, strand) group -- the strand comes with the descriptor
+// (pad) and the group's end is the chunk's.  One strand per chunk means one target column in the ring (see `rt` below) and
+// the packed-key loop with the strand compiled in.  A template parameter: the ring's layout is fixed per kernel.
+template <int BIGW, bool FUSED, bool SPEC, bool PAIR = false>
 __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const SpecBlock* __restrict__ desc, uint32_t m,
                                                         const uint64_t* __restrict__ s_grp,
                                                         const uint32_t* __restrict__ s_qs,
@@ -1737,13 +1811,15 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
                                                         int walk_plain_lists = 0) {
   constexpr bool spec = SPEC;
   if (gate && *gate == 0) return;  // (a speculative round behind a round without changes: pair_walk_long_launch)
-  // The pair-resident path (swg_pair.hip): the chunk list is made on the device, so its length is read here (n_blocks is
-  // then the list's capacity), and a chunk never leaves one (query, target, strand) group -- the strand comes with the
-  // descriptor (pad) and the group's end is the chunk's: s_grp / s_gidx / group_begin are not read (nullptr).
+  static_assert(!PAIR || (FUSED && !SPEC), "the pair-resident chunk walk is the fused, non-speculative one");
+  // Ranges of the pair-resident path (PAIR, and its long chunks' blocks: SPEC with s_gidx == nullptr): s_grp / s_gidx /
+  // group_begin are not read (nullptr).
   if (n_blocks_dev) n_blocks = min(n_blocks, *n_blocks_dev);
-  const bool pair_desc = s_gidx == nullptr;
-  __shared__ unsigned long long ring[BIGW];          // scores of positions [base, base + BIGW) as this range sees them
-  __shared__ uint32_t rq[BIGW], rt[BIGW], re[BIGW];  // their q_start, t_start, t_end
+  const bool pair_desc = PAIR || s_gidx == nullptr;
+  __shared__ unsigned long long ring[BIGW];  // scores of positions [base, base + BIGW) as this range sees them
+  // their q_start, t_start, t_end.  PAIR: `rt` is the one target column that d(i, j) reads of a LATER element j -- t_start on
+  // the '+' strand, t_end on '-' -- and there is no `re` (5 KB of LDS per wavefront instead of 6: 32 of them per CU)
+  __shared__ uint32_t rq[BIGW], rt[BIGW], re[PAIR ? 1 : BIGW];
   __shared__ uint32_t hcnt[WALK_HASH];   // lowest lane naming a j that hashes here
   __shared__ uint32_t hnum[WALK_HASH];   // ... and how many lanes do
   __shared__ unsigned long long l_fd[64];  // the lanes' first choices, for the lanes that share a slot with one other lane
@@ -1756,6 +1832,13 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
   const bool wrap = max_gap == ~0ull;  // `max_gap + 1` (= reject) wraps to 0 in release Rust
   const bool can_cut = max_gap < (uint64_t(1) << 31);  // accepted gaps < 2^31: d cannot wrap and grows with the query gap
   const bool fast_keys = max_gap <= (uint64_t(1) << 22) && !walk_plain_lists;  // the candidates as packed keys (see the batch loop)
+  // Scores in key space: a chunk of whole units whose lists come from the packed-key loop keeps every score -- in the ring, in the
+  // lists, in `own` once a commit goes beyond the ring -- as bit 62 | d << 16, a key with its low 16 bits cleared.  A key's low
+  // bits are never zero, so `key < score` is `d < score's d`: the lists need no decoding of d, only of j.  Nobody else reads a
+  // chunk's scores (below); the rare paths that compute a plain d (beyond the ring, the whole window) convert it (to_score).
+  // Speculative blocks and the plain lists keep plain d: their scores cross blocks through memory.
+  const bool ks = FUSED && !SPEC && fast_keys;
+  auto to_score = [&](uint64_t d) -> uint64_t { return ks ? (WALK_KEY_BIT | (d << 16)) : d; };  // (ks: d < 2^45, gaps <= 2^22)
   for (int k = lane; k < WALK_HASH; k += 64) {
     hcnt[k] = 0xffffffffu;
     hnum[k] = 0;
@@ -1766,6 +1849,10 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
     const uint32_t b = D.bb, be = D.be, ue = D.ue;  // i runs over [b, be), j may reach into the next block (< ue)
     if (be <= b || ue - b < 2) continue;
     if (!SPEC && pair_desc && be - b >= LABEL_CAP_ELEMS) continue;  // a long unit of the pair-resident path: walked in blocks
+    // PAIR: the chunk's strand, the target column of a later element j (in the ring) and that of element i itself (loaded)
+    const bool minus_u = PAIR && (D.pad & 1u) != 0;
+    const uint32_t* __restrict__ const s_tj = minus_u ? s_te : s_ts;
+    const uint32_t* __restrict__ const s_ti = minus_u ? s_ts : s_te;
     auto view_ptr = [&](uint32_t p) -> unsigned long long* { return (spec && p >= be) ? &prev[p] : &own[p]; };
     auto view_load = [&](uint32_t p) -> uint64_t {
       return __hip_atomic_load(view_ptr(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1781,8 +1868,8 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
       const bool ok = p < ue;
       ring[p % BIGW] = (ok && SPEC) ? view_load(p) : INF;
       rq[p % BIGW] = ok ? s_qs[p] : 0xffffffffu;
-      rt[p % BIGW] = ok ? s_ts[p] : 0u;
-      re[p % BIGW] = ok ? s_te[p] : 0u;
+      rt[p % BIGW] = ok ? (PAIR ? s_tj[p] : s_ts[p]) : 0u;
+      if (!PAIR) re[p % BIGW] = ok ? s_te[p] : 0u;
     }
     wave_lds_sync();
     auto current = [&](uint32_t j) -> uint64_t {  // the committed score of j
@@ -1798,7 +1885,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
       uint64_t bd[KC];
       uint32_t bj[KC];
       uint32_t nv;                    // lists
-      uint32_t qe, ts, te, minus, ei; // own element
+      uint32_t qe, r, minus, ei;      // own element (r, PAIR: its target coordinate in d(i, j); else read from the ring)
     };
     auto prefetch = [&](uint32_t i0n, uint32_t base_n, bool refill) {
       Pre P;
@@ -1810,8 +1897,8 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
         if (pn < ue) {
           if (far_any) P.view = view_load(pn);
           P.q = s_qs[pn];
-          P.t = s_ts[pn];
-          P.e = s_te[pn];
+          P.t = PAIR ? s_tj[pn] : s_ts[pn];
+          if (!PAIR) P.e = s_te[pn];
         }
       }
       const uint32_t i = i0n + lane;
@@ -1822,7 +1909,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
         P.bj[c] = NONE;
       }
       P.nv = 0;
-      P.qe = P.ts = P.te = P.minus = 0;
+      P.qe = P.r = P.minus = 0;
       P.ei = ue;
       if (valid) {
         if (!spec && !pair_desc) {
@@ -1832,8 +1919,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
         }
         if (FUSED) {
           P.qe = s_qe[i];
-          P.ts = s_ts[i];
-          P.te = s_te[i];
+          if (PAIR) P.r = s_ti[i];
           P.minus = pair_desc ? D.pad & 1u : (uint32_t)(s_grp[i] & 1ull);  // (bit 0: the strand; bit 1 is the pair stage's mark)
         } else {
 #pragma unroll
@@ -1857,7 +1943,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
         ring[pn % BIGW] = cur.view;
         rq[pn % BIGW] = cur.q;
         rt[pn % BIGW] = cur.t;
-        re[pn % BIGW] = cur.e;
+        if (!PAIR) re[pn % BIGW] = cur.e;
         base += 64;
         wave_lds_sync();
       }
@@ -1879,72 +1965,52 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
       bool listed = false;  // (wave-uniform) the part of the windows inside the ring went through the packed-key loop
       uint32_t j_next = i + 1;
       bool open_next = valid;
+      // d(i, j) holds one target coordinate of i against one of j: plus strand t_end[i] against t_start[j], minus strand
+      // t_start[i] against t_end[j].  PAIR loads i's (the ring holds the other column only); else i's columns are in the ring
+      // themselves (base == i0: element i sits in slot i % BIGW), and the column of j is chosen once per element.
+      const bool minus_i = FUSED && (PAIR ? minus_u : cur.minus != 0);
+      const uint32_t r_own = !FUSED ? 0u : PAIR ? cur.r : (minus_i ? rt : re)[i % BIGW];
+      const uint32_t* const r_ring = (!PAIR && minus_i) ? re : rt;
       if (FUSED && fast_keys) {
         // The windows' part inside the ring, for gap limits up to 2^22 (the CLI's 50,000 among them): ONE loop for the
         // wavefront, as long as its longest window, without a branch in its body.  A candidate is one 64-bit key --
-        // bit 62 | d << 16 | (j - i), d = q_gap^2 + r_gap^2 < 2^45 -- and the keys are read as doubles: positive normal
+        // bit 62 | d << 16 | low, d = q_gap^2 + r_gap^2 < 2^45, low = the ring slot's unwrapped byte offset (non-zero, growing
+        // with j: walk_key_loop) -- and the keys are read as doubles: positive normal
         // numbers order like their bit patterns, so v_min_f64 / v_max_f64 are the 64-bit integer minimum and maximum in one
         // instruction each, and keeping the KC smallest keys in order is a chain of KC min / max pairs (no compare, no
         // select, no "does it enter the list" branch); a rejected pair is +infinity.  Keys are distinct ((j - i) is), so
         // the list is the (d, j)-ordered list of paf_filter.rs:798-836 exactly.  The per-lane loop this replaces spent
         // ~40 scalar and branch instructions per step on exec-mask bookkeeping and ~20 vector ones per insertion.
         const uint32_t qe_i = cur.qe;
-        const bool minus = cur.minus != 0;
         const uint64_t bound64 = (uint64_t)qe_i + max_gap;  // (no wrap: max_gap <= 2^22)
         const uint32_t bound = bound64 > 0xffffffffull ? 0xffffffffu : (uint32_t)bound64;
-        const uint32_t r_i = minus ? cur.ts : cur.te;
-        const uint32_t* r_ring = minus ? re : rt;
         const uint32_t e_ring = min(e_i, base + (uint32_t)BIGW);
-        constexpr uint64_t KEY_INF = 0x7ff0000000000000ull, KEY_BIT = 1ull << 62;
         double kb[KC];
 #pragma unroll
-        for (int c = 0; c < KC; ++c) kb[c] = __longlong_as_double((long long)KEY_INF);
-        // (the loop's own variables: `off` = j - i, `sl` = the ring slot's byte offset, both advanced only while the lane is
-        // inside its window; the two limits sit in vector registers, the key's bit 62 in the addend's high word)
-        uint32_t off = 1, cnt = 0, sl = ((i + 1) % BIGW) * 4u;
-        const uint32_t off_end = e_ring > i ? e_ring - i : 0u;  // j < e_ring  <=>  off < off_end
-        uint32_t gap_v = gap32, fifth_v = fifth32, key_hi = (uint32_t)(KEY_BIT >> 32);
-        asm volatile("" : "+v"(gap_v), "+v"(fifth_v), "+v"(key_hi));
-        const char* const rq_b = reinterpret_cast<const char*>(rq);
-        const char* const rr_b = reinterpret_cast<const char*>(r_ring);
-        bool open = valid;
-        for (;;) {
-          const bool in = open && off < off_end;
-          if (__ballot(in) == 0ull) break;
-          uint32_t qs_j = *reinterpret_cast<const uint32_t*>(rq_b + sl), r_j = *reinterpret_cast<const uint32_t*>(rr_b + sl);
-          asm volatile("" : "+v"(qs_j), "+v"(r_j));  // both reads issued here, one wait
-          const bool inw = in && qs_j <= bound;  // sorted by q_start (paf_filter.rs:794-796)
-          open = open && !(in && qs_j > bound);
-          const uint32_t q_gap = absdiff_vv(qs_j, qe_i), r_gap = absdiff_vv(r_j, r_i);
-          // (at q_gap == 0 / r_gap == 0 either limit passes: the sides need no "or equal")
-          const uint32_t lim_q = qs_j < qe_i ? fifth_v : gap_v;
-          const uint32_t lim_r = ((r_j > r_i) != minus) ? gap_v : fifth_v;
-          const bool ok = inw && q_gap <= lim_q && r_gap <= lim_r;
-          const uint32_t qa = q_gap << 8, ra = r_gap << 8;  // (their squares: the gaps' squares << 16; garbage when !ok)
-          const uint64_t add = ((uint64_t)key_hi << 32) | off;
-          uint64_t key = (uint64_t)qa * qa + ((uint64_t)ra * ra + add);
-          key = ok ? key : KEY_INF;
-          cnt += ok ? 1u : 0u;
-          const uint32_t step = in ? 1u : 0u;
-          off += step;
-          sl = (sl + (step << 2)) & (BIGW * 4u - 1u);
-          double t = __longlong_as_double((long long)key);
-#pragma unroll
-          for (int c = 0; c < KC; ++c) {  // (the list entry is updated in place: no register copies at the loop's back edge)
-            double hi = t;
-            if (c + 1 < KC) asm("v_max_f64 %0, %1, %2" : "=v"(hi) : "v"(kb[c]), "v"(t));
-            asm("v_min_f64 %0, %0, %1" : "+v"(kb[c]) : "v"(t));
-            t = hi;
-          }
-        }
-        const uint32_t j = i + off;
+        for (int c = 0; c < KC; ++c) kb[c] = __longlong_as_double((long long)WALK_KEY_INF);
+        // (the loop, its counter and the key's low bits: walk_key_loop)
+        const uint32_t off_end = e_ring > i ? e_ring - i : 0u;  // j < e_ring  <=>  j - i < off_end
+        const uint32_t c0 = (i % BIGW) * 4u;
+        uint32_t cnt = 0;
+        uint64_t open_m = __builtin_amdgcn_ballot_w64(valid);
+        if (!PAIR)
+          walk_key_loop<BIGW, STRAND_LANE>(rq, r_ring, minus_i, c0 + 4u, c0 + off_end * 4u, open_m, qe_i, bound, r_own, gap32, fifth32, kb, cnt);
+        else if (minus_u)  // (wave-uniform: the chunk's strand)
+          walk_key_loop<BIGW, STRAND_MINUS>(rq, rt, true, c0 + 4u, c0 + off_end * 4u, open_m, qe_i, bound, r_own, gap32, fifth32, kb, cnt);
+        else
+          walk_key_loop<BIGW, STRAND_PLUS>(rq, rt, false, c0 + 4u, c0 + off_end * 4u, open_m, qe_i, bound, r_own, gap32, fifth32, kb, cnt);
+        const bool open = mask_select_or_zero(open_m, 1u) != 0;
+        const uint32_t j = i + max(off_end, 1u);  // (of a lane whose window is still open: the first j beyond the ring's part)
         nv = cnt < (uint32_t)KC + 1u ? cnt : (uint32_t)KC + 1u;
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
           const uint64_t bits = (uint64_t)__double_as_longlong(kb[c]);
-          const bool none = bits == KEY_INF;
-          bd[c] = none ? INF : (bits & ~KEY_BIT) >> 16;
-          bj[c] = none ? NONE : i + (uint32_t)(bits & 0xffffu);
+          const bool none = bits == WALK_KEY_INF;
+          if (ks)
+            bd[c] = bits & ~0xffffull;  // (no entry: +infinity's pattern, above every score; read only below nv or to be displaced)
+          else
+            bd[c] = none ? INF : (bits & ~WALK_KEY_BIT) >> 16;
+          bj[c] = none ? NONE : (i & ~(uint32_t)(BIGW - 1)) + (((uint32_t)bits & 0xffffu) >> 2);  // (low bits: 4 * (i % BIGW + j - i))
         }
         listed = true;
         j_next = j;
@@ -1953,13 +2019,11 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
       if (FUSED && valid && (!listed || (open_next && j_next < e_i))) {
         // d(i, j) of paf_filter.rs:798-836 in 32-bit arithmetic, selects instead of branches (as in chain_candidates_wave_kernel)
         const uint32_t qe_i = cur.qe;
-        const bool minus = cur.minus != 0;
+        const bool minus = minus_i;
         const uint64_t bound64 = (uint64_t)qe_i + max_gap;  // wrapping, as release Rust
         const uint32_t bound = bound64 > 0xffffffffull ? 0xffffffffu : (uint32_t)bound64;
-        // the target coordinates that enter d(i, j): plus strand t_start[j] against t_end[i], minus strand t_end[j] against
-        // t_start[i] -- chosen once per element (two LDS reads per j instead of three)
-        const uint32_t r_i = minus ? cur.ts : cur.te;
-        const uint32_t* r_ring = minus ? re : rt;
+        // (two LDS reads per j instead of three: r_own / r_ring above)
+        const uint32_t r_i = r_own;
         const uint32_t* __restrict__ r_mem = minus ? s_te : s_ts;
         // one j: a gap is |a - b|; it passes when it is at most the limit on the gap side, a fifth of the limit on the
         // overlap side (the predicate of paf_filter.rs:798-836; with the limit at u64::MAX both bounds are 2^32 - 1:
@@ -1969,7 +2033,7 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
           const uint32_t lim_q = qs_j >= qe_i ? gap32 : fifth32;
           const uint32_t lim_r = (minus ? r_j <= r_i : r_j >= r_i) ? gap32 : fifth32;
           if ((q_gap > lim_q) | (r_gap > lim_r)) return;
-          const uint64_t d = (uint64_t)q_gap * q_gap + (uint64_t)r_gap * r_gap;  // wrapping, as release Rust
+          const uint64_t d = to_score((uint64_t)q_gap * q_gap + (uint64_t)r_gap * r_gap);  // wrapping, as release Rust
           if (nv <= (uint32_t)KC) ++nv;
           if (d < bd[KC - 1]) {  // insert keeping (d asc, j asc), see chain_candidates_kernel
             uint64_t cd = d;
@@ -2122,7 +2186,8 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
           for (uint32_t j0 = ii + 1; j0 < e_l; j0 += 64) {
             if (wstats && lane == 0) atomicAdd(&wstats[3], 1ull);  // their 64-element batches
             if (can_cut) {  // the batch starts past q_end[i] and its smallest query gap already reaches the best distance held
-              const uint64_t wmin = wave_min_u64(ld);
+              uint64_t wmin = wave_min_u64(ld);
+              if (ks && wmin != INF) wmin = (wmin & ~WALK_KEY_BIT) >> 16;  // (the cut compares plain distances)
               const uint64_t q0 = (j0 - base) < (uint32_t)BIGW ? (uint64_t)rq[j0 % BIGW] : (uint64_t)s_qs[j0];
               if (wmin != INF && q0 >= qe_l && (q0 - qe_l) * (q0 - qe_l) >= wmin) break;
             }
@@ -2136,8 +2201,15 @@ __global__ __launch_bounds__(64) void chain_walk_kernel(uint32_t n_blocks, const
             }
             if (in) {
               uint64_t d;
-              const uint64_t ts_j = inring ? rt[j % BIGW] : s_ts[j], te_j = inring ? re[j % BIGW] : s_te[j];
+              uint64_t ts_j, te_j;
+              if (PAIR) {  // chain_dist reads one target coordinate of j: t_start on '+', t_end on '-' -- the ring's column
+                ts_j = te_j = inring ? rt[j % BIGW] : s_tj[j];
+              } else {
+                ts_j = inring ? rt[j % BIGW] : s_ts[j];
+                te_j = inring ? re[j % BIGW] : s_te[j];
+              }
               if (chain_dist(minus_l, qe_l, ts_l, te_l, qs_j, ts_j, te_j, max_gap, fifth, &d)) {
+                d = to_score(d);
                 const uint64_t cur = current(j);
                 if (d < cur && d < ld) {
                   ld = d;
@@ -3230,7 +3302,7 @@ int pair_walk_launch(swg_ctx* ctx, uint32_t cap_chunks, const uint32_t* n_chunks
   if (cap_chunks == 0) return SWG_OK;
   static const uint64_t per_cu = getenv("SWG_WALK_BLOCKS") ? (uint64_t)atoi(getenv("SWG_WALK_BLOCKS")) : 128;  // (blocks per CU: 64 -> 128 took 10 % off the walk -- chunks are of uneven length, a finer grid balances them)
   const uint64_t wb = cap_chunks < (uint64_t)ctx->num_cu * per_cu ? cap_chunks : (uint64_t)ctx->num_cu * per_cu;
-  SWG_LAUNCH(ctx, "chain_walk", chain_walk_kernel<256, true, false><<<(unsigned)wb, 64, 0, ctx->stream>>>(
+  SWG_LAUNCH(ctx, "chain_walk", chain_walk_kernel<256, true, false, true><<<(unsigned)wb, 64, 0, ctx->stream>>>(
                                     cap_chunks, desc, 0u, nullptr, s_qs, s_qe, s_ts, s_te, nullptr, nullptr, 0u, max_gap, nullptr, nullptr,
                                     nullptr, bps, bps, pred, pred, nullptr, n_chunks_dev, nullptr, walk_plain_knob()));
   SWG_KERNEL_CHECK(ctx);
