@@ -977,6 +977,89 @@ int swg_lift_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t*
 int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
                  char** out_text, uint64_t* out_len);
 
+/* ---- base-exact lift: the rows of the lift refined through the records' CIGARs, on the device --------------
+ * Hits, clips, sets, axes, row order, summary and candidates are the lift's, unchanged.  A CIGAR SET names k records (strictly
+ * ascending) and gives each an ENTRY, a CIGAR text; only records that are hit need one (swg_lift_hit_records lists them).
+ * The walk: an op is 1 to 10 decimal digits, value < 2^32 (0 allowed), and one letter of MIDNSHP=X.  With offsets x (query) and y
+ * (target) from 0, in text order: M, = and X of length l make l aligned COLUMNS (x + i, y + i) and advance both; I advances x; D and
+ * N advance y; S, H and P advance nothing.  A column's target coordinate is t_start + y, its query coordinate q_start + x on '+' and
+ * q_end - 1 - x on '-' (PAF CIGARs run along the target's forward strand).
+ * Entry state, a byte, 0 = usable:  1 syntax (a foreign byte, a letter without digits, more than 10 digits, trailing digits);
+ * 2 an op value >= 2^32 (in at most 10 digits);  4 the query advances do not sum to q_end - q_start;  8 the target advances do not
+ * sum to t_end - t_start (both sums in 64 bits, and looked at only when neither 1 nor 2 is set);  16 the entry is empty (a record
+ * without CIGAR).  1 to 8 count as bad (cigar_bad), 16 does not.
+ * Exact row: for a hit with clip [ca, cb) on the source side and destination side [d0, d1), A = the columns whose source coordinate
+ * lies in [ca, cb); aligned = |A|, matches = the members of A from '=' ops.  A non-empty: dst = [min dst coordinate over A, max + 1).
+ * A empty (the clip lies in bases without a partner): dst_start = dst_end = p, with B = the columns whose source coordinate is < ca:
+ * on '+' p = max dst(B) + 1, or d0 when B is empty; on '-' p = min dst(B), or d1 when B is empty.  A row is exact when its record
+ * has an entry of state 0: flag SWG_LIFT_EXACT is set.  Every other row keeps the lift's interpolated dst, aligned = matches = 0 and
+ * the flag clear.  So dst lies inside [d0, d1], matches <= aligned <= min(cb - ca, dst_end - dst_start), a row with columns never
+ * shrinks when its region grows, and a record whose CIGAR is the single op `L M` with equal sides gives the interpolated interval.
+ * Capacity protocol and errors of swg_lift_records; besides: a set that is not strictly ascending, a record >= n, offset[0] != 0 or
+ * a decreasing offset: SWG_ERR_INVALID; k >= 2^31, or 2^31 ops or more: SWG_ERR_RANGE.  k == 0 or cigars == NULL: every row is
+ * interpolated (the first 32 bytes of each row are swg_lift_records' row).  ops, cigar_bad and state are written whenever the call
+ * succeeds; exact_rows is 0 when the rows were not written.  n == 0 records with k > 0 is SWG_ERR_INVALID (a record >= n); m == 0
+ * with k > 0 still parses the set.  Scratch from the arena on top of the lift's (SWG_ERR_OOM under a limit that does not hold it):
+ * per text byte 1 byte staged (host seam only) and 0.25 of a rank per 16 bytes, plus 8 per tile of 4,096; per op 32 bytes (four
+ * 64-bit prefix sums; the scans' own block sums are 1/4096 of that); per entry 5 bytes and, host seam only, the 12 of record[] and
+ * offset[]; per row 40 bytes more when the rows are written. */
+typedef struct swg_cigar_set {
+  const uint32_t* record; /* [k] strictly ascending record indices, each < n */
+  const uint64_t* offset; /* [k + 1], offset[0] = 0, non-decreasing: entry j is text[offset[j] .. offset[j + 1]) */
+  const char* text;       /* the CIGARs end to end, no separators */
+  uint64_t k;
+} swg_cigar_set; /* 32 bytes */
+typedef struct swg_lift_exact_row {
+  uint32_t region, record;     /* the eight words of swg_lift_row */
+  uint32_t src_start, src_end;
+  uint32_t dst_seq;
+  uint32_t dst_start, dst_end;
+  uint32_t flags;              /* bits 0 and 1 as in swg_lift_row, bit 2: SWG_LIFT_EXACT */
+  uint32_t aligned, matches;   /* columns inside the clip, and those of them from '=' ops; 0 on an interpolated row */
+} swg_lift_exact_row; /* 40 bytes */
+#define SWG_LIFT_EXACT 4u
+#define SWG_CIGAR_SYNTAX 1u /* entry states */
+#define SWG_CIGAR_VALUE 2u
+#define SWG_CIGAR_QUERY_SUM 4u
+#define SWG_CIGAR_TARGET_SUM 8u
+#define SWG_CIGAR_EMPTY 16u
+typedef struct swg_lift_exact_request {
+  uint32_t set, axes;          /* as in swg_lift_request */
+  uint64_t n;                  /* out: rows */
+  uint64_t candidates[2];      /* out */
+  uint64_t capacity;           /* in: entries `rows` can hold */
+  swg_lift_exact_row* rows;    /* in: caller-owned [capacity] or NULL; written only when n <= capacity */
+  swg_lift_summary* summary;   /* in: caller-owned [m] or NULL; written whenever non-NULL */
+  uint8_t* state;              /* in: caller-owned [k] or NULL; written whenever non-NULL */
+  uint64_t ops;                /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;          /* out: entries with a state bit of 1 .. 8 */
+  uint64_t exact_rows;         /* out: rows with SWG_LIFT_EXACT; 0 when the rows were not written */
+} swg_lift_exact_request; /* 88 bytes */
+/* Everything on the host. */
+int swg_lift_exact_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                           const swg_cigar_set* cigars, swg_lift_exact_request* req);
+/* Columns, strand, status, regions and the three arrays of the set in device memory of ctx's GPU; the set structure itself, the
+ * request, its rows, summary and state on the host. */
+int swg_lift_exact_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                                  const swg_cigar_set* cigars, swg_lift_exact_request* req);
+/* The distinct records with at least one hit of `set` on the wanted axes, ascending: the records whose CIGARs an exact call needs.
+ * *k receives their number; out (host, [capacity], may be NULL) is written only when *k <= capacity.  Checks and errors of
+ * swg_lift_records; one byte per record of scratch on top of the lift's and its rows. */
+int swg_lift_hit_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m, uint32_t set,
+                         uint32_t axes, uint32_t* out, uint64_t capacity, uint64_t* k);
+/* The same with the columns, strand, status and regions in device memory; out and k on the host. */
+int swg_lift_hit_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                                uint32_t set, uint32_t axes, uint32_t* out, uint64_t capacity, uint64_t* k);
+/* swg_paf_lift through the CIGARs of the handle's own lines: contract, BED parser, marking protocol and refusals of swg_paf_lift.
+ * The hit records come from the device (swg_lift_hit_records), the LAST cg:Z: tag of each one's line is its entry (the parser's
+ * "last writer wins"; a line without the tag gives an empty entry), then one exact call.  Rows text: the ten columns of swg_paf_lift,
+ * then `aligned matches mode`, mode = exact | interp.  The summary text is swg_paf_lift's. */
+int swg_paf_lift_exact(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                       char** out_text, uint64_t* out_len);
+/* What the calling thread's last successful swg_paf_lift_exact met: records hit, entries of state 0, bad entries, records without
+ * a tag. */
+void swg_paf_lift_exact_counts(uint64_t out[4]);
+
 /* ---- transitive lift: the closure of each region under the lift, hop by hop, on the device -----------------
  * Per region, independently of every other region (all sets are point sets per sequence, all arithmetic is in integers):
  *   hop 0      F_0 = V_0 = { [start, end) on seq } when seq is known and start < end, else both empty

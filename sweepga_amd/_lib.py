@@ -43,6 +43,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_dotplot_records", "swg_dotplot_records_device", "swg_paf_dotplot",
            "swg_lift_records", "swg_lift_records_device", "swg_paf_lift",
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
+           "swg_lift_exact_records", "swg_lift_exact_records_device", "swg_lift_hit_records", "swg_lift_hit_records_device",
+           "swg_paf_lift_exact", "swg_paf_lift_exact_counts",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
@@ -292,6 +294,20 @@ class SwgLiftSummary(C.Structure):
 class SwgLiftRequest(C.Structure):
     _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
                 ("rows", C.c_void_p), ("summary", C.c_void_p)]
+
+
+class SwgCigarSet(C.Structure):
+    _fields_ = [("record", C.c_void_p), ("offset", C.c_void_p), ("text", C.c_void_p), ("k", C.c_uint64)]
+
+
+class SwgLiftExactRow(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("region", "record", "src_start", "src_end", "dst_seq", "dst_start", "dst_end", "flags", "aligned", "matches")]
+
+
+class SwgLiftExactRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
+                ("rows", C.c_void_p), ("summary", C.c_void_p), ("state", C.c_void_p), ("ops", C.c_uint64), ("cigar_bad", C.c_uint64),
+                ("exact_rows", C.c_uint64)]
 
 
 class SwgClosureRow(C.Structure):
@@ -550,6 +566,19 @@ def load():
     lib.swg_paf_lift.restype = C.c_int
     lib.swg_paf_lift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_uint64)]
+    for name in ("swg_lift_exact_records", "swg_lift_exact_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SwgCigarSet), C.POINTER(SwgLiftExactRequest)]
+    for name in ("swg_lift_hit_records", "swg_lift_hit_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                      C.POINTER(C.c_uint64)]
+    lib.swg_paf_lift_exact.restype = C.c_int
+    lib.swg_paf_lift_exact.argtypes = lib.swg_paf_lift.argtypes
+    lib.swg_paf_lift_exact_counts.restype = None
+    lib.swg_paf_lift_exact_counts.argtypes = [C.POINTER(C.c_uint64)]
     for name in ("swg_lift_closure_records", "swg_lift_closure_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

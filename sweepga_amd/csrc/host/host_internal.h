@@ -115,7 +115,20 @@ int swg_paf_seq_last_lengths(const swg_paf* p, std::vector<uint32_t>* seq_len);
 // columns of rec, status and regions on the host (on_device = false: staged in the arena) or on the device; req on the host
 int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                  swg_lift_request* req);
-// the same for the transitive lift (swg_lift_closure.hip)
+// ---- base-exact lift (swg_cigar.hip: kernels and record seams; lift_text.cpp: swg_paf_lift_exact;
+//      cigar_text.cpp: the tag finder and the row formatter; paf_io.cpp: the handle's lines) ----
+// the arrays of the set on the host (on_device = false) or on the device, like the columns; the set structure and req on the host
+int swg_lift_exact_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                       const swg_cigar_set* cigars, swg_lift_exact_request* req);
+int swg_lift_hit_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                     uint32_t set, uint32_t axes, uint32_t* out, uint64_t capacity, uint64_t* k);
+// the value of the last cg:Z: tag of a PAF line (len bytes, with or without its line end), or nullptr; *value_len its length
+const char* swg_cigar_tag_find(const char* line, uint64_t len, uint64_t* value_len);
+// one line of the exact rows text: dst_name dst_start dst_end label src_name src_start src_end strand axis record aligned matches mode
+void swg_lift_exact_row_text(std::string& o, const char* dst_name, const std::string& label, const std::string& src_name, const swg_lift_exact_row& w);
+// the handle's text and each record's line in it
+void swg_paf_lines_view(const swg_paf* p, const char** text, const uint64_t** rec_off, const uint32_t** rec_len);
+// ---- transitive lift (swg_lift_closure.hip): swg_lift_run's arguments ----
 int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                          swg_closure_request* req);
 // hop 0 on the host (lift_text.cpp), all there is without records: validates the regions (returns the lift's bad-input bits, 0 = fine),

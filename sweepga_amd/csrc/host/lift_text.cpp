@@ -1,5 +1,6 @@
 // swg_paf_lift: BED regions parsed on the host, lifted through an open PAF by one device call
-// (swg_lift.hip), and the two texts -- rows and per-region summary -- written with the handle's names.  swg_paf_lift_closure
+// (swg_lift.hip), and the two texts -- rows and per-region summary -- written with the handle's names.  swg_paf_lift_exact (section
+// 30) is the same through the CIGARs of the hit records' lines (swg_cigar.hip, cigar_text.cpp).  swg_paf_lift_closure
 // (section 24) is the same around the transitive lift (swg_lift_closure.hip), with hop 0 on the host for a PAF without records.
 #include <algorithm>
 #include <cstdint>
@@ -8,12 +9,14 @@
 #include <new>
 #include <string>
 #include <string_view>
+#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "../../../include/sweepga_gpu.h"
 #include "host_internal.h"
+#include "threads.h"
 
 namespace {
 
@@ -76,21 +79,51 @@ int parse_bed(const char* who, const char* bed, uint64_t len, const std::unorder
   return SWG_OK;
 }
 
-}  // namespace
+// the counts of the calling thread's last successful swg_paf_lift_exact: records hit, state 0, bad, without a tag
+thread_local uint64_t exact_counts[4] = {0, 0, 0, 0};
 
-extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
-                            char** out_text, uint64_t* out_len) {
-  if (!p || !out_text || !out_len || (!bed && bed_len)) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: NULL argument");
+// The CIGAR set of the records `hit` (ascending) of an open PAF: the last cg:Z: tag of each one's line, found by host threads over
+// rec_off / rec_len, laid end to end; a line without the tag gives an empty entry.  Returns the entries without a tag.
+uint64_t gather_cigars(const swg_paf* p, const std::vector<uint32_t>& hit, std::vector<uint64_t>* offset, std::string* text) {
+  const char* paf_text;
+  const uint64_t* rec_off;
+  const uint32_t* rec_len;
+  swg_paf_lines_view(p, &paf_text, &rec_off, &rec_len);
+  const uint64_t k = hit.size();
+  std::vector<const char*> at(k);
+  offset->assign(k + 1, 0);
+  const int threads = (int)std::min<uint64_t>(std::max(1u, std::min(16u, std::thread::hardware_concurrency())), k / 4096 + 1);
+  swg_host::run(threads, [&](int t) {
+    for (uint64_t j = k * t / threads; j < k * (t + 1) / threads; ++j)
+      at[j] = swg_cigar_tag_find(paf_text + rec_off[hit[j]], rec_len[hit[j]], &(*offset)[j + 1]);
+  });
+  uint64_t untagged = 0;
+  for (uint64_t j = 0; j < k; ++j) {
+    untagged += at[j] == nullptr;
+    (*offset)[j + 1] += (*offset)[j];
+  }
+  text->resize((*offset)[k]);
+  swg_host::run(threads, [&](int t) {
+    for (uint64_t j = k * t / threads; j < k * (t + 1) / threads; ++j)
+      if (at[j]) std::memcpy(&(*text)[(*offset)[j]], at[j], (*offset)[j + 1] - (*offset)[j]);
+  });
+  return untagged;
+}
+
+// swg_paf_lift and swg_paf_lift_exact: one contract, one BED parser, one summary text; `exact` routes the rows through the CIGARs
+int paf_lift(const char* who, bool exact, swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set,
+             uint32_t axes, char** out_text, uint64_t* out_len) {
+  if (!p || !out_text || !out_len || (!bed && bed_len)) return swg_alnstats_error(SWG_ERR_INVALID, "%s: NULL argument", who);
   const bool wanted[2] = {out_text[0] != nullptr, out_text[1] != nullptr};
   out_text[0] = out_text[1] = nullptr;
   out_len[0] = out_len[1] = 0;
-  if (!wanted[0] && !wanted[1]) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: neither text is asked for");
-  if (set > 1) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: set must be SWG_IV_ALL or SWG_IV_KEPT");
-  if (axes == 0 || axes >> 2) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: axes names nothing, or a bit beyond the two");
-  if (set == SWG_IV_KEPT && !status) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: the kept rows need a status column");
+  if (!wanted[0] && !wanted[1]) return swg_alnstats_error(SWG_ERR_INVALID, "%s: neither text is asked for", who);
+  if (set > 1) return swg_alnstats_error(SWG_ERR_INVALID, "%s: set must be SWG_IV_ALL or SWG_IV_KEPT", who);
+  if (axes == 0 || axes >> 2) return swg_alnstats_error(SWG_ERR_INVALID, "%s: axes names nothing, or a bit beyond the two", who);
+  if (set == SWG_IV_KEPT && !status) return swg_alnstats_error(SWG_ERR_INVALID, "%s: the kept rows need a status column", who);
   if (swg_paf_seq_offsets(p) || swg_paf_record_offsets(p, 0))
     return swg_alnstats_error(SWG_ERR_UNSUPPORTED,
-                              "swg_paf_lift: the file has a value >= 2^32, its columns are rebased: a lift through 64-bit columns is not supported");
+                              "%s: the file has a value >= 2^32, its columns are rebased: a lift through 64-bit columns is not supported", who);
   try {
     const uint32_t n_names = swg_paf_num_sequences(p);
     std::unordered_map<std::string_view, uint32_t> ids;
@@ -98,49 +131,91 @@ extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* statu
     for (uint32_t s = 0; s < n_names; ++s) ids.emplace(swg_paf_sequence_name(p, s), s);
     std::vector<swg_lift_region> regions;
     std::vector<BedRegion> bed_text;
-    const int parsed = parse_bed("swg_paf_lift", bed, bed_len, ids, &regions, &bed_text);
+    const int parsed = parse_bed(who, bed, bed_len, ids, &regions, &bed_text);
     if (parsed != SWG_OK) return parsed;
     const swg_records* rec = swg_paf_records(p);
     const uint64_t m = regions.size();
     std::string text[2];
     text[1] = "label\tsequence\tstart\tend\tall_q\tall_t\tkept_q\tkept_t\tstate\n";
+    uint64_t counts[4] = {0, 0, 0, 0};
     if (m && rec->n) {
-      if (!ctx) return swg_alnstats_error(SWG_ERR_INVALID, "swg_paf_lift: NULL context");
+      if (!ctx) return swg_alnstats_error(SWG_ERR_INVALID, "%s: NULL context", who);
       std::vector<swg_lift_summary> summary(m);
-      std::vector<swg_lift_row> rows;
-      swg_lift_request req{};
-      req.set = set, req.axes = axes;
-      req.summary = summary.data();
-      if (wanted[0]) {  // a first guess at the rows; a second call when there are more
-        rows.resize(std::max<uint64_t>(4 * m, uint64_t(1) << 16));
-        req.capacity = rows.size(), req.rows = rows.data();
-      }
-      int rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
-      if (rc == SWG_OK && wanted[0] && req.n > req.capacity) {
-        rows.resize(req.n);
-        req.capacity = rows.size(), req.rows = rows.data();
-        rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
-      }
-      if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
-      if (wanted[0]) {
-        for (uint64_t k = 0; k < req.n; ++k) {
-          const swg_lift_row& w = rows[k];
-          const uint32_t ax = w.flags >> 1 & 1u;
-          std::string& o = text[0];
-          o += swg_paf_sequence_name(p, w.dst_seq);
-          o += '\t';
-          append_u64(o, w.dst_start, '\t');
-          append_u64(o, w.dst_end, '\t');
-          o += bed_text[w.region].label;
-          o += '\t';
-          o += bed_text[w.region].name;
-          o += '\t';
-          append_u64(o, w.src_start, '\t');
-          append_u64(o, w.src_end, '\t');
-          o += w.flags & SWG_LIFT_MINUS ? "-\t" : "+\t";
-          o += ax ? "t\t" : "q\t";
-          append_u64(o, w.record, '\n');
+      if (!exact) {
+        std::vector<swg_lift_row> rows;
+        swg_lift_request req{};
+        req.set = set, req.axes = axes;
+        req.summary = summary.data();
+        if (wanted[0]) {  // a first guess at the rows; a second call when there are more
+          rows.resize(std::max<uint64_t>(4 * m, uint64_t(1) << 16));
+          req.capacity = rows.size(), req.rows = rows.data();
         }
+        int rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
+        if (rc == SWG_OK && wanted[0] && req.n > req.capacity) {
+          rows.resize(req.n);
+          req.capacity = rows.size(), req.rows = rows.data();
+          rc = swg_lift_run(ctx, rec, false, status, regions.data(), m, &req);
+        }
+        if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+        if (wanted[0]) {
+          for (uint64_t k = 0; k < req.n; ++k) {
+            const swg_lift_row& w = rows[k];
+            const uint32_t ax = w.flags >> 1 & 1u;
+            std::string& o = text[0];
+            o += swg_paf_sequence_name(p, w.dst_seq);
+            o += '\t';
+            append_u64(o, w.dst_start, '\t');
+            append_u64(o, w.dst_end, '\t');
+            o += bed_text[w.region].label;
+            o += '\t';
+            o += bed_text[w.region].name;
+            o += '\t';
+            append_u64(o, w.src_start, '\t');
+            append_u64(o, w.src_end, '\t');
+            o += w.flags & SWG_LIFT_MINUS ? "-\t" : "+\t";
+            o += ax ? "t\t" : "q\t";
+            append_u64(o, w.record, '\n');
+          }
+        }
+      } else {
+        // the hit records, their CIGARs from the lines, then the exact call: the lift's index is built once for the list and once
+        // for the rows
+        std::vector<uint32_t> hit(std::max<uint64_t>(4 * m, uint64_t(1) << 16));
+        uint64_t k = 0;
+        int rc = swg_lift_hit_run(ctx, rec, false, status, regions.data(), m, set, axes, hit.data(), hit.size(), &k);
+        if (rc == SWG_OK && k > hit.size()) {
+          hit.resize(k);
+          rc = swg_lift_hit_run(ctx, rec, false, status, regions.data(), m, set, axes, hit.data(), hit.size(), &k);
+        }
+        if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+        hit.resize(k);
+        std::vector<uint64_t> offset;
+        std::string cigar_text;
+        counts[3] = gather_cigars(p, hit, &offset, &cigar_text);
+        const swg_cigar_set cigars{hit.data(), offset.data(), cigar_text.data(), k};
+        std::vector<swg_lift_exact_row> rows;
+        swg_lift_exact_request req{};
+        req.set = set, req.axes = axes;
+        req.summary = summary.data();
+        std::vector<uint8_t> state(k);
+        req.state = k ? state.data() : nullptr;
+        if (wanted[0]) {
+          rows.resize(std::max<uint64_t>(4 * m, uint64_t(1) << 16));
+          req.capacity = rows.size(), req.rows = rows.data();
+        }
+        rc = swg_lift_exact_run(ctx, rec, false, status, regions.data(), m, &cigars, &req);
+        if (rc == SWG_OK && wanted[0] && req.n > req.capacity) {
+          rows.resize(req.n);
+          req.capacity = rows.size(), req.rows = rows.data();
+          rc = swg_lift_exact_run(ctx, rec, false, status, regions.data(), m, &cigars, &req);
+        }
+        if (rc != SWG_OK) return swg_alnstats_error(rc, "%s", swg_last_error(ctx));
+        counts[0] = k, counts[1] = (uint64_t)std::count(state.begin(), state.end(), uint8_t(0)), counts[2] = req.cigar_bad;
+        if (wanted[0])
+          for (uint64_t r = 0; r < req.n; ++r) {
+            const swg_lift_exact_row& w = rows[r];
+            swg_lift_exact_row_text(text[0], swg_paf_sequence_name(p, w.dst_seq), bed_text[w.region].label, bed_text[w.region].name, w);
+          }
       }
       if (wanted[1]) {
         for (uint64_t r = 0; r < m; ++r) {
@@ -165,11 +240,27 @@ extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* statu
         }
       }
     }
-    return texts_hand_over(text, wanted, 2, out_text, out_len);
+    const int rc = texts_hand_over(text, wanted, 2, out_text, out_len);
+    if (rc == SWG_OK && exact) std::memcpy(exact_counts, counts, sizeof counts);
+    return rc;
   } catch (const std::bad_alloc&) {
     return swg_alnstats_error(SWG_ERR_OOM, "out of host memory");
   }
 }
+
+}  // namespace
+
+extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                            char** out_text, uint64_t* out_len) {
+  return paf_lift("swg_paf_lift", false, ctx, p, status, bed, bed_len, set, axes, out_text, out_len);
+}
+
+extern "C" int swg_paf_lift_exact(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set,
+                                  uint32_t axes, char** out_text, uint64_t* out_len) {
+  return paf_lift("swg_paf_lift_exact", true, ctx, p, status, bed, bed_len, set, axes, out_text, out_len);
+}
+
+extern "C" void swg_paf_lift_exact_counts(uint64_t out[4]) { std::memcpy(out, exact_counts, sizeof exact_counts); }
 
 uint32_t swg_closure_hop0_host(const swg_lift_region* regions, uint64_t m, uint32_t n_seq, swg_closure_request* req) {
   uint64_t n = 0;

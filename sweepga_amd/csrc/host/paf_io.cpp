@@ -1589,6 +1589,11 @@ void swg_paf_tree_view(const swg_paf* p, swg_tree_handle_view* v) {
   v->text_len = p->text.len;
   v->rec_off = p->rec_off.data();
 }
+void swg_paf_lines_view(const swg_paf* p, const char** text, const uint64_t** rec_off, const uint32_t** rec_len) {
+  *text = p->text.data;
+  *rec_off = p->rec_off.data();
+  *rec_len = p->rec_len.data();
+}
 void swg_aln_tree_view(const swg_aln* a, swg_tree_handle_view* v) {
   v->rec = &a->rec;
   v->prefix_two = &a->g_two_prefix;

@@ -385,13 +385,22 @@ void write_dotplot(const std::string& image_path, const std::string& layout_path
 }
 
 // --lift / --lift-summary: the rows and the summary of swg_paf_lift (BED regions projected through the mappings), both from one
-// device call when both are asked for.  "-" = standard error.
+// device call when both are asked for.  "-" = standard error.  exact (--lift-exact): through swg_paf_lift_exact, the rows refined
+// through the cg:Z: tags of the lines that are hit; what it met goes to standard error in one line.
 void write_lift(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
-                const std::string& bed, uint32_t set, uint32_t axes) {
+                const std::string& bed, uint32_t set, uint32_t axes, bool exact, bool quiet) {
   char marker = 0;  // (a text is asked for by a non-NULL entry)
   char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
   uint64_t len[2] = {0, 0};
-  if (swg_paf_lift(ctx, paf, status, bed.data(), bed.size(), set, axes, text, len) != SWG_OK) die(3, std::string("--lift: ") + swg_alnstats_last_error());
+  const int rc = exact ? swg_paf_lift_exact(ctx, paf, status, bed.data(), bed.size(), set, axes, text, len)
+                       : swg_paf_lift(ctx, paf, status, bed.data(), bed.size(), set, axes, text, len);
+  if (rc != SWG_OK) die(3, std::string(exact ? "--lift-exact: " : "--lift: ") + swg_alnstats_last_error());
+  if (exact && !quiet) {
+    uint64_t c[4];
+    swg_paf_lift_exact_counts(c);
+    std::fprintf(stderr, "[sweepga-gpu] --lift-exact: %llu records hit, %llu exact, %llu bad, %llu without a cg:Z: tag\n", (unsigned long long)c[0],
+                 (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3]);
+  }
   const std::string* paths[2] = {&rows_path, &summary_path};
   write_texts(paths, text, len, 2);
 }
@@ -472,6 +481,7 @@ int main(int argc, char** argv) {
   std::string lift_regions_path, lift_path, lift_summary_path, lift_bed;  // --lift-regions, --lift, --lift-summary: empty = not given
   uint32_t lift_set = SWG_IV_KEPT, lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
   bool lift_flag = false;  // (--lift-set or --lift-axis was given)
+  bool lift_exact = false;  // --lift-exact: the rows of --lift through the CIGARs
   std::string closure_path, closure_summary_path;  // --lift-closure, --lift-closure-summary: empty = not given
   uint64_t lift_hops = 0, lift_min_length = 100;   // --lift-hops (0 = not given), --lift-min-length
   bool lift_min_length_flag = false;
@@ -568,6 +578,7 @@ int main(int argc, char** argv) {
     else if (a == "--lift-regions") { lift_regions_path = value(); if (lift_regions_path.empty()) die(2, "empty value for --lift-regions"); }
     else if (a == "--lift") { lift_path = value(); if (lift_path.empty()) die(2, "empty value for --lift"); }
     else if (a == "--lift-summary") { lift_summary_path = value(); if (lift_summary_path.empty()) die(2, "empty value for --lift-summary"); }
+    else if (a == "--lift-exact") lift_exact = true;
     else if (a == "--lift-hops") { if (!parse_u64(value(), &lift_hops) || lift_hops < 1 || lift_hops > 65535) die(2, "invalid value for --lift-hops: 1 .. 65535"); }
     else if (a == "--lift-closure") { closure_path = value(); if (closure_path.empty()) die(2, "empty value for --lift-closure"); }
     else if (a == "--lift-closure-summary") { closure_summary_path = value(); if (closure_summary_path.empty()) die(2, "empty value for --lift-closure-summary"); }
@@ -682,6 +693,7 @@ int main(int argc, char** argv) {
                 "         [--mosaic FILE|-] [--mosaic-share FILE|-] [--mosaic-axis query|target] [--mosaic-set kept|all] [--mosaic-by matches|length]\n"
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
+                "         [--lift-exact]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
@@ -766,6 +778,9 @@ int main(int argc, char** argv) {
                 "                      - = standard error)\n"
                 "  --lift-summary FILE `label sequence start end all_q all_t kept_q kept_t state` per region: its hits before and after the\n"
                 "                      filter; state lost = the filter left it without a projection; with --lift, one device call\n"
+                "  --lift-exact        project the rows of --lift base by base through the cg:Z: CIGARs of the lines that are hit (parsed on\n"
+                "                      the device): three more columns `aligned matches mode`, mode exact | interp (no usable CIGAR on the\n"
+                "                      line: the interpolated row); needs --lift-regions and --lift; one line of counts on standard error\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
                 "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
@@ -806,6 +821,7 @@ int main(int argc, char** argv) {
     die(2, "--lift, --lift-summary, --lift-set and --lift-axis need --lift-regions");
   if (!lift_hops && (!closure_path.empty() || !closure_summary_path.empty() || lift_min_length_flag))
     die(2, "--lift-closure, --lift-closure-summary and --lift-min-length need --lift-hops");
+  if (lift_exact && (!lift || lift_path.empty())) die(2, "--lift-exact needs --lift-regions and --lift");
   if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
   if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
   if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
@@ -1070,7 +1086,7 @@ int main(int argc, char** argv) {
       std::fflush(out);
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
       const std::vector<uint8_t> every(n ? n : 1, 1);
-      if (lift_once) write_lift(lift_path, lift_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes);
+      if (lift_once) write_lift(lift_path, lift_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes, lift_exact, quiet);
       if (lift_hops)
         write_lift_closure(closure_path, closure_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes,
                            (uint32_t)lift_hops, (uint32_t)lift_min_length);
@@ -1239,7 +1255,7 @@ int main(int argc, char** argv) {
   // ---- --lift / --lift-summary: on the first context (with --sparsify: "all" is the whole input, "kept" what is written)
   if (lift) {
     const auto tb = clk::now();
-    if (lift_once) write_lift(lift_path, lift_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes);
+    if (lift_once) write_lift(lift_path, lift_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes, lift_exact, quiet);
     if (lift_once && !quiet) std::fprintf(stderr, "[sweepga-gpu] --lift: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
     if (lift_hops) {  // --lift-hops: the transitive lift through the same set and axes
       const auto tc = clk::now();

@@ -263,8 +263,10 @@ int bad_input(swg_ctx* ctx, uint64_t bad) {
   return SWG_OK;
 }
 
-// inside an arena frame; c and regions hold device pointers
-int lift_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, const swg_lift_region* regions, uint64_t m, swg_lift_request* req) {
+// inside an arena frame; c and regions hold device pointers.  dev: the finished rows stay in the frame for the caller (the exact
+// lift and the hit records, swg_cigar.hip) instead of going to req->rows
+int lift_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, const swg_lift_region* regions, uint64_t m, swg_lift_request* req,
+                LiftDeviceRows* dev = nullptr) {
   hipStream_t st = ctx->stream;
   const uint32_t axes = req->axes, set = req->set;
   unsigned long long* scalars = swg_alloc<unsigned long long>(ctx, D_TOTAL);
@@ -318,7 +320,8 @@ int lift_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, con
   req->candidates[0] = ix[0].C;
   req->candidates[1] = ix[1].C;
   if (req->summary) SWG_HIP(ctx, hipMemcpyAsync(req->summary, summary, m * sizeof(swg_lift_summary), hipMemcpyDeviceToHost, st));
-  if (n_rows && req->rows && n_rows <= req->capacity) {
+  const bool fetch = req->rows && n_rows <= req->capacity;
+  if (n_rows && (fetch || (dev && dev->always))) {
     swg_lift_row* rows = swg_alloc<swg_lift_row>(ctx, n_rows);
     uint64_t* other[2] = {nullptr, nullptr};  // other[ax]: the scanned rows per region of axis 1 - ax
     const bool both = h[D_ROWS] && h[D_ROWS + 1];
@@ -337,7 +340,8 @@ int lift_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, con
       SWG_LAUNCH(ctx, "lift_rows", lift_rows_kernel<<<grid_of(ix[ax]), TB, 0, st>>>(J));
       SWG_KERNEL_CHECK(ctx);
     }
-    SWG_HIP(ctx, hipMemcpyAsync(req->rows, rows, n_rows * sizeof(swg_lift_row), hipMemcpyDeviceToHost, st));
+    if (dev) dev->rows = rows;
+    else SWG_HIP(ctx, hipMemcpyAsync(req->rows, rows, n_rows * sizeof(swg_lift_row), hipMemcpyDeviceToHost, st));
   }
   SWG_HIP(ctx, hipStreamSynchronize(st));
   return SWG_OK;
@@ -383,26 +387,24 @@ int swg_lift_ix::swg_lift_index_build(swg_ctx* ctx, uint64_t n, uint32_t n_seq, 
   return SWG_OK;
 }
 
-// the seams' argument checks, then the device work inside an arena frame (also the device half of swg_paf_lift, host/lift_text.cpp)
-int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
-                 swg_lift_request* req) {
-  static_assert(sizeof(swg_lift_row) == 32 && sizeof(swg_lift_region) == 16 && sizeof(swg_lift_summary) == 16, "the ABI's sizes");
-  if (!ctx) return SWG_ERR_INVALID;
-  if (!rec || !req) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: NULL records or request");
-  if (req->set > 1) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: set must be SWG_IV_ALL or SWG_IV_KEPT");
-  if (req->axes == 0 || req->axes >> 2) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: axes names nothing, or a bit beyond the two");
-  if (req->set == SWG_IV_KEPT && !status) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: the KEPT rows need a status column");
+int swg_lift_ix::swg_lift_rows_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, const swg_lift_region* regions, uint64_t m,
+                                      swg_lift_request* req, LiftDeviceRows* dev) {
+  return lift_device(ctx, n, n_seq, c, regions, m, req, dev);
+}
+
+int swg_lift_ix::swg_lift_check_request(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                                        uint32_t set, uint32_t axes) {
+  if (set > 1) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: set must be SWG_IV_ALL or SWG_IV_KEPT");
+  if (axes == 0 || axes >> 2) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: axes names nothing, or a bit beyond the two");
+  if (set == SWG_IV_KEPT && !status) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: the KEPT rows need a status column");
   if (m && !regions) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: NULL regions");
-  const uint64_t n = rec->n;
-  const uint32_t n_seq = rec->n_seq;
-  if (n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift: 2^31 records or more in one call");
+  if (rec->n >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift: 2^31 records or more in one call");
   if (m >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift: 2^31 regions or more in one call");
-  req->n = 0;
-  req->candidates[0] = req->candidates[1] = 0;
-  if (m == 0 || n == 0) {  // no device work
-    if (req->summary && m) std::memset(req->summary, 0, m * sizeof(swg_lift_summary));
-    return SWG_OK;
-  }
+  return SWG_OK;
+}
+
+int swg_lift_ix::swg_lift_check_columns(swg_ctx* ctx, const swg_records* rec, bool on_device, const swg_lift_region* regions, uint64_t m) {
+  const uint32_t n_seq = rec->n_seq;
   if (!rec->q_id || !rec->t_id || !rec->q_start || !rec->q_end || !rec->t_start || !rec->t_end || !rec->strand)
     return swg_set_error(ctx, SWG_ERR_INVALID, "lift: NULL column (q_id, t_id, the four coordinates and strand are read)");
   if (n_seq == 0) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: records without sequences");
@@ -410,6 +412,32 @@ int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uin
     for (uint64_t r = 0; r < m; ++r)
       SWG_TRY(bad_input(ctx, (regions[r].reserved != 0 ? 2u : 0u) | (regions[r].start > regions[r].end ? 4u : 0u) |
                                  (regions[r].seq >= n_seq && regions[r].seq != UNKNOWN_SEQ ? 8u : 0u)));
+  return SWG_OK;
+}
+
+void swg_lift_ix::swg_lift_stage(swg_stager* s, uint64_t n, uint64_t m, LiftCols* c, const swg_lift_region** regions) {
+  for (const uint32_t** col : {&c->id[0], &c->id[1], &c->start[0], &c->start[1], &c->end[0], &c->end[1]}) s->add(col, n);
+  s->add(&c->strand, n);
+  s->add(&c->status, n);
+  s->add(regions, m);
+}
+
+// the seams' argument checks, then the device work inside an arena frame (also the device half of swg_paf_lift, host/lift_text.cpp)
+int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                 swg_lift_request* req) {
+  static_assert(sizeof(swg_lift_row) == 32 && sizeof(swg_lift_region) == 16 && sizeof(swg_lift_summary) == 16, "the ABI's sizes");
+  if (!ctx) return SWG_ERR_INVALID;
+  if (!rec || !req) return swg_set_error(ctx, SWG_ERR_INVALID, "lift: NULL records or request");
+  SWG_TRY(swg_lift_check_request(ctx, rec, status, regions, m, req->set, req->axes));
+  const uint64_t n = rec->n;
+  const uint32_t n_seq = rec->n_seq;
+  req->n = 0;
+  req->candidates[0] = req->candidates[1] = 0;
+  if (m == 0 || n == 0) {  // no device work
+    if (req->summary && m) std::memset(req->summary, 0, m * sizeof(swg_lift_summary));
+    return SWG_OK;
+  }
+  SWG_TRY(swg_lift_check_columns(ctx, rec, on_device, regions, m));
   const int n_axes = __builtin_popcount(req->axes);
   SWG_HIP(ctx, hipSetDevice(ctx->device));
   SWG_TRY(reserve_first(ctx, (size_t)n * (24 * n_axes + (on_device ? 0 : 26)) + (size_t)m * (12 * n_axes + 48) + (size_t(4) << 20)));
@@ -418,10 +446,7 @@ int swg_lift_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uin
     const swg_lift_region* d_regions = regions;
     if (!on_device) {
       swg_stager s(ctx);
-      for (const uint32_t** col : {&c.id[0], &c.id[1], &c.start[0], &c.start[1], &c.end[0], &c.end[1]}) s.add(col, n);
-      s.add(&c.strand, n);
-      s.add(&c.status, n);
-      s.add(&d_regions, m);
+      swg_lift_stage(&s, n, m, &c, &d_regions);
       SWG_TRY(s.run());
     }
     return lift_device(ctx, n, n_seq, c, d_regions, m, req);

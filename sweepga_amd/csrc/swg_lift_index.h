@@ -37,6 +37,24 @@ int swg_lift_limits(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c,
 // lift_keys, the radix sort, lift_gather and the prefix maximum for one axis: 24 bytes of arena per record
 int swg_lift_index_build(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, uint32_t axis, uint64_t max_start, LiftIndex* out);
 
+// The lift's own seams for the calls built on it (the exact lift and the hit records, swg_cigar.hip).
+// The checks of swg_lift_records on the request (set, axes, status, regions, the two ranges) and, once there is device work, on the
+// columns and the host regions: the same errors in the same words.
+int swg_lift_check_request(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m, uint32_t set,
+                           uint32_t axes);
+int swg_lift_check_columns(swg_ctx* ctx, const swg_records* rec, bool on_device, const swg_lift_region* regions, uint64_t m);
+// the host columns of c (strand and status with them) and the regions into the stager, in the order swg_lift_records stages them
+void swg_lift_stage(swg_stager* s, uint64_t n, uint64_t m, LiftCols* c, const swg_lift_region** regions);
+// The whole lift inside the caller's arena frame (c and regions: device pointers): req's n, candidates and summary as
+// swg_lift_records fills them, but the finished rows stay in the frame -- dev->rows, NULL when there are none or they were not
+// written -- and req->rows is only looked at as "rows are wanted" (with req->capacity) unless `always` is set.
+struct LiftDeviceRows {
+  bool always = false;
+  const swg_lift_row* rows = nullptr;
+};
+int swg_lift_rows_device(swg_ctx* ctx, uint64_t n, uint32_t n_seq, const LiftCols& c, const swg_lift_region* regions, uint64_t m,
+                         swg_lift_request* req, LiftDeviceRows* dev);
+
 #ifdef __HIPCC__
 // the first position of a[0 .. n) whose value is >= v (n when none)
 __device__ __forceinline__ uint64_t lower_bound64(const uint64_t* __restrict__ a, uint64_t n, uint64_t v) {

@@ -1,21 +1,25 @@
 """The lift seen from Python: caller-given regions projected through the mappings of a filter call on the device
 (csrc/swg_lift.hip).  lift_records / lift_records_device are the two record seams, Lift.from_paf BED text through an open PafFile.
 lift_closure_records / lift_closure_records_device / LiftClosure.from_paf are the same three for the transitive lift
-(csrc/swg_lift_closure.hip): what each region reaches in up to max_hops hops, as disjoint pieces with the hop that found them."""
+(csrc/swg_lift_closure.hip): what each region reaches in up to max_hops hops, as disjoint pieces with the hop that found them.
+lift_exact_records / lift_exact_records_device / lift_hit_records / lift_hit_records_device / Lift.from_paf(exact=True) are the
+base-exact lift (csrc/swg_cigar.hip): the rows refined through the CIGARs of the records that are hit."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import SwgClosureRequest, SwgLiftRequest, default_context, load
+from ._lib import SwgCigarSet, SwgClosureRequest, SwgLiftExactRequest, SwgLiftRequest, default_context, load
 from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
 REGION_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32)])
 ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "record", "src_start", "src_end", "dst_seq", "dst_start", "dst_end", "flags")])
+EXACT_ROW_DTYPE = np.dtype(ROW_DTYPE.descr + [("aligned", np.uint32), ("matches", np.uint32)])
 UNKNOWN = 2**32 - 1
 SET_ALL, SET_KEPT = 0, 1
 AXIS_QUERY, AXIS_TARGET, AXIS_BOTH = 1, 2, 3
-MINUS, ON_TARGET = 1, 2
+MINUS, ON_TARGET, EXACT = 1, 2, 4
+CIGAR_SYNTAX, CIGAR_VALUE, CIGAR_QUERY_SUM, CIGAR_TARGET_SUM, CIGAR_EMPTY = 1, 2, 4, 8, 16
 CLOSURE_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")])
 CLOSURE_SUMMARY_DTYPE = np.dtype([("bases", np.uint64), ("pieces", np.uint32), ("sequences", np.uint32), ("hops", np.uint32), ("flags", np.uint32)])
 CLOSURE_CUT = 1
@@ -104,6 +108,113 @@ def lift_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=
                  int(n_regions), SETS.get(set, set), AXES.get(axes, axes), capacity)
 
 
+class LiftExactResult(LiftResult):
+    """A LiftResult whose rows are an EXACT_ROW_DTYPE array; state: a uint8 per entry of the CIGAR set (0 = usable); ops, cigar_bad
+    and exact_rows as the request returns them."""
+
+    def __init__(self, rows, n, summary, candidates, state, ops, cigar_bad, exact_rows):
+        super().__init__(rows, n, summary, candidates)
+        self.state, self.ops, self.cigar_bad, self.exact_rows = state, ops, cigar_bad, exact_rows
+
+
+def cigar_set(records, cigars):
+    """(record, offset, text) as the numpy arrays of a swg_cigar_set from ascending record indices and one CIGAR (str or bytes)
+    per record."""
+    texts = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in cigars]
+    record = np.ascontiguousarray(records, dtype=np.uint32)
+    if len(texts) != record.size:
+        raise ValueError("one CIGAR per record is needed")
+    offset = np.zeros(record.size + 1, dtype=np.uint64)
+    np.cumsum([len(t) for t in texts], out=offset[1:])
+    text = np.frombuffer(b"".join(texts) or b"\0", dtype=np.uint8)
+    return record, offset, text
+
+
+def _exact_call(ctx, fn, rec, status_addr, regions_addr, m, cigars, k, set_, axes, capacity):
+    """cigars: (record address, offset address, text address) or None; capacity as in _call."""
+    req = SwgLiftExactRequest()
+    req.set, req.axes = int(set_), int(axes)
+    summary = np.zeros((m, 2, 2), dtype=np.uint32)
+    req.summary = summary.ctypes.data if m else None
+    state = np.zeros(int(k), dtype=np.uint8)
+    req.state = state.ctypes.data if k else None
+    cs = None
+    if cigars is not None:
+        cs = SwgCigarSet()
+        cs.record, cs.offset, cs.text, cs.k = cigars[0], cigars[1], cigars[2], int(k)
+    call = lambda: ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(cs) if cs is not None else None, C.byref(req)))   # noqa: E731
+    rows = None
+    if capacity is not None:
+        rows = np.zeros(int(capacity), dtype=EXACT_ROW_DTYPE)
+        req.capacity, req.rows = int(capacity), rows.ctypes.data if capacity else None
+    call()
+    if capacity is None:
+        rows = np.zeros(int(req.n), dtype=EXACT_ROW_DTYPE)
+        if req.n:
+            req.capacity, req.rows = int(req.n), rows.ctypes.data
+            call()
+    elif req.n > capacity:
+        rows = None
+    else:
+        rows = rows[:int(req.n)]
+    return LiftExactResult(rows, int(req.n), summary, (int(req.candidates[0]), int(req.candidates[1])), state, int(req.ops), int(req.cigar_bad),
+                           int(req.exact_rows))
+
+
+def lift_exact_records(ctx, records, strand, n_seq, regions, cigar_records, cigars, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_exact_records: the arguments of lift_records, plus the CIGAR set -- ascending record indices and one CIGAR text per
+    record (empty: the record has none), or the (record, offset, text) arrays of cigar_set() as `cigars` with cigar_records None.
+    Returns a LiftExactResult."""
+    regs = regions_array(regions)
+    rec, keep = _host_records(records, strand, n_seq)
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    record, offset, text = cigars if cigar_records is None else cigar_set(cigar_records, cigars)
+    k = int(record.size)
+    return _exact_call(ctx, ctx.lib.swg_lift_exact_records, rec, addr(st), regs.ctypes.data if regs.size else None, regs.size,
+                       (record.ctypes.data, offset.ctypes.data, text.ctypes.data) if k else None, k, SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+def lift_exact_records_device(ctx, columns, strand, n_seq, regions, n_regions, cigar_record, cigar_offset, cigar_text, k, status=None, set="all",
+                              axes="both", capacity=None):
+    """swg_lift_exact_records_device: the arguments of lift_records_device, plus the three arrays of the set as device tensors
+    (uint32 [k], uint64 [k + 1], bytes) and k.  Rows, summary and state come back as numpy arrays on the host."""
+    rec = _device_records(columns, strand, n_seq, regions, n_regions, status)
+    k = int(k)
+    if k and (int(cigar_record.numel()) * cigar_record.element_size() < 4 * k or int(cigar_offset.numel()) * cigar_offset.element_size() < 8 * (k + 1)):
+        raise ValueError("the CIGAR set's record or offset tensor is shorter than k asks for")
+    cig = (int(cigar_record.data_ptr()), int(cigar_offset.data_ptr()), int(cigar_text.data_ptr())) if k else None
+    return _exact_call(ctx, ctx.lib.swg_lift_exact_records_device, rec, int(status.data_ptr()) if status is not None else None,
+                       int(regions.data_ptr()), int(n_regions), cig, k, SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
+def _hit_call(ctx, fn, rec, status_addr, regions_addr, m, set_, axes, capacity):
+    k = C.c_uint64(0)
+    out = np.zeros(int(capacity) if capacity is not None else 0, dtype=np.uint32)
+    call = lambda: ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, int(set_), int(axes), out.ctypes.data if out.size else None,   # noqa: E731
+                                out.size, C.byref(k)))
+    call()
+    if capacity is None and k.value:
+        out = np.zeros(int(k.value), dtype=np.uint32)
+        call()
+    return (out[:int(k.value)] if k.value <= out.size else None), int(k.value)
+
+
+def lift_hit_records(ctx, records, strand, n_seq, regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_hit_records: the distinct records with a hit, ascending -> (uint32 array, or None when `capacity` did not hold them; k)."""
+    regs = regions_array(regions)
+    rec, keep = _host_records(records, strand, n_seq)
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    return _hit_call(ctx, ctx.lib.swg_lift_hit_records, rec, addr(st), regs.ctypes.data if regs.size else None, regs.size, SETS.get(set, set),
+                     AXES.get(axes, axes), capacity)
+
+
+def lift_hit_records_device(ctx, columns, strand, n_seq, regions, n_regions, status=None, set="all", axes="both", capacity=None):
+    """swg_lift_hit_records_device over the tensors of lift_records_device; the list comes back as a numpy array on the host."""
+    rec = _device_records(columns, strand, n_seq, regions, n_regions, status)
+    return _hit_call(ctx, ctx.lib.swg_lift_hit_records_device, rec, int(status.data_ptr()) if status is not None else None, int(regions.data_ptr()),
+                     int(n_regions), SETS.get(set, set), AXES.get(axes, axes), capacity)
+
+
 class LiftClosureResult:
     """rows: a CLOSURE_ROW_DTYPE array in (region, seq, start) order, or None when the capacity given did not hold them; n: their
     number; summary: a CLOSURE_SUMMARY_DTYPE array per region; hops_run, projections (summed over the hops) and candidates (query
@@ -165,17 +276,33 @@ def parse_rows(text):
     return out
 
 
+def parse_exact_rows(text):
+    """The rows text of an exact lift: parse_rows' fields, then aligned, matches and mode ("exact" / "interp")."""
+    dt = np.dtype([("dst_name", object), ("dst_start", np.uint32), ("dst_end", np.uint32), ("label", object), ("src_name", object),
+                   ("src_start", np.uint32), ("src_end", np.uint32), ("strand", "U1"), ("axis", "U1"), ("record", np.uint32),
+                   ("aligned", np.uint32), ("matches", np.uint32), ("mode", "U6")])
+    lines = [ln.split("\t") for ln in text.split("\n") if ln]
+    out = np.zeros(len(lines), dtype=dt)
+    for k, f in enumerate(lines):
+        out[k] = (f[0], int(f[1]), int(f[2]), f[3], f[4], int(f[5]), int(f[6]), f[7], f[8], int(f[9]), int(f[10]), int(f[11]), f[12])
+    return out
+
+
 class Lift:
     """BED regions lifted through an open PafFile: `text` (one line per row: dst_name dst_start dst_end label src_name src_start
     src_end strand axis record) and `summary_text` (label sequence start end all_q all_t kept_q kept_t state per region); `rows` and
-    `summary` are the same parsed into structured numpy arrays.  None where not asked for."""
+    `summary` are the same parsed into structured numpy arrays.  None where not asked for.  An exact lift (from_paf(exact=True)) has
+    three more columns per row -- aligned matches mode -- and `exact_counts`: (records hit, entries of state 0, bad entries, records
+    without a cg:Z: tag)."""
 
-    def __init__(self, text, summary_text):
-        self.text, self.summary_text = text, summary_text
+    def __init__(self, text, summary_text, exact_counts=None):
+        self.text, self.summary_text, self.exact_counts = text, summary_text, exact_counts
 
     @property
     def rows(self):
-        return parse_rows(self.text) if self.text is not None else None
+        if self.text is None:
+            return None
+        return parse_exact_rows(self.text) if self.exact_counts is not None else parse_rows(self.text)
 
     @property
     def summary(self):
@@ -190,9 +317,10 @@ class Lift:
         return out
 
     @classmethod
-    def from_paf(cls, paf, status, bed_text, set="kept", axes="both", ctx=None, rows=True, summary=True):
+    def from_paf(cls, paf, status, bed_text, set="kept", axes="both", ctx=None, rows=True, summary=True, exact=False):
         """swg_paf_lift: both texts from one device call.  status None: set must be "all".  ctx: a Context, anything with a `.ctx`
-        (PafFilter), or None = the default context, which is only opened when there are records and regions."""
+        (PafFilter), or None = the default context, which is only opened when there are records and regions.  exact: swg_paf_lift_exact,
+        the rows through the cg:Z: tags of the lines that are hit."""
         ctx = getattr(ctx, "ctx", ctx)
         lib = load()
         bed = bed_text.encode("utf-8", errors="surrogateescape") if isinstance(bed_text, str) else bytes(bed_text)
@@ -201,11 +329,16 @@ class Lift:
             ctx = default_context()
         st = host_column(status, np.uint8, paf.n, "status", optional=True)
         p, n = text_slots((rows, summary))
-        rc = lib.swg_paf_lift(ctx.handle if ctx is not None else None, paf.handle, addr(st), bed, len(bed), SETS.get(set, set),
-                              AXES.get(axes, axes), p, n)
+        fn = lib.swg_paf_lift_exact if exact else lib.swg_paf_lift
+        rc = fn(ctx.handle if ctx is not None else None, paf.handle, addr(st), bed, len(bed), SETS.get(set, set), AXES.get(axes, axes), p, n)
         raise_alnstats(lib, rc)
         text = [t.decode("utf-8", errors="surrogateescape") if t is not None else None for t in take_texts(lib, p, n, (rows, summary))]
-        return cls(text[0], text[1])
+        counts = None
+        if exact:
+            c4 = (C.c_uint64 * 4)()
+            lib.swg_paf_lift_exact_counts(c4)
+            counts = tuple(int(x) for x in c4)
+        return cls(text[0], text[1], counts)
 
 
 class LiftClosure:
