@@ -1060,6 +1060,96 @@ int swg_paf_lift_exact(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, co
  * a tag. */
 void swg_paf_lift_exact_counts(uint64_t out[4]);
 
+/* ---- UCSC chain files: one chain per record from its CIGAR, built and formatted on the device --------------
+ * The CIGAR set, the walk and the entry states 1 .. 16 are those of the base-exact lift above.  One more state bit, 32 = BEYOND:
+ * q_end > seq_len[q_id] or t_end > seq_len[t_id].  An entry gives a chain when its state is 0 and its record is in `set`
+ * (SWG_IV_ALL, or SWG_IV_KEPT: status != 0).
+ * An op ADVANCES when it adds to x or y and is ALIGNED when it makes columns (M, =, X of non-zero length).  An aligned op is a BLOCK
+ * START when the nearest earlier advancing op of its entry is not aligned, or there is none: zero-length ops and S, H, P neither
+ * start nor separate blocks, runs of M, = and X merge, runs of I, D and N are one gap.  With the block starts s_0 < ... < s_{B-1},
+ * e the entry's end and X, Y, A, E the exclusive prefix sums of x, y, columns and '=' columns over the ops:
+ *   size_j = A[next] - A[s_j]  (next = s_{j+1}, or e for the last block);  for j < B - 1  dq_j = X[s_{j+1}] - X[s_j] - size_j and
+ *   dt_j = Y[s_{j+1}] - Y[s_j] - size_j;  the last block has dt = dq = 0.  Leading and trailing gaps are cut off:
+ *   x0 = X[s_0] - X[first], x1 = X[s_{B-1}] - X[first] + size_{B-1}, y0 and y1 alike on Y.
+ * from = SWG_UCSC_FROM_TARGET (the PAF's target is the chain's reference sequence, as liftOver expects):
+ *   ref = [t_start + y0, t_start + y1);  other = [q_start + x0, q_start + x1) on '+', and in UCSC's reverse-complement coordinates
+ *   [seq_len[q] - q_end + x0, seq_len[q] - q_end + x1) on '-';  blocks in text order, (size, dt, dq).
+ * from = SWG_UCSC_FROM_QUERY: on '+' the two sides and dt, dq change places; on '-' ref = [q_end - x1, q_end - x0), other =
+ *   [seq_len[t] - t_start - y1, seq_len[t] - t_start - y0) on '-', and the blocks are reversed: block j' has size_{B-1-j'} and, for
+ *   j' < B - 1, dt' = dq_{B-2-j'}, dq' = dt_{B-2-j'}.
+ * score = the entry's '=' columns when it has any, else its aligned columns.  B == 0 (no aligned column): no chain (empty_chains).
+ * Rows: one swg_ucsc_chain per ENTRY in set order (n_blocks == 0: no chain); its blocks are blocks[first_block .. + n_blocks), its
+ * block lines text[text_first ..): `size\tdt\tdq\n` per block but the last, `size\n\n` for the last.  n_blocks, text_bytes and
+ * first_block / text_first run over the emitted chains in set order.
+ * Capacity protocol: chains is written when k <= chain_capacity, blocks when n_blocks <= block_capacity, text when text_bytes <=
+ * text_capacity (each only when non-NULL); state whenever non-NULL; the counts whenever the call succeeds.  Refusals of the set as in
+ * swg_lift_exact_records; a NULL seq_len, set or from out of range, SWG_IV_KEPT without status: SWG_ERR_INVALID; 2^32 text bytes
+ * or more in one call, 2^31 blocks or more: SWG_ERR_RANGE.  k == 0 needs no device work.  Scratch from the arena (SWG_ERR_OOM under a
+ * limit that does not hold it): the build's (see swg_lift_exact_records) plus, per op, 1 byte (flag) and 16 bytes per tile of 1,024;
+ * per block 4 + 12 + 8 bytes and its text; per entry 48 bytes; the host seam stages 26 bytes per record and 4 per sequence. */
+#define SWG_CIGAR_BEYOND 32u
+#define SWG_UCSC_FROM_TARGET 0u
+#define SWG_UCSC_FROM_QUERY 1u
+#define SWG_UCSC_MINUS 1u /* swg_ucsc_chain.flags bit 0: the other side's strand is '-'; bits 8 .. 15: the entry's state */
+typedef struct swg_ucsc_block {
+  uint32_t size, dt, dq;
+} swg_ucsc_block; /* 12 bytes */
+typedef struct swg_ucsc_chain {
+  uint32_t record, flags;
+  uint32_t ref_start, ref_end; /* on the reference side, '+' */
+  uint32_t oth_start, oth_end; /* on the other side, in that side's strand coordinates */
+  uint32_t score, n_blocks;    /* n_blocks == 0: the entry gives no chain, every other field but record and flags is 0 */
+  uint64_t first_block;        /* into blocks */
+  uint64_t text_first;         /* into text */
+} swg_ucsc_chain; /* 48 bytes */
+typedef struct swg_ucsc_request {
+  uint32_t set, from;          /* in */
+  uint64_t chain_capacity;     /* in: entries `chains` can hold */
+  swg_ucsc_chain* chains;      /* in: caller-owned or NULL; written only when k <= chain_capacity */
+  uint64_t block_capacity;
+  swg_ucsc_block* blocks;      /* written only when n_blocks <= block_capacity */
+  uint64_t text_capacity;
+  char* text;                  /* written only when text_bytes <= text_capacity */
+  uint8_t* state;              /* in: caller-owned [k] or NULL; written whenever non-NULL */
+  uint64_t n_chains;           /* out: entries that give a chain */
+  uint64_t n_blocks;           /* out */
+  uint64_t text_bytes;         /* out */
+  uint64_t ops;                /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;          /* out: entries with a state bit of 1 .. 8 */
+  uint64_t beyond;             /* out: entries with state bit 32 */
+  uint64_t empty_chains;       /* out: entries of the set with state 0 and no aligned column */
+} swg_ucsc_request; /* 120 bytes */
+/* Everything on the host.  seq_len: [rec->n_seq]. */
+int swg_ucsc_chain_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint8_t* status, const swg_cigar_set* cigars,
+                           swg_ucsc_request* req);
+/* Columns, strand, seq_len, status and the three arrays of the set in device memory of ctx's GPU; the set structure, the request
+ * and its arrays on the host. */
+int swg_ucsc_chain_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint8_t* status, const swg_cigar_set* cigars,
+                                  swg_ucsc_request* req);
+typedef struct swg_ucsc_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t chains;   /* chains written */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t beyond;   /* records that end beyond their sequence */
+  uint64_t untagged; /* records without a cg:Z: tag */
+  uint64_t empty;    /* entries without an aligned column */
+  uint64_t blocks;
+  uint64_t batches;  /* device calls */
+} swg_ucsc_counts; /* 64 bytes */
+/* The chain file of an open PAF: one chain per record of `set` whose line's LAST cg:Z: tag parses and fits (a line without the tag
+ * is an empty entry), in record order, ids from 1.  Header `chain score tName tSize tStrand tStart tEnd qName qSize qStrand qStart
+ * qEnd id` (names from the handle, sizes = the length on the line that mentions the sequence last), then the block lines.  The
+ * records go to the device in batches of consecutive records whose CIGAR text stays within batch_bytes (0: a default from the
+ * context's memory limit or the free device memory, below 2^32; a record larger than the batch is a batch of its own; one CIGAR of
+ * 2^32 bytes or more is SWG_ERR_RANGE); the output is the same bytes for every batch_bytes.  counts may be NULL.  A PAF without
+ * records of the set gives an empty file and needs no device (ctx may be NULL).  A handle whose columns are rebased:
+ * SWG_ERR_UNSUPPORTED.  Errors: swg_alnstats_last_error(). */
+int swg_paf_ucsc_chain_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t from, const char* out_path,
+                             uint64_t batch_bytes, swg_ucsc_counts* counts);
+/* The same as one malloc'd text (release with swg_free), for small inputs. */
+int swg_paf_ucsc_chain_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t from, uint64_t batch_bytes,
+                            swg_ucsc_counts* counts, char** text, uint64_t* len);
+
 /* ---- transitive lift: the closure of each region under the lift, hop by hop, on the device -----------------
  * Per region, independently of every other region (all sets are point sets per sequence, all arithmetic is in integers):
  *   hop 0      F_0 = V_0 = { [start, end) on seq } when seq is known and start < end, else both empty

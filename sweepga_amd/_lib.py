@@ -45,6 +45,7 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
            "swg_lift_exact_records", "swg_lift_exact_records_device", "swg_lift_hit_records", "swg_lift_hit_records_device",
            "swg_paf_lift_exact", "swg_paf_lift_exact_counts",
+           "swg_ucsc_chain_records", "swg_ucsc_chain_records_device", "swg_paf_ucsc_chain_write", "swg_paf_ucsc_chain_text",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
@@ -308,6 +309,25 @@ class SwgLiftExactRequest(C.Structure):
     _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
                 ("rows", C.c_void_p), ("summary", C.c_void_p), ("state", C.c_void_p), ("ops", C.c_uint64), ("cigar_bad", C.c_uint64),
                 ("exact_rows", C.c_uint64)]
+
+
+class SwgUcscBlock(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("size", "dt", "dq")]
+
+
+class SwgUcscChain(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("record", "flags", "ref_start", "ref_end", "oth_start", "oth_end", "score", "n_blocks")]
+    _fields_ += [("first_block", C.c_uint64), ("text_first", C.c_uint64)]
+
+
+class SwgUcscRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("from_", C.c_uint32), ("chain_capacity", C.c_uint64), ("chains", C.c_void_p), ("block_capacity", C.c_uint64),
+                ("blocks", C.c_void_p), ("text_capacity", C.c_uint64), ("text", C.c_void_p), ("state", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in ("n_chains", "n_blocks", "text_bytes", "ops", "cigar_bad", "beyond", "empty_chains")]
+
+
+class SwgUcscCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "chains", "bad", "beyond", "untagged", "empty", "blocks", "batches")]
 
 
 class SwgClosureRow(C.Structure):
@@ -579,6 +599,15 @@ def load():
     lib.swg_paf_lift_exact.argtypes = lib.swg_paf_lift.argtypes
     lib.swg_paf_lift_exact_counts.restype = None
     lib.swg_paf_lift_exact_counts.argtypes = [C.POINTER(C.c_uint64)]
+    for name in ("swg_ucsc_chain_records", "swg_ucsc_chain_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.POINTER(SwgCigarSet), C.POINTER(SwgUcscRequest)]
+    lib.swg_paf_ucsc_chain_write.restype = C.c_int
+    lib.swg_paf_ucsc_chain_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(SwgUcscCounts)]
+    lib.swg_paf_ucsc_chain_text.restype = C.c_int
+    lib.swg_paf_ucsc_chain_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SwgUcscCounts),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_lift_closure_records", "swg_lift_closure_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

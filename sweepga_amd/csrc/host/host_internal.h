@@ -3,6 +3,7 @@
 #define SWG_HOST_INTERNAL_H
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -128,6 +129,30 @@ const char* swg_cigar_tag_find(const char* line, uint64_t len, uint64_t* value_l
 void swg_lift_exact_row_text(std::string& o, const char* dst_name, const std::string& label, const std::string& src_name, const swg_lift_exact_row& w);
 // the handle's text and each record's line in it
 void swg_paf_lines_view(const swg_paf* p, const char** text, const uint64_t** rec_off, const uint32_t** rec_len);
+// ---- UCSC chain files (swg_ucsc.hip: kernels and record seams; ucsc_text.cpp: the two PAF seams) ----
+int swg_ucsc_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_len, const uint8_t* status, const swg_cigar_set* cigars,
+                 swg_ucsc_request* req);
+// bytes of CIGAR text per batch when the caller names none: from the memory limit or the free device memory, below 2^32
+uint64_t swg_ucsc_default_batch(swg_ctx* ctx);
+// `chain score tName tSize + tStart tEnd qName qSize qStrand qStart qEnd id\n` of one row
+void swg_ucsc_header_text(std::string& o, const swg_ucsc_chain& ch, const char* ref_name, uint64_t ref_size, const char* oth_name, uint64_t oth_size,
+                          uint64_t id);
+// first[b] .. first[b + 1]: the entries of batch b -- consecutive entries whose lengths add up to at most batch_bytes, an entry longer
+// than that alone; batch_bytes 0: no bound but the call's (fewer than 2^32 bytes).  k == 0: no batch (first = {0}).
+void swg_ucsc_plan_batches(const uint64_t* len, uint64_t k, uint64_t batch_bytes, std::vector<uint64_t>* first);
+// where the chain file goes: a stream, or a text
+struct swg_ucsc_sink {
+  std::FILE* file = nullptr;
+  std::string* text = nullptr;
+  bool failed = false;
+  void put(const char* b, size_t n) {
+    if (!n) return;
+    if (text) text->append(b, n);
+    else if (std::fwrite(b, 1, n, file) != n) failed = true;
+  }
+};
+// one batch into the sink: for every row with blocks its header (hdr[j]) and its block lines out of the device's text
+void swg_ucsc_splice(swg_ucsc_sink* sink, const swg_ucsc_chain* rows, uint64_t k, const std::string* hdr, const char* text, uint64_t text_bytes);
 // ---- transitive lift (swg_lift_closure.hip): swg_lift_run's arguments ----
 int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                          swg_closure_request* req);

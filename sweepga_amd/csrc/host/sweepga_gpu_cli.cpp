@@ -405,6 +405,18 @@ void write_lift(const std::string& rows_path, const std::string& summary_path, s
   write_texts(paths, text, len, 2);
 }
 
+// --ucsc-chain: the liftOver chain file of swg_paf_ucsc_chain_write, one chain per record of the set from its cg:Z: CIGAR (blocks and
+// their lines built on the device); what it met goes to standard error in one line.
+void write_ucsc_chain(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set, uint32_t from, uint64_t batch,
+                      bool quiet) {
+  swg_ucsc_counts c;
+  if (swg_paf_ucsc_chain_write(ctx, paf, status, set, from, path.c_str(), batch, &c) != SWG_OK) die(3, std::string("--ucsc-chain: ") + swg_alnstats_last_error());
+  if (!quiet)
+    std::fprintf(stderr, "[sweepga-gpu] --ucsc-chain: %llu chains of %llu records, %llu blocks, %llu bad, %llu beyond, %llu without a cg:Z: tag, "
+                 "%llu without an aligned column\n", (unsigned long long)c.chains, (unsigned long long)c.records, (unsigned long long)c.blocks,
+                 (unsigned long long)c.bad, (unsigned long long)c.beyond, (unsigned long long)c.untagged, (unsigned long long)c.empty);
+}
+
 // --lift-closure / --lift-closure-summary: the two texts of swg_paf_lift_closure (the regions walked through the mappings for up to
 // `hops` hops), both from one walk.  "-" = standard error.
 void write_lift_closure(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
@@ -482,6 +494,10 @@ int main(int argc, char** argv) {
   uint32_t lift_set = SWG_IV_KEPT, lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
   bool lift_flag = false;  // (--lift-set or --lift-axis was given)
   bool lift_exact = false;  // --lift-exact: the rows of --lift through the CIGARs
+  std::string ucsc_path;    // --ucsc-chain: empty = no file
+  uint32_t ucsc_from = SWG_UCSC_FROM_TARGET, ucsc_set = SWG_IV_KEPT;
+  uint64_t ucsc_batch = 0;  // --ucsc-chain-batch: 0 = the library's default
+  bool ucsc_flag = false;   // (one of --ucsc-chain-from / --ucsc-chain-set / --ucsc-chain-batch was given)
   std::string closure_path, closure_summary_path;  // --lift-closure, --lift-closure-summary: empty = not given
   uint64_t lift_hops = 0, lift_min_length = 100;   // --lift-hops (0 = not given), --lift-min-length
   bool lift_min_length_flag = false;
@@ -579,6 +595,29 @@ int main(int argc, char** argv) {
     else if (a == "--lift") { lift_path = value(); if (lift_path.empty()) die(2, "empty value for --lift"); }
     else if (a == "--lift-summary") { lift_summary_path = value(); if (lift_summary_path.empty()) die(2, "empty value for --lift-summary"); }
     else if (a == "--lift-exact") lift_exact = true;
+    else if (a == "--ucsc-chain") {
+      ucsc_path = value();
+      if (ucsc_path.empty()) die(2, "empty value for --ucsc-chain");
+      if (ucsc_path == "-") die(2, "--ucsc-chain needs a file: a chain file is not a standard error report");
+    }
+    else if (a == "--ucsc-chain-from") {
+      const std::string v = value();
+      if (v == "target") ucsc_from = SWG_UCSC_FROM_TARGET;
+      else if (v == "query") ucsc_from = SWG_UCSC_FROM_QUERY;
+      else die(2, "invalid value for --ucsc-chain-from: target or query");
+      ucsc_flag = true;
+    }
+    else if (a == "--ucsc-chain-set") {
+      const std::string v = value();
+      if (v == "kept") ucsc_set = SWG_IV_KEPT;
+      else if (v == "all") ucsc_set = SWG_IV_ALL;
+      else die(2, "invalid value for --ucsc-chain-set: kept or all");
+      ucsc_flag = true;
+    }
+    else if (a == "--ucsc-chain-batch") {
+      if (!parse_metric_number(value(), &ucsc_batch) || ucsc_batch == 0) die(2, "invalid value for --ucsc-chain-batch: 1 or more bytes");
+      ucsc_flag = true;
+    }
     else if (a == "--lift-hops") { if (!parse_u64(value(), &lift_hops) || lift_hops < 1 || lift_hops > 65535) die(2, "invalid value for --lift-hops: 1 .. 65535"); }
     else if (a == "--lift-closure") { closure_path = value(); if (closure_path.empty()) die(2, "empty value for --lift-closure"); }
     else if (a == "--lift-closure-summary") { closure_summary_path = value(); if (closure_summary_path.empty()) die(2, "empty value for --lift-closure-summary"); }
@@ -694,6 +733,7 @@ int main(int argc, char** argv) {
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
                 "         [--lift-exact]\n"
+                "         [--ucsc-chain FILE] [--ucsc-chain-from target|query] [--ucsc-chain-set kept|all] [--ucsc-chain-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
@@ -781,6 +821,11 @@ int main(int argc, char** argv) {
                 "  --lift-exact        project the rows of --lift base by base through the cg:Z: CIGARs of the lines that are hit (parsed on\n"
                 "                      the device): three more columns `aligned matches mode`, mode exact | interp (no usable CIGAR on the\n"
                 "                      line: the interpolated row); needs --lift-regions and --lift; one line of counts on standard error\n"
+                "  --ucsc-chain FILE   write a UCSC chain file (liftOver, CrossMap, bcftools +liftover): one chain per record from its cg:Z:\n"
+                "                      CIGAR, blocks and block lines built on the device; one line of counts on standard error\n"
+                "  --ucsc-chain-from target|query  which side is the chain's reference sequence (default target, as liftOver expects)\n"
+                "  --ucsc-chain-set kept|all       the records that give chains (default kept)\n"
+                "  --ucsc-chain-batch BYTES        CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
                 "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
@@ -822,6 +867,8 @@ int main(int argc, char** argv) {
   if (!lift_hops && (!closure_path.empty() || !closure_summary_path.empty() || lift_min_length_flag))
     die(2, "--lift-closure, --lift-closure-summary and --lift-min-length need --lift-hops");
   if (lift_exact && (!lift || lift_path.empty())) die(2, "--lift-exact needs --lift-regions and --lift");
+  if (ucsc_path.empty() && ucsc_flag) die(2, "--ucsc-chain-from, --ucsc-chain-set and --ucsc-chain-batch need --ucsc-chain");
+  const bool ucsc = !ucsc_path.empty();
   if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
   if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
   if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
@@ -913,7 +960,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1091,6 +1138,12 @@ int main(int argc, char** argv) {
         write_lift_closure(closure_path, closure_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes,
                            (uint32_t)lift_hops, (uint32_t)lift_min_length);
     }
+    if (ucsc) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_ucsc_chain(ucsc_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), ucsc_set, ucsc_from, ucsc_batch, quiet);
+    }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
     return 0;
@@ -1263,6 +1316,12 @@ int main(int argc, char** argv) {
                          (uint32_t)lift_min_length);
       if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift-hops: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tc).count());
     }
+  }
+  // ---- --ucsc-chain: on the first context, the records in batches of bounded CIGAR text
+  if (ucsc) {
+    const auto tb = clk::now();
+    write_ucsc_chain(ucsc_path, ctx, paf, status.data(), ucsc_set, ucsc_from, ucsc_batch, quiet);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --ucsc-chain: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

@@ -32,6 +32,7 @@
 #include "swg_lift_index.h"
 #include "swg_pair_table.h"
 #include "swg_cigar_walk.h"
+#include "swg_cigar_build.h"
 #include "host/host_internal.h"
 
 namespace {
@@ -42,8 +43,8 @@ using namespace swg_cigar;
 
 constexpr int CT = TB * 16;  // text bytes per tile
 static_assert(TB == 256 && WAVES == 4, "16 bytes per thread, four wavefronts");
-// device scalars of a call
-enum { C_BAD = 0, C_BYTES = 1, C_BAD_ENTRIES = 2, C_EXACT = 3, C_HITS = 4, C_TOTAL = 5 };
+// device scalars of a call, behind those of the build
+enum { C_EXACT = C_BUILD_TOTAL, C_HITS, C_TOTAL };
 
 // the thread's 16 bytes from position i on; bytes at or behind B read as '0' (a digit: never an op)
 __device__ __forceinline__ void load_text16(const char* __restrict__ text, uint64_t i, uint64_t B, bool aligned, uint32_t w[4]) {
@@ -176,25 +177,6 @@ __global__ __launch_bounds__(TB) void cigar_parse_kernel(CigarParse P) {
   }
 }
 
-struct CigarSet {  // device pointers
-  uint64_t k, B, ops;
-  const uint32_t* record;
-  const uint64_t* offset;
-  const char* text;
-  const uint32_t* chunk_rank;
-  uint32_t* op_first;  // [k + 1]
-  uint32_t* state;     // the state bytes, four to a word
-  Prefix P;
-};
-
-// the ops in front of text byte p
-__device__ __forceinline__ uint32_t rank_at(const CigarSet& S, uint64_t p) {
-  if (p >= S.B) return (uint32_t)S.ops;
-  uint32_t r = S.chunk_rank[p >> 4];
-  for (uint64_t q = p & ~uint64_t(15); q < p; ++q) r += is_digit((unsigned char)S.text[q]) ? 0u : 1u;
-  return r;
-}
-
 __global__ __launch_bounds__(TB) void cigar_entries_kernel(CigarSet S, LiftCols c, unsigned long long* __restrict__ scalars) {
   const uint64_t j = (uint64_t)blockIdx.x * TB + threadIdx.x;
   bool bad = false;
@@ -261,17 +243,50 @@ __global__ __launch_bounds__(TB) void hit_mark_kernel(uint64_t n_rows, const swg
   if (i < n_rows) flags[rows[i].record] = 1;
 }
 
-int bad_set(swg_ctx* ctx, uint64_t bad) {
-  if (bad & 1u) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: a record of the CIGAR set is >= n");
-  if (bad & 2u) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: the records of the CIGAR set are not strictly ascending");
-  if (bad & 4u) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: the offsets of the CIGAR set do not start at 0 or decrease");
+int bad_set(swg_ctx* ctx, const char* who, uint64_t bad) {
+  if (bad & 1u) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: a record of the CIGAR set is >= n", who);
+  if (bad & 2u) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: the records of the CIGAR set are not strictly ascending", who);
+  if (bad & 4u) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: the offsets of the CIGAR set do not start at 0 or decrease", who);
   return SWG_OK;
 }
 
 unsigned grid_of(uint64_t items) { return (unsigned)((items + TB - 1) / TB); }
 
+}  // namespace
+
+namespace swg_cigar {
+
+int cigar_set_check_host(swg_ctx* ctx, const char* who, const swg_cigar_set* cigars, bool on_device, uint64_t n, uint64_t* B) {
+  const uint64_t k = cigars ? cigars->k : 0;
+  *B = 0;
+  if (k >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "%s: 2^31 entries or more in one call", who);
+  if (k && (!cigars->record || !cigars->offset)) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: NULL record or offset array of the CIGAR set", who);
+  if (k && n == 0) return bad_set(ctx, who, 1);  // (any record is >= n)
+  if (k && !on_device) {  // the set is here: its faults cost no device work
+    uint64_t bad = cigars->offset[0] != 0 ? 4u : 0u;
+    for (uint64_t j = 0; j < k; ++j)
+      bad |= (cigars->record[j] >= n ? 1u : 0u) | (j && cigars->record[j - 1] >= cigars->record[j] ? 2u : 0u) |
+             (cigars->offset[j + 1] < cigars->offset[j] ? 4u : 0u);
+    SWG_TRY(bad_set(ctx, who, bad));
+    *B = cigars->offset[k];
+    if (*B && !cigars->text) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: NULL text of the CIGAR set", who);
+  }
+  return SWG_OK;
+}
+
+int cigar_set_check_device(swg_ctx* ctx, const char* who, uint64_t n, CigarSet* S, unsigned long long* scalars) {
+  uint64_t h[2];
+  SWG_LAUNCH(ctx, "cigar_set_check", cigar_set_check_kernel<<<grid_of(S->k), TB, 0, ctx->stream>>>(S->k, n, S->record, S->offset, scalars));
+  SWG_KERNEL_CHECK(ctx);
+  SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, 2));
+  SWG_TRY(bad_set(ctx, who, h[C_BAD]));
+  S->B = h[C_BYTES];
+  if (S->B && !S->text) return swg_set_error(ctx, SWG_ERR_INVALID, "%s: NULL text of the CIGAR set", who);
+  return SWG_OK;
+}
+
 // Parse, prefix sums and entry states of a set whose arrays are in device memory (inside an arena frame).  B: the text's length.
-int cigar_build(swg_ctx* ctx, const LiftCols& c, CigarSet* S, unsigned long long* scalars) {
+int cigar_build(swg_ctx* ctx, const char* who, const LiftCols& c, CigarSet* S, unsigned long long* scalars) {
   hipStream_t st = ctx->stream;
   const uint64_t k = S->k, B = S->B;
   const uint64_t state_words = (k + 3) / 4;
@@ -283,7 +298,7 @@ int cigar_build(swg_ctx* ctx, const LiftCols& c, CigarSet* S, unsigned long long
   uint64_t* prefix[4] = {nullptr, nullptr, nullptr, nullptr};
   if (B) {
     const uint64_t tiles = (B + CT - 1) / CT;
-    if (tiles >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift_exact: 2^43 bytes of CIGAR text or more in one call");
+    if (tiles >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "%s: 2^43 bytes of CIGAR text or more in one call", who);
     uint64_t* tile_inc = swg_alloc<uint64_t>(ctx, tiles);
     uint32_t* chunk_rank = swg_alloc<uint32_t>(ctx, (B + 15) / 16);
     SWG_CHECK_ARENA(ctx);
@@ -292,7 +307,7 @@ int cigar_build(swg_ctx* ctx, const LiftCols& c, CigarSet* S, unsigned long long
     SWG_KERNEL_CHECK(ctx);
     SWG_TRY(swg_inclusive_sum_scan_u64(ctx, tile_inc, tile_inc, tiles));
     SWG_TRY(swg_read_scalars(ctx, tile_inc + (tiles - 1), &S->ops, 1));  // sizes the prefix arrays
-    if (S->ops >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift_exact: 2^31 ops or more in one call");
+    if (S->ops >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "%s: 2^31 ops or more in one call", who);
     // ops + 1 sums per array, the values from element 1 on: element 1 sits on a 16-byte boundary for the scan's wide loads
     for (auto& p : prefix) p = swg_alloc<uint64_t>(ctx, S->ops + 2) + 1;
     SWG_CHECK_ARENA(ctx);
@@ -313,6 +328,10 @@ int cigar_build(swg_ctx* ctx, const LiftCols& c, CigarSet* S, unsigned long long
   return SWG_OK;
 }
 
+}  // namespace swg_cigar
+
+namespace {
+
 int exact_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
               const swg_cigar_set* cigars, swg_lift_exact_request* req) {
   static_assert(sizeof(swg_cigar_set) == 32 && sizeof(swg_lift_exact_row) == 40 && sizeof(swg_lift_exact_request) == 88, "the ABI's sizes");
@@ -321,19 +340,8 @@ int exact_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_
   SWG_TRY(swg_lift_check_request(ctx, rec, status, regions, m, req->set, req->axes));
   const uint64_t n = rec->n, k = cigars ? cigars->k : 0;
   const uint32_t n_seq = rec->n_seq;
-  if (k >= (uint64_t(1) << 31)) return swg_set_error(ctx, SWG_ERR_RANGE, "lift_exact: 2^31 entries or more in one call");
-  if (k && (!cigars->record || !cigars->offset)) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: NULL record or offset array of the CIGAR set");
   uint64_t B = 0;
-  if (k && n == 0) return bad_set(ctx, 1);  // (any record is >= n)
-  if (k && !on_device) {  // the set is here: its faults cost no device work
-    uint64_t bad = cigars->offset[0] != 0 ? 4u : 0u;
-    for (uint64_t j = 0; j < k; ++j)
-      bad |= (cigars->record[j] >= n ? 1u : 0u) | (j && cigars->record[j - 1] >= cigars->record[j] ? 2u : 0u) |
-             (cigars->offset[j + 1] < cigars->offset[j] ? 4u : 0u);
-    SWG_TRY(bad_set(ctx, bad));
-    B = cigars->offset[k];
-    if (B && !cigars->text) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: NULL text of the CIGAR set");
-  }
+  SWG_TRY(cigar_set_check_host(ctx, "lift_exact", cigars, on_device, n, &B));
   req->n = 0;
   req->candidates[0] = req->candidates[1] = 0;
   req->ops = req->cigar_bad = req->exact_rows = 0;
@@ -365,15 +373,8 @@ int exact_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_
     SWG_CHECK_ARENA(ctx);
     SWG_HIP(ctx, hipMemsetAsync(scalars, 0, C_TOTAL * sizeof(unsigned long long), st));
     uint64_t h[C_TOTAL];
-    if (k && on_device) {
-      SWG_LAUNCH(ctx, "cigar_set_check", cigar_set_check_kernel<<<grid_of(k), TB, 0, st>>>(k, n, S.record, S.offset, scalars));
-      SWG_KERNEL_CHECK(ctx);
-      SWG_TRY(swg_read_scalars(ctx, reinterpret_cast<uint64_t*>(scalars), h, 2));
-      SWG_TRY(bad_set(ctx, h[C_BAD]));
-      S.B = h[C_BYTES];
-      if (S.B && !S.text) return swg_set_error(ctx, SWG_ERR_INVALID, "lift_exact: NULL text of the CIGAR set");
-    }
-    if (k) SWG_TRY(cigar_build(ctx, c, &S, scalars));
+    if (k && on_device) SWG_TRY(cigar_set_check_device(ctx, "lift_exact", n, &S, scalars));
+    if (k) SWG_TRY(cigar_build(ctx, "lift_exact", c, &S, scalars));
     swg_lift_request plain{};
     plain.set = req->set, plain.axes = req->axes;
     plain.capacity = req->capacity;
