@@ -1150,6 +1150,102 @@ int swg_paf_ucsc_chain_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* stat
 int swg_paf_ucsc_chain_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t from, uint64_t batch_bytes,
                             swg_ucsc_counts* counts, char** text, uint64_t* len);
 
+/* ---- differences: every mismatch run, insertion and deletion of the CIGARs, on the device -------------------
+ * The CIGAR set, the walk offsets x / y and the entry states 1 .. 16 are those of the base-exact lift above.  An entry is USABLE when
+ * its state is 0 and its record is in `set` (SWG_IV_ALL, or SWG_IV_KEPT: status != 0).  Each op of a usable entry with letter c and
+ * length l > 0 gives at most one ROW:
+ *   X  SWG_DIFF_SNP   target [t_start + y, t_start + y + l), query length l
+ *   I  SWG_DIFF_INS   target empty at t_start + y,           query length l
+ *   D  SWG_DIFF_DEL   target [t_start + y, t_start + y + l), query length 0
+ *   N  SWG_DIFF_SKIP  as D
+ * =, M, S, H, P and ops of length 0 give no row; adjacent ops of one kind are NOT merged.  The query interval of query length L at
+ * walk offset x is [q_start + x, q_start + x + L) on '+' and [q_end - x - L, q_end - x) on '-' (L == 0: the empty interval at that
+ * point).  A row is written when its kind is in `kinds` and -- INS, DEL, SKIP only -- l >= min_indel.  left: the length of the op
+ * directly in front of the row's op in the same entry when its letter is '=', else 0; right: the same for the op directly behind.
+ * Rows come in (entry, op) order: record order, then text order (on '-' descending along the query).
+ * Summary: per ordered genome pair (seq_genome[q_id], seq_genome[t_id]) over ALL ops of the usable entries, whatever kinds and
+ * min_indel are; pairs ascend by (q_genome, t_genome); aligned = eq + snp_bases + m_columns.  Spectrum: [4][SWG_DIFF_BINS] over the
+ * same ops, first index SNP, INS, DEL, SKIP, bin = the bit length of l (bin 0 stays 0).
+ * Capacity protocol: rows is written when n_rows <= row_capacity, pairs when n_pairs <= pair_capacity (each only when non-NULL; rows
+ * that nobody can take are counted and not built); spectrum and state whenever non-NULL; the counts whenever the call succeeds.
+ * Refusals of the set as in swg_lift_exact_records; kinds == 0 or > 15, SWG_IV_KEPT without status, a NULL seq_genome, a record of the
+ * set whose q_id / t_id is >= n_seq or whose sequence has a genome id >= n_genome: SWG_ERR_INVALID; 2^32 text bytes or more, 2^31
+ * rows or more: SWG_ERR_RANGE.  k == 0 needs no device work.  Scratch from the arena (SWG_ERR_OOM under a limit that does not hold
+ * it): the build's (see swg_lift_exact_records) plus, per op, 2 bytes (letter kind, row flag); per entry 8 bytes (its genome pair);
+ * per row 4 + 32 bytes when the rows are built; the genome-pair table (96 bytes per slot, 120 per listed pair); the host seam stages
+ * 26 bytes per record and 4 per sequence. */
+#define SWG_DIFF_SNP 1u
+#define SWG_DIFF_INS 2u
+#define SWG_DIFF_DEL 4u
+#define SWG_DIFF_SKIP 8u
+#define SWG_DIFF_MINUS 256u /* swg_diff_row.kind_flags bit 8: the record is on the '-' strand; bits 0 .. 7: the kind */
+#define SWG_DIFF_BINS 33
+typedef struct swg_diff_row {
+  uint32_t record, kind_flags;
+  uint32_t t_start, t_end;
+  uint32_t q_start, q_end;
+  uint32_t left, right;
+} swg_diff_row; /* 32 bytes */
+typedef struct swg_diff_pair {
+  uint32_t q_genome, t_genome;
+  uint64_t entries, aligned, eq;
+  uint64_t m_columns;            /* columns under M ops: mismatches there are unknowable */
+  uint64_t snp_runs, snp_bases;
+  uint64_t n_ins, ins_bases;
+  uint64_t n_del, del_bases;
+  uint64_t n_skip, skip_bases;
+} swg_diff_pair; /* 104 bytes */
+typedef struct swg_diff_request {
+  uint32_t set, kinds;           /* in */
+  uint32_t min_indel, reserved;  /* in; reserved must be 0 */
+  uint64_t row_capacity;         /* in: entries `rows` can hold */
+  swg_diff_row* rows;            /* in: caller-owned or NULL; written only when n_rows <= row_capacity */
+  uint64_t pair_capacity;
+  swg_diff_pair* pairs;          /* written only when n_pairs <= pair_capacity */
+  uint64_t* spectrum;            /* in: caller-owned [4 * SWG_DIFF_BINS] or NULL; written whenever non-NULL */
+  uint8_t* state;                /* in: caller-owned [k] or NULL; written whenever non-NULL */
+  uint64_t n_rows;               /* out */
+  uint64_t n_pairs;              /* out */
+  uint64_t ops;                  /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;            /* out: entries with a state bit of 1 .. 8 */
+  uint64_t usable;               /* out: usable entries */
+} swg_diff_request; /* 104 bytes */
+/* Everything on the host.  seq_genome: [rec->n_seq]. */
+int swg_diff_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                     const swg_cigar_set* cigars, swg_diff_request* req);
+/* Columns, strand, seq_genome, status and the three arrays of the set in device memory of ctx's GPU; the set structure, the request
+ * and its arrays on the host. */
+int swg_diff_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                            const swg_cigar_set* cigars, swg_diff_request* req);
+typedef struct swg_diff_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t usable;   /* usable entries */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t untagged; /* records without a cg:Z: tag */
+  uint64_t rows;
+  uint64_t snp_runs, snp_bases; /* over all ops of the usable entries, as the summary */
+  uint64_t n_ins, ins_bases;
+  uint64_t n_del, del_bases;
+  uint64_t n_skip, skip_bases;
+  uint64_t m_columns;
+  uint64_t batches;  /* device calls */
+} swg_diff_counts; /* 120 bytes */
+/* The differences of an open PAF into files: the records of `set` with the LAST cg:Z: tag of each one's line as its entry (a line
+ * without the tag is an empty entry), in batches as swg_paf_ucsc_chain_write sends them; both texts are the same bytes for every
+ * batch_bytes.  Genomes: the handle's seq_genome_two.  Either path may be NULL (not both); without rows_path the rows are counted
+ * and not built.  Tab-separated texts, each with one header line when the set has a record:
+ *   rows     t_name t_start t_end q_name q_start q_end strand(+|-) kind(SNP|INS|DEL|SKIP) len left right record
+ *   summary  q_genome t_genome entries aligned eq m_columns snp_runs snp_bases ins ins_bases del del_bases skip skip_bases, one line
+ *            per genome pair with an entry, ascending; then `#spectrum KIND lo hi count` per non-empty bin
+ * A PAF without records of the set gives empty outputs (no header either) and needs no device (ctx may be NULL).  Every refusal comes before a file is
+ * opened.  A handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  counts may be NULL.  Errors: swg_alnstats_last_error(). */
+int swg_paf_diffs_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t kinds, uint32_t min_indel,
+                        uint64_t batch_bytes, const char* rows_path, const char* summary_path, swg_diff_counts* counts);
+/* The same as malloc'd texts (release each with swg_free); rows_text or summary_text may be NULL (not both). */
+int swg_paf_diffs_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t kinds, uint32_t min_indel,
+                       uint64_t batch_bytes, swg_diff_counts* counts, char** rows_text, uint64_t* rows_len, char** summary_text,
+                       uint64_t* summary_len);
+
 /* ---- transitive lift: the closure of each region under the lift, hop by hop, on the device -----------------
  * Per region, independently of every other region (all sets are point sets per sequence, all arithmetic is in integers):
  *   hop 0      F_0 = V_0 = { [start, end) on seq } when seq is known and start < end, else both empty

@@ -24,6 +24,7 @@ from .dotplot import Dotplot, DotplotResult, dotplot_records, dotplot_records_de
 from .lift import Lift, LiftClosure, LiftClosureResult, LiftResult, lift_closure_records, lift_closure_records_device, lift_records, lift_records_device  # noqa: F401
 from .lift import LiftExactResult, lift_exact_records, lift_exact_records_device, lift_hit_records, lift_hit_records_device  # noqa: F401
 from .ucsc import UcscChain, UcscResult, ucsc_chain_records, ucsc_chain_records_device  # noqa: F401  (its CHAIN_DTYPE / BLOCK_DTYPE: sweepga_amd.ucsc)
+from .diffs import Diffs, DiffsResult, diff_records, diff_records_device  # noqa: F401  (its ROW_DTYPE / PAIR_DTYPE: sweepga_amd.diffs)
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401
                   parse_identity_value)
 

@@ -46,6 +46,7 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_lift_exact_records", "swg_lift_exact_records_device", "swg_lift_hit_records", "swg_lift_hit_records_device",
            "swg_paf_lift_exact", "swg_paf_lift_exact_counts",
            "swg_ucsc_chain_records", "swg_ucsc_chain_records_device", "swg_paf_ucsc_chain_write", "swg_paf_ucsc_chain_text",
+           "swg_diff_records", "swg_diff_records_device", "swg_paf_diffs_write", "swg_paf_diffs_text",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
@@ -330,6 +331,28 @@ class SwgUcscCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "chains", "bad", "beyond", "untagged", "empty", "blocks", "batches")]
 
 
+class SwgDiffRow(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("record", "kind_flags", "t_start", "t_end", "q_start", "q_end", "left", "right")]
+
+
+DIFF_SUMS = ("entries", "aligned", "eq", "m_columns", "snp_runs", "snp_bases", "n_ins", "ins_bases", "n_del", "del_bases", "n_skip", "skip_bases")
+
+
+class SwgDiffPair(C.Structure):
+    _fields_ = [("q_genome", C.c_uint32), ("t_genome", C.c_uint32)] + [(k, C.c_uint64) for k in DIFF_SUMS]
+
+
+class SwgDiffRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("kinds", C.c_uint32), ("min_indel", C.c_uint32), ("reserved", C.c_uint32), ("row_capacity", C.c_uint64),
+                ("rows", C.c_void_p), ("pair_capacity", C.c_uint64), ("pairs", C.c_void_p), ("spectrum", C.c_void_p), ("state", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in ("n_rows", "n_pairs", "ops", "cigar_bad", "usable")]
+
+
+class SwgDiffCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "usable", "bad", "untagged", "rows", "snp_runs", "snp_bases", "n_ins", "ins_bases", "n_del",
+                                          "del_bases", "n_skip", "skip_bases", "m_columns", "batches")]
+
+
 class SwgClosureRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")]
 
@@ -608,6 +631,16 @@ def load():
     lib.swg_paf_ucsc_chain_text.restype = C.c_int
     lib.swg_paf_ucsc_chain_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SwgUcscCounts),
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_diff_records", "swg_diff_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgCigarSet), C.POINTER(SwgDiffRequest)]
+    lib.swg_paf_diffs_write.restype = C.c_int
+    lib.swg_paf_diffs_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p,
+                                        C.POINTER(SwgDiffCounts)]
+    lib.swg_paf_diffs_text.restype = C.c_int
+    lib.swg_paf_diffs_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SwgDiffCounts),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_lift_closure_records", "swg_lift_closure_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

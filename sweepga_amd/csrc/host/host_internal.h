@@ -153,6 +153,16 @@ struct swg_ucsc_sink {
 };
 // one batch into the sink: for every row with blocks its header (hdr[j]) and its block lines out of the device's text
 void swg_ucsc_splice(swg_ucsc_sink* sink, const swg_ucsc_chain* rows, uint64_t k, const std::string* hdr, const char* text, uint64_t text_bytes);
+// ---- differences (swg_diffs.hip: kernels and record seams; diffs_text.cpp: the two PAF seams) ----
+int swg_diff_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                 const swg_cigar_set* cigars, swg_diff_request* req);
+// `#target t_start t_end query q_start q_end strand kind len left right record\n`, and one row under its two names
+void swg_diffs_rows_header(std::string& o);
+void swg_diffs_row_text(std::string& o, const char* t_name, const char* q_name, const swg_diff_row& w);
+// `add` (ascending by genome pair, as a call returns them) summed into `total` (ascending, and so it stays)
+void swg_diffs_merge_pairs(std::vector<swg_diff_pair>* total, const swg_diff_pair* add, uint64_t n);
+// header, one line per genome pair, then `#spectrum KIND lo hi count` per non-empty bin of spectrum [4][SWG_DIFF_BINS]
+std::string swg_diffs_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_diff_pair>& pairs, const uint64_t* spectrum);
 // ---- transitive lift (swg_lift_closure.hip): swg_lift_run's arguments ----
 int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                          swg_closure_request* req);

@@ -417,6 +417,21 @@ void write_ucsc_chain(const std::string& path, swg_ctx* ctx, const swg_paf* paf,
                  (unsigned long long)c.bad, (unsigned long long)c.beyond, (unsigned long long)c.untagged, (unsigned long long)c.empty);
 }
 
+// --diffs / --diffs-summary: the difference list of swg_paf_diffs_write, one row per X, I, D or N op of the set's cg:Z: CIGARs (built on
+// the device), and its sums per genome pair; either path may be empty.  What it met goes to standard error in one line.
+void write_diffs(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set,
+                 uint32_t kinds, uint32_t min_indel, uint64_t batch, bool quiet) {
+  swg_diff_counts c;
+  if (swg_paf_diffs_write(ctx, paf, status, set, kinds, min_indel, batch, rows_path.empty() ? nullptr : rows_path.c_str(),
+                          summary_path.empty() ? nullptr : summary_path.c_str(), &c) != SWG_OK)
+    die(3, std::string("--diffs: ") + swg_alnstats_last_error());
+  if (!quiet)
+    std::fprintf(stderr, "[sweepga-gpu] --diffs: %llu rows of %llu usable entries in %llu records, %llu mismatched, %llu inserted, %llu deleted bases, "
+                 "%llu columns under M ops, %llu bad, %llu without a cg:Z: tag\n", (unsigned long long)c.rows, (unsigned long long)c.usable,
+                 (unsigned long long)c.records, (unsigned long long)c.snp_bases, (unsigned long long)c.ins_bases,
+                 (unsigned long long)(c.del_bases + c.skip_bases), (unsigned long long)c.m_columns, (unsigned long long)c.bad, (unsigned long long)c.untagged);
+}
+
 // --lift-closure / --lift-closure-summary: the two texts of swg_paf_lift_closure (the regions walked through the mappings for up to
 // `hops` hops), both from one walk.  "-" = standard error.
 void write_lift_closure(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
@@ -498,6 +513,10 @@ int main(int argc, char** argv) {
   uint32_t ucsc_from = SWG_UCSC_FROM_TARGET, ucsc_set = SWG_IV_KEPT;
   uint64_t ucsc_batch = 0;  // --ucsc-chain-batch: 0 = the library's default
   bool ucsc_flag = false;   // (one of --ucsc-chain-from / --ucsc-chain-set / --ucsc-chain-batch was given)
+  std::string diffs_path, diffs_summary_path;  // --diffs, --diffs-summary: empty = not given
+  uint32_t diffs_set = SWG_IV_KEPT, diffs_kinds = SWG_DIFF_SNP | SWG_DIFF_INS | SWG_DIFF_DEL;
+  uint64_t diffs_min_indel = 1, diffs_batch = 0;  // --diffs-min-indel; --diffs-batch: 0 = the library's default
+  bool diffs_flag = false;  // (one of --diffs-set / --diffs-kinds / --diffs-min-indel / --diffs-batch was given)
   std::string closure_path, closure_summary_path;  // --lift-closure, --lift-closure-summary: empty = not given
   uint64_t lift_hops = 0, lift_min_length = 100;   // --lift-hops (0 = not given), --lift-min-length
   bool lift_min_length_flag = false;
@@ -618,6 +637,41 @@ int main(int argc, char** argv) {
       if (!parse_metric_number(value(), &ucsc_batch) || ucsc_batch == 0) die(2, "invalid value for --ucsc-chain-batch: 1 or more bytes");
       ucsc_flag = true;
     }
+    else if (a == "--diffs" || a == "--diffs-summary") {
+      std::string& path = a == "--diffs" ? diffs_path : diffs_summary_path;
+      path = value();
+      if (path.empty()) die(2, "empty value for " + a);
+      if (path == "-") die(2, a + " needs a file: the difference list is not a standard error report");
+    }
+    else if (a == "--diffs-set") {
+      const std::string v = value();
+      if (v == "kept") diffs_set = SWG_IV_KEPT;
+      else if (v == "all") diffs_set = SWG_IV_ALL;
+      else die(2, "invalid value for --diffs-set: kept or all");
+      diffs_flag = true;
+    }
+    else if (a == "--diffs-kinds") {
+      const std::string v = value() + ",";
+      diffs_kinds = 0;
+      for (size_t from = 0, to; (to = v.find(',', from)) != std::string::npos; from = to + 1) {
+        const std::string w = v.substr(from, to - from);
+        if (w == "snp") diffs_kinds |= SWG_DIFF_SNP;
+        else if (w == "ins") diffs_kinds |= SWG_DIFF_INS;
+        else if (w == "del") diffs_kinds |= SWG_DIFF_DEL;
+        else if (w == "skip") diffs_kinds |= SWG_DIFF_SKIP;
+        else if (!w.empty()) die(2, "invalid value for --diffs-kinds: a comma-separated list of snp, ins, del, skip");
+      }
+      if (!diffs_kinds) die(2, "invalid value for --diffs-kinds: the list is empty");
+      diffs_flag = true;
+    }
+    else if (a == "--diffs-min-indel") {
+      if (!parse_metric_number(value(), &diffs_min_indel) || diffs_min_indel > 0xffffffffull) die(2, "invalid value for --diffs-min-indel: 0 .. 2^32 - 1");
+      diffs_flag = true;
+    }
+    else if (a == "--diffs-batch") {
+      if (!parse_metric_number(value(), &diffs_batch) || diffs_batch == 0) die(2, "invalid value for --diffs-batch: 1 or more bytes");
+      diffs_flag = true;
+    }
     else if (a == "--lift-hops") { if (!parse_u64(value(), &lift_hops) || lift_hops < 1 || lift_hops > 65535) die(2, "invalid value for --lift-hops: 1 .. 65535"); }
     else if (a == "--lift-closure") { closure_path = value(); if (closure_path.empty()) die(2, "empty value for --lift-closure"); }
     else if (a == "--lift-closure-summary") { closure_summary_path = value(); if (closure_summary_path.empty()) die(2, "empty value for --lift-closure-summary"); }
@@ -734,6 +788,8 @@ int main(int argc, char** argv) {
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
                 "         [--lift-exact]\n"
                 "         [--ucsc-chain FILE] [--ucsc-chain-from target|query] [--ucsc-chain-set kept|all] [--ucsc-chain-batch BYTES]\n"
+                "         [--diffs FILE] [--diffs-summary FILE] [--diffs-set kept|all] [--diffs-kinds snp,ins,del,skip] [--diffs-min-indel N]\n"
+                "         [--diffs-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
@@ -826,6 +882,15 @@ int main(int argc, char** argv) {
                 "  --ucsc-chain-from target|query  which side is the chain's reference sequence (default target, as liftOver expects)\n"
                 "  --ucsc-chain-set kept|all       the records that give chains (default kept)\n"
                 "  --ucsc-chain-batch BYTES        CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
+                "  --diffs FILE        write every mismatch run, insertion and deletion of the cg:Z: CIGARs, one line per X, I, D or N op (built on\n"
+                "                      the device; adjacent ops are not merged): t_name t_start t_end q_name q_start q_end strand kind len left\n"
+                "                      right record, left / right the '=' runs beside it; one line of counts on standard error\n"
+                "  --diffs-summary FILE  per genome pair the aligned, matching, mismatched, inserted and deleted bases over all ops, and a length\n"
+                "                      spectrum per kind; alone: the rows are counted and not built\n"
+                "  --diffs-set kept|all            the records that are read (default kept)\n"
+                "  --diffs-kinds LIST              the kinds that give rows: snp,ins,del,skip (default snp,ins,del)\n"
+                "  --diffs-min-indel N             rows of ins, del and skip from N bases on (default 1; mismatches are never dropped)\n"
+                "  --diffs-batch BYTES             CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
                 "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
@@ -869,6 +934,8 @@ int main(int argc, char** argv) {
   if (lift_exact && (!lift || lift_path.empty())) die(2, "--lift-exact needs --lift-regions and --lift");
   if (ucsc_path.empty() && ucsc_flag) die(2, "--ucsc-chain-from, --ucsc-chain-set and --ucsc-chain-batch need --ucsc-chain");
   const bool ucsc = !ucsc_path.empty();
+  const bool diffs = !diffs_path.empty() || !diffs_summary_path.empty();
+  if (!diffs && diffs_flag) die(2, "--diffs-set, --diffs-kinds, --diffs-min-indel and --diffs-batch need --diffs or --diffs-summary");
   if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
   if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
   if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
@@ -960,7 +1027,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1144,6 +1211,13 @@ int main(int argc, char** argv) {
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_ucsc_chain(ucsc_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), ucsc_set, ucsc_from, ucsc_batch, quiet);
     }
+    if (diffs) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_diffs(diffs_path, diffs_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel,
+                  diffs_batch, quiet);
+    }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
     return 0;
@@ -1322,6 +1396,12 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_ucsc_chain(ucsc_path, ctx, paf, status.data(), ucsc_set, ucsc_from, ucsc_batch, quiet);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --ucsc-chain: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --diffs / --diffs-summary: on the first context, the records in batches of bounded CIGAR text
+  if (diffs) {
+    const auto tb = clk::now();
+    write_diffs(diffs_path, diffs_summary_path, ctx, paf, status.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel, diffs_batch, quiet);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --diffs: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

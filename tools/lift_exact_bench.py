@@ -30,10 +30,18 @@ from tools.lift_bench import OWN, REPS, timed  # noqa: E402
 CIGAR_OWN = ("cigar_set_check", "cigar_count", "cigar_parse", "cigar_entries", "cigar_refine")
 
 
-def synthetic_cigar(lq, lt):
-    """About one op per 100 bases, the sides' sums exact"""
+DIFF_UNIT = "99=1X48=2I50=2D"      # 200 bases on either side, as "198=2X": a mismatch, a 2-base insertion and a 2-base deletion
+
+
+def synthetic_cigar(lq, lt, diff_every=0):
+    """About one op per 100 bases, the sides' sums exact.  diff_every = N > 0: every N-th unit of 200 bases is DIFF_UNIT (for
+    tools/diffs_bench.py, which needs indels inside the mappings); 0: the text as it always was."""
     both = min(lq, lt)
-    text = "198=2X" * (both // 200)
+    units = both // 200
+    if diff_every > 0:
+        text = ("198=2X" * (diff_every - 1) + DIFF_UNIT) * (units // diff_every) + "198=2X" * (units % diff_every)
+    else:
+        text = "198=2X" * units
     if both % 200:
         text += "%d=" % (both % 200)
     if lq != lt:
