@@ -1642,6 +1642,101 @@ int swg_windows_records_device(swg_ctx* ctx, const swg_records* rec, const uint3
 int swg_paf_windows(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t axis, uint32_t window, const char* other_genome,
                     char** out_text, uint64_t* out_len);
 
+/* ---- divergence: exact matches, mismatches and indels per fixed window, from the CIGARs (no reference counterpart; DESIGN.md
+ * section 33) ----
+ * The windows, the axis and who takes part are those of the windows above; the CIGAR set, the walk offsets x / y, the entry states
+ * and USABLE (state 0, record in `set`: SWG_IV_ALL, or SWG_IV_KEPT: status != 0) are those of the differences.  One set per call.
+ *   takes part  a record of the set with seq_genome[s] != seq_genome[o], a < b and other_genome == SWG_WINDOWS_ANY or
+ *               seq_genome[o] == other_genome.  One that ends beyond its sequence is an error that names the smallest such record.
+ *   listed      a sequence that carries a record that takes part, WHETHER OR NOT the record has an entry in the CIGAR set: the
+ *               window table does not depend on which records a call's CIGAR set carries.
+ *   coordinate  of an aligned column or of a base facing a gap: t_start + y on axis 1; on axis 0 q_start + x on '+' and
+ *               q_end - 1 - x on '-'.
+ * Per window, over the usable entries whose records take part (ov = the overlap of [a, b) with the window):
+ *   n              the entries with ov > 0
+ *   aligned        the columns of =, X and M ops whose axis coordinate is in the window
+ *   matches        those of = ops;  mismatches  those of X ops;  m_columns  those of M ops (aligned is the sum of the three)
+ *   unaligned      axis bases in the window that the entry consumes against a gap (D / N on axis 1, I on axis 0); aligned +
+ *                  unaligned = the sum of ov
+ *   inserted       bases of the OTHER sequence inserted at a point p of this axis (I on axis 1, D / N on axis 0): p = t_start + y
+ *                  on axis 1, q_start + x on axis 0 '+', q_end - x on axis 0 '-'; the op belongs with all its bases to the window
+ *                  of base min(p, b - 1)
+ *   mismatch_runs  X ops of length > 0 whose lowest axis base is in the window
+ *   indels         I, D and N ops of length > 0: one with axis extent in the window of its lowest axis base, one without in the
+ *                  window of `inserted`
+ * S, H, P and ops of length 0 add nothing.  Column identity is matches / aligned, gap-compressed identity matches / (aligned +
+ * indels), BLAST identity matches / (aligned + unaligned + inserted): the caller divides.
+ * Rows: one per window of every listed sequence, (seq, window) ascending, empty windows included.  Summary: one entry per listed
+ * sequence, ascending: windows, records (of the set that take part on it), entries (the usable ones among them) and the eight sums
+ * over its windows.  Nothing depends on the order of the records or on a launch shape.
+ * `want` and the capacity protocol are those of swg_windows_records; state whenever non-NULL; ops, cigar_bad and usable (usable
+ * entries whose records take part) whenever the call succeeds.  Refusals: those of swg_windows_records (window == 0, axis > 1, a bad
+ * other_genome, want, reserved, NULL columns, bad ids, the record beyond its sequence) and of the set as in swg_lift_exact_records,
+ * set > 1, SWG_IV_KEPT without status: SWG_ERR_INVALID; n, k or ops >= 2^31, 2^32 text bytes, 2^31 windows or more (refused before
+ * anything of that size is allocated): SWG_ERR_RANGE.  n == 0 needs no device work.  Scratch from the arena (SWG_ERR_OOM under a
+ * limit that does not hold it): the build's (see swg_lift_exact_records) plus 1 byte per op, 16 per entry, 17 per sequence, 104 per
+ * window plus 80 for its row, 88 per listed sequence; the host seam stages 26 bytes per record and 8 per sequence. */
+typedef struct swg_divergence_row {
+  uint32_t seq, start, end; /* the window, half-open, clipped to seq_len */
+  uint32_t n;
+  uint64_t aligned, matches, mismatches, m_columns, unaligned, inserted, mismatch_runs, indels;
+} swg_divergence_row; /* 80 bytes, no implicit padding */
+typedef struct swg_divergence_seq {
+  uint32_t seq, windows;
+  uint64_t records, entries;
+  uint64_t aligned, matches, mismatches, m_columns, unaligned, inserted, mismatch_runs, indels;
+} swg_divergence_seq; /* 88 bytes, no implicit padding */
+#define SWG_DIVERGENCE_ROWS 1u
+#define SWG_DIVERGENCE_SUMMARY 2u
+typedef struct swg_divergence_request {
+  uint32_t set;             /* in: SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t axis;            /* 0 = query, 1 = target */
+  uint32_t window;          /* W >= 1 */
+  uint32_t other_genome;    /* a genome id or SWG_WINDOWS_ANY */
+  uint32_t want;            /* the two bits above */
+  uint32_t reserved;        /* 0 */
+  uint64_t capacity;        /* in: entries `rows` can hold */
+  swg_divergence_row* rows; /* in: caller-owned [capacity] or NULL; written only when n_rows <= capacity */
+  uint64_t seq_capacity;
+  swg_divergence_seq* seqs; /* written only when n_seqs <= seq_capacity */
+  uint8_t* state;           /* in: caller-owned [k] or NULL; written whenever non-NULL */
+  uint64_t n_rows;          /* out (rows bit) */
+  uint64_t n_seqs;          /* out (summary bit) */
+  uint64_t ops;             /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;       /* out: entries with a state bit of 1 .. 8 */
+  uint64_t usable;          /* out: usable entries whose records take part */
+} swg_divergence_request; /* 104 bytes, no implicit padding */
+/* Everything on the host.  seq_len, seq_genome: [rec->n_seq]. */
+int swg_divergence_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                           const uint8_t* status, const swg_cigar_set* cigars, swg_divergence_request* req);
+/* Columns, strand, seq_len, seq_genome, status and the three arrays of the set in device memory of ctx's GPU; the set structure, the
+ * request and its arrays on the host. */
+int swg_divergence_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                                  const uint8_t* status, const swg_cigar_set* cigars, swg_divergence_request* req);
+typedef struct swg_divergence_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t usable;   /* usable entries whose records take part */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t untagged; /* records of the set without a cg:Z: tag */
+  uint64_t windows;  /* rows */
+  uint64_t seqs;     /* listed sequences */
+  uint64_t batches;  /* device calls */
+} swg_divergence_counts; /* 56 bytes */
+/* Both texts of an open PAF (release each with swg_free; a text is asked for by a non-NULL out_text[k] on entry, as in
+ * swg_paf_windows): the records of `set` with the LAST cg:Z: tag of each one's line as its entry, in batches as
+ * swg_paf_ucsc_chain_write cuts them, one device call per batch over ALL records and that batch's CIGAR set, the rows and summaries
+ * added up across the batches; both texts are the same bytes for every batch_bytes.  Genome map, names and lengths as in
+ * swg_paf_windows.  Tab-separated, integers only:
+ *   text 0  header `#sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels`, one line
+ *           per row (the first three columns are a BED source)
+ *   text 1  header `#sequence length windows records entries aligned matches mismatches m_columns unaligned inserted mismatch_runs
+ *           indels`, one line per listed sequence
+ * A PAF without records of the set gives the header-only texts and needs no device (ctx may be NULL then).  set > 1, SWG_IV_KEPT
+ * without status, axis > 1, window == 0, an unknown genome name: SWG_ERR_INVALID; a handle with rebased columns:
+ * SWG_ERR_UNSUPPORTED.  counts may be NULL.  Errors: swg_alnstats_last_error(). */
+int swg_paf_divergence(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t axis, uint32_t window,
+                       const char* other_genome, uint64_t batch_bytes, char** out_text, uint64_t* out_len, swg_divergence_counts* counts);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498

@@ -50,7 +50,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
-           "swg_windows_records", "swg_windows_records_device", "swg_paf_windows"]
+           "swg_windows_records", "swg_windows_records_device", "swg_paf_windows",
+           "swg_divergence_records", "swg_divergence_records_device", "swg_paf_divergence"]
 
 
 class SwgError(RuntimeError):
@@ -329,6 +330,27 @@ class SwgUcscRequest(C.Structure):
 
 class SwgUcscCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "chains", "bad", "beyond", "untagged", "empty", "blocks", "batches")]
+
+
+DIVERGENCE_SUMS = ("aligned", "matches", "mismatches", "m_columns", "unaligned", "inserted", "mismatch_runs", "indels")
+
+
+class SwgDivergenceRow(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("seq", "start", "end", "n")] + [(k, C.c_uint64) for k in DIVERGENCE_SUMS]
+
+
+class SwgDivergenceSeq(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("windows", C.c_uint32), ("records", C.c_uint64), ("entries", C.c_uint64)] + [(k, C.c_uint64) for k in DIVERGENCE_SUMS]
+
+
+class SwgDivergenceRequest(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("set", "axis", "window", "other_genome", "want", "reserved")]
+    _fields_ += [("capacity", C.c_uint64), ("rows", C.c_void_p), ("seq_capacity", C.c_uint64), ("seqs", C.c_void_p), ("state", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in ("n_rows", "n_seqs", "ops", "cigar_bad", "usable")]
+
+
+class SwgDivergenceCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "usable", "bad", "untagged", "windows", "seqs", "batches")]
 
 
 class SwgDiffRow(C.Structure):
@@ -641,6 +663,14 @@ def load():
     lib.swg_paf_diffs_text.restype = C.c_int
     lib.swg_paf_diffs_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SwgDiffCounts),
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_divergence_records", "swg_divergence_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgCigarSet),
+                      C.POINTER(SwgDivergenceRequest)]
+    lib.swg_paf_divergence.restype = C.c_int
+    lib.swg_paf_divergence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_uint64), C.POINTER(SwgDivergenceCounts)]
     for name in ("swg_lift_closure_records", "swg_lift_closure_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

@@ -163,6 +163,20 @@ void swg_diffs_row_text(std::string& o, const char* t_name, const char* q_name, 
 void swg_diffs_merge_pairs(std::vector<swg_diff_pair>* total, const swg_diff_pair* add, uint64_t n);
 // header, one line per genome pair, then `#spectrum KIND lo hi count` per non-empty bin of spectrum [4][SWG_DIFF_BINS]
 std::string swg_diffs_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_diff_pair>& pairs, const uint64_t* spectrum);
+// ---- divergence (swg_divergence.hip: kernels and record seams; divergence_text.cpp: the PAF seam) ----
+// vec_rows / vec_seqs: library-owned storage instead of the request's arrays (swg_paf_divergence)
+int swg_divergence_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_len, const uint32_t* seq_genome, uint32_t n_genome,
+                       const uint8_t* status, const swg_cigar_set* cigars, swg_divergence_request* req, std::vector<swg_divergence_row>* vec_rows,
+                       std::vector<swg_divergence_seq>* vec_seqs);
+// `#sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels\n`, and one row under its name
+void swg_divergence_rows_header(std::string& o);
+void swg_divergence_row_text(std::string& o, const char* name, const swg_divergence_row& w);
+// `#sequence length windows records entries` and the eight sums, and one listed sequence under its name and length
+void swg_divergence_summary_header(std::string& o);
+void swg_divergence_seq_text(std::string& o, const char* name, uint64_t length, const swg_divergence_seq& s);
+// one batch's rows / summaries into the total (first: taken as they are): n, entries and the sums add; false = the keys disagree
+bool swg_divergence_merge_rows(std::vector<swg_divergence_row>* total, const std::vector<swg_divergence_row>& add, bool first);
+bool swg_divergence_merge_seqs(std::vector<swg_divergence_seq>* total, const std::vector<swg_divergence_seq>& add, bool first);
 // ---- transitive lift (swg_lift_closure.hip): swg_lift_run's arguments ----
 int swg_lift_closure_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
                          swg_closure_request* req);

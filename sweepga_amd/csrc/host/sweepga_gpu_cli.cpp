@@ -432,6 +432,24 @@ void write_diffs(const std::string& rows_path, const std::string& summary_path, 
                  (unsigned long long)(c.del_bases + c.skip_bases), (unsigned long long)c.m_columns, (unsigned long long)c.bad, (unsigned long long)c.untagged);
 }
 
+// --divergence / --divergence-summary: the two texts of swg_paf_divergence (exact matches, mismatches and indels per fixed window,
+// from the set's cg:Z: CIGARs, built on the device).  "-" = standard error.  What it met goes to standard error in one line.
+void write_divergence(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set,
+                      uint32_t axis, uint32_t window, const std::string& genome, uint64_t batch, bool quiet) {
+  char marker = 0;  // (a text is asked for by a non-NULL entry)
+  char* text[2] = {rows_path.empty() ? nullptr : &marker, summary_path.empty() ? nullptr : &marker};
+  uint64_t len[2] = {0, 0};
+  swg_divergence_counts c;
+  if (swg_paf_divergence(ctx, paf, status, set, axis, window, genome.empty() ? nullptr : genome.c_str(), batch, text, len, &c) != SWG_OK)
+    die(3, std::string("--divergence: ") + swg_alnstats_last_error());
+  const std::string* paths[2] = {&rows_path, &summary_path};
+  write_texts(paths, text, len, 2);
+  if (!quiet)
+    std::fprintf(stderr, "[sweepga-gpu] --divergence: %llu windows on %llu sequences from %llu usable entries of %llu records, %llu bad, "
+                 "%llu without a cg:Z: tag\n", (unsigned long long)c.windows, (unsigned long long)c.seqs, (unsigned long long)c.usable,
+                 (unsigned long long)c.records, (unsigned long long)c.bad, (unsigned long long)c.untagged);
+}
+
 // --lift-closure / --lift-closure-summary: the two texts of swg_paf_lift_closure (the regions walked through the mappings for up to
 // `hops` hops), both from one walk.  "-" = standard error.
 void write_lift_closure(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status,
@@ -517,6 +535,10 @@ int main(int argc, char** argv) {
   uint32_t diffs_set = SWG_IV_KEPT, diffs_kinds = SWG_DIFF_SNP | SWG_DIFF_INS | SWG_DIFF_DEL;
   uint64_t diffs_min_indel = 1, diffs_batch = 0;  // --diffs-min-indel; --diffs-batch: 0 = the library's default
   bool diffs_flag = false;  // (one of --diffs-set / --diffs-kinds / --diffs-min-indel / --diffs-batch was given)
+  std::string divergence_path, divergence_summary_path, divergence_genome;  // --divergence, --divergence-summary: empty = no file; -genome: empty = any
+  uint32_t divergence_set = SWG_IV_KEPT, divergence_axis = 0;
+  uint64_t divergence_window = 10000, divergence_batch = 0;  // --divergence-window; --divergence-batch: 0 = the library's default
+  bool divergence_flag = false;  // (one of the --divergence-* sub-options was given)
   std::string closure_path, closure_summary_path;  // --lift-closure, --lift-closure-summary: empty = not given
   uint64_t lift_hops = 0, lift_min_length = 100;   // --lift-hops (0 = not given), --lift-min-length
   bool lift_min_length_flag = false;
@@ -672,6 +694,39 @@ int main(int argc, char** argv) {
       if (!parse_metric_number(value(), &diffs_batch) || diffs_batch == 0) die(2, "invalid value for --diffs-batch: 1 or more bytes");
       diffs_flag = true;
     }
+    else if (a == "--divergence" || a == "--divergence-summary") {
+      std::string& path = a == "--divergence" ? divergence_path : divergence_summary_path;
+      path = value();
+      if (path.empty()) die(2, "empty value for " + a);
+    }
+    else if (a == "--divergence-window") {
+      if (!parse_metric_number(value(), &divergence_window) || divergence_window == 0 || divergence_window > 0xffffffffull)
+        die(2, "invalid value for --divergence-window: 1 .. 2^32 - 1");
+      divergence_flag = true;
+    }
+    else if (a == "--divergence-axis") {
+      const std::string v = value();
+      if (v == "query") divergence_axis = 0;
+      else if (v == "target") divergence_axis = 1;
+      else die(2, "invalid value for --divergence-axis: query or target");
+      divergence_flag = true;
+    }
+    else if (a == "--divergence-genome") {
+      divergence_genome = value();
+      if (divergence_genome.empty()) die(2, "empty value for --divergence-genome");
+      divergence_flag = true;
+    }
+    else if (a == "--divergence-set") {
+      const std::string v = value();
+      if (v == "kept") divergence_set = SWG_IV_KEPT;
+      else if (v == "all") divergence_set = SWG_IV_ALL;
+      else die(2, "invalid value for --divergence-set: kept or all");
+      divergence_flag = true;
+    }
+    else if (a == "--divergence-batch") {
+      if (!parse_metric_number(value(), &divergence_batch) || divergence_batch == 0) die(2, "invalid value for --divergence-batch: 1 or more bytes");
+      divergence_flag = true;
+    }
     else if (a == "--lift-hops") { if (!parse_u64(value(), &lift_hops) || lift_hops < 1 || lift_hops > 65535) die(2, "invalid value for --lift-hops: 1 .. 65535"); }
     else if (a == "--lift-closure") { closure_path = value(); if (closure_path.empty()) die(2, "empty value for --lift-closure"); }
     else if (a == "--lift-closure-summary") { closure_summary_path = value(); if (closure_summary_path.empty()) die(2, "empty value for --lift-closure-summary"); }
@@ -790,6 +845,8 @@ int main(int argc, char** argv) {
                 "         [--ucsc-chain FILE] [--ucsc-chain-from target|query] [--ucsc-chain-set kept|all] [--ucsc-chain-batch BYTES]\n"
                 "         [--diffs FILE] [--diffs-summary FILE] [--diffs-set kept|all] [--diffs-kinds snp,ins,del,skip] [--diffs-min-indel N]\n"
                 "         [--diffs-batch BYTES]\n"
+                "         [--divergence FILE|-] [--divergence-summary FILE|-] [--divergence-window N] [--divergence-axis query|target]\n"
+                "         [--divergence-genome NAME] [--divergence-set kept|all] [--divergence-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
                 "       sweepga-gpu --joblist <in.fa[.gz]>... [--sparsify S] [--mash-kmer-size K] [--mash-sketch-size N]\n"
                 "         [--joblist-output-dir DIR] [--threads T] [--min-aln-length L] [--output-file jobs.txt]\n"
@@ -891,6 +948,17 @@ int main(int argc, char** argv) {
                 "  --diffs-kinds LIST              the kinds that give rows: snp,ins,del,skip (default snp,ins,del)\n"
                 "  --diffs-min-indel N             rows of ins, del and skip from N bases on (default 1; mismatches are never dropped)\n"
                 "  --diffs-batch BYTES             CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
+                "  --divergence FILE   after the filter: one line per window of every sequence that carries an inter-genome mapping of the set --\n"
+                "                      `sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels`, exact\n"
+                "                      from the cg:Z: CIGARs (built on the device), empty windows included; integers only: column identity is\n"
+                "                      matches / aligned, gap-compressed identity matches / (aligned + indels); - = standard error\n"
+                "  --divergence-summary FILE  per sequence `length windows records entries` and the eight sums; records - entries is what the\n"
+                "                      track does not see (a bad CIGAR, no tag)\n"
+                "  --divergence-window N           bases per window; k/m/g suffixes (default 10k)\n"
+                "  --divergence-axis query|target  the sequences the windows lie on (default query)\n"
+                "  --divergence-genome NAME        only the mappings whose other side belongs to this genome (default: any other genome)\n"
+                "  --divergence-set kept|all       the records that are read (default kept)\n"
+                "  --divergence-batch BYTES        CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
                 "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
@@ -936,6 +1004,9 @@ int main(int argc, char** argv) {
   const bool ucsc = !ucsc_path.empty();
   const bool diffs = !diffs_path.empty() || !diffs_summary_path.empty();
   if (!diffs && diffs_flag) die(2, "--diffs-set, --diffs-kinds, --diffs-min-indel and --diffs-batch need --diffs or --diffs-summary");
+  const bool divergence = !divergence_path.empty() || !divergence_summary_path.empty();
+  if (!divergence && divergence_flag)
+    die(2, "--divergence-window, --divergence-axis, --divergence-genome, --divergence-set and --divergence-batch need --divergence or --divergence-summary");
   if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
   if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
   if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
@@ -1027,7 +1098,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1097,6 +1168,10 @@ int main(int argc, char** argv) {
   if (windows && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
     die(3, "--windows: the file has a value >= 2^32, its columns are rebased: the windows of 64-bit columns are not supported");
+  }
+  if (divergence && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
+    gpu_init.join();
+    die(3, "--divergence: the file has a value >= 2^32, its columns are rebased: the divergence of 64-bit columns is not supported");
   }
   if ((!dotplot_path.empty() || !dotplot_layout_path.empty()) && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {  // (likewise)
     gpu_init.join();
@@ -1217,6 +1292,13 @@ int main(int argc, char** argv) {
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_diffs(diffs_path, diffs_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel,
                   diffs_batch, quiet);
+    }
+    if (divergence) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_divergence(divergence_path, divergence_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), divergence_set, divergence_axis,
+                       (uint32_t)divergence_window, divergence_genome, divergence_batch, quiet);
     }
     for (swg_ctx* c : ctxs) swg_destroy(c);
     swg_paf_close(paf);
@@ -1402,6 +1484,13 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_diffs(diffs_path, diffs_summary_path, ctx, paf, status.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel, diffs_batch, quiet);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --diffs: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --divergence / --divergence-summary: likewise, one device call per batch over all records
+  if (divergence) {
+    const auto tb = clk::now();
+    write_divergence(divergence_path, divergence_summary_path, ctx, paf, status.data(), divergence_set, divergence_axis, (uint32_t)divergence_window,
+                     divergence_genome, divergence_batch, quiet);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --divergence: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   const auto t2s = clk::now();
 

@@ -4,7 +4,8 @@
 // holds the rules.
 //
 //   diffs_letters  one thread per 16-byte chunk of the text: from chunk_rank[chunk] on, a kind byte at the rank of every byte that is
-//                  no digit (the prefix sums cannot tell M from X, or D from N).  Every byte has one writer.
+//                  no digit (the prefix sums cannot tell M from X, or D from N).  Every byte has one writer.  The body is
+//                  swg_diffs_letters.h's, which the divergence track (swg_divergence.hip) calls too.
 //   diffs_entries  one thread per entry: usable or not (state 0, record in the set), the ids checked, the entry's genome pair into
 //                  entry_key[] (EMPTY: not usable), and its entries / aligned / eq into the genome-pair table.
 //   diffs_ops      a tile of 1,024 ops per work-group, 4 consecutive ones per thread: the tile's first and last op are searched in
@@ -29,6 +30,7 @@
 #include "swg_pair_table.h"
 #include "swg_cigar_build.h"
 #include "swg_diffs_walk.h"
+#include "swg_diffs_letters.h"
 #include "host/host_internal.h"
 
 namespace {
@@ -53,25 +55,7 @@ using SumList = PairList<Q_TOTAL, false>;
 unsigned grid_of(uint64_t items) { return (unsigned)((items + TB - 1) / TB); }
 
 __global__ __launch_bounds__(TB) void diffs_letters_kernel(CigarSet S, int aligned, uint8_t* __restrict__ kind) {
-  const uint64_t chunk = (uint64_t)blockIdx.x * TB + threadIdx.x, p0 = chunk * 16;
-  if (p0 >= S.B) return;
-  unsigned char ch[16];
-  if (aligned && p0 + 16 <= S.B) {
-    const uint4 q = *reinterpret_cast<const uint4*>(S.text + p0);
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) ch[b] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
-  } else {
-#pragma unroll
-    for (int b = 0; b < 16; ++b) ch[b] = p0 + b < S.B ? (unsigned char)S.text[p0 + b] : (unsigned char)'0';  // (a digit: never an op)
-  }
-  uint64_t r = S.chunk_rank[chunk];
-#pragma unroll
-  for (int b = 0; b < 16; ++b) {
-    if (is_digit(ch[b])) continue;
-    if (r < S.ops) kind[r] = (uint8_t)kind_of(ch[b]);  // (always: the ranks are the parse's own count of these bytes)
-    ++r;
-  }
+  letters_of_chunk(S, aligned, (uint64_t)blockIdx.x * TB + threadIdx.x, kind);
 }
 
 // the sums of one run head into the work-group's table, or past it when its probes found no slot
