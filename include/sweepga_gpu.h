@@ -1737,6 +1737,97 @@ typedef struct swg_divergence_counts {
 int swg_paf_divergence(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t axis, uint32_t window,
                        const char* other_genome, uint64_t batch_bytes, char** out_text, uint64_t* out_len, swg_divergence_counts* counts);
 
+/* ---- variants: SNVs, insertions and deletions with their bases, from the CIGARs and the sequences (no reference counterpart;
+ * DESIGN.md section 34) ----
+ * The CIGAR set, the walk offsets x / y and the entry states are those of the base-exact lift; kinds and the query interval on '-'
+ * are those of the differences.  Integers and bytes only.
+ * SEQUENCES: n_seq (= rec->n_seq), offset[n_seq + 1] and bases (as read).  Sequence s is PRESENT when offset[s + 1] > offset[s]; the
+ * difference is its length.  norm(b): A, C, G, T for those letters in either case, N for every other byte; comp swaps A/T and C/G
+ * and keeps N.
+ * An entry is USABLE when its state is 0, its record is in `set`, the target's genome is t_genome or t_genome is SWG_VARIANTS_ANY
+ * (likewise q_genome), both sequences are present, and t_end <= len(t), q_end <= len(q).  One that fails the presence test (and no
+ * earlier one) counts as no_sequence, one that fails the bounds test (and no earlier one) as out_of_sequence.
+ * QUERY COLUMN at walk offset x: norm(Q[q_start + x]) on '+', comp(norm(Q[q_end - 1 - x])) on '-'.
+ * Per op of a usable entry with length l > 0, p = t_start + y:
+ *   X, M  column by column, b in 0 .. l - 1: r = norm(T[p + b]), a = the query column at x + b.  r or a is N: n_columns.  r == a:
+ *         `same` under X, m_equal under M.  Else an SNV: pos = p + b, REF r, ALT a, q_pos = the column's forward-strand query
+ *         coordinate, sub[r][a] + 1.  Runs are split per base: there are no MNPs.
+ *   I     ins = the l query columns from x on (text order: reverse-complemented on '-').  p > 0: pos = p - 1, REF T[p - 1], ALT
+ *         T[p - 1] + ins.  p == 0: pos = 0, REF T[0], ALT ins + T[0] (the VCF rule at a contig's first base).
+ *   D     p > 0: pos = p - 1, REF T[p - 1 .. p + l), ALT T[p - 1].  p == 0 and l < len(t): pos = 0, REF T[0 .. l] (l + 1 bases), ALT
+ *         T[l].  p == 0 and l == len(t): UNANCHORED, counted, no variant.
+ *   An I or D that is not unanchored with l > max_indel (max_indel != 0) counts as long_indels and gives no variant.  Allele bytes go
+ *   through norm; N may stand in an indel allele.  N, =, S, H, P and ops of length 0 give nothing.
+ * A VARIANT is 32 bytes; q_pos of an indel is the start of the op's query interval; its ref_len + alt_len allele bytes lie in the
+ * POOL at allele_offset, REF first.  Variants come in (entry, op, column) order; the pool offsets are the exclusive sum of ref_len +
+ * alt_len in that order.
+ * SUMMARY per ordered genome pair over the usable entries; only long_indels depends on max_indel.  compared = snvs + same + m_equal
+ * + n_columns (the columns under X and M), snvs = the sum of sub; n_ins .. del_bases count every I / D of length > 0.  Pairs ascend
+ * by (q_genome, t_genome).
+ * Capacity protocol: variants AND pool are written only when n_variants <= variant_capacity, pool_bytes <= pool_capacity and both
+ * arrays are non-NULL (else they are counted and not built); pairs when n_pairs <= pair_capacity; the counts whenever the call
+ * succeeds.  Refusals: those of swg_diff_records (the set, SWG_IV_KEPT without status, a NULL seq_genome or column, bad ids,
+ * reserved != 0); a NULL seqs, offset or bases, or seqs->n_seq != rec->n_seq, with k > 0; offsets that descend; t_genome or q_genome
+ * >= n_genome and not SWG_VARIANTS_ANY: SWG_ERR_INVALID.  2^32 text bytes, 2^32 candidates (the columns under X and M plus one per
+ * indel with a variant: no range loop is built), 2^31 variants or 2^32 pool bytes or more: SWG_ERR_RANGE.  k == 0 needs no device.
+ * Scratch from the arena: the build's plus, per op, 1 + 16 bytes (kind, candidates and their scan); per entry 8; per candidate 1
+ * (its flag); per variant 4 + 8, and 32 plus its allele bytes when variants and pool are built; the genome-pair table (176 bytes
+ * per slot, 184 per listed pair); the host seam stages 26 bytes per record, 12 per sequence and every base. */
+#define SWG_VARIANTS_ANY 0xffffffffu
+#define SWG_VARIANT_SNP 1u
+#define SWG_VARIANT_INS 2u
+#define SWG_VARIANT_DEL 4u
+#define SWG_VARIANT_MINUS 256u /* swg_variant.kind_flags bit 8: the record is on the '-' strand; bits 0 .. 7: the kind */
+typedef struct swg_seq_set {
+  const uint64_t* offset; /* [n_seq + 1], non-decreasing: sequence s is bases[offset[s] .. offset[s + 1]) */
+  const uint8_t* bases;   /* offset[n_seq] bytes, as read */
+  uint32_t n_seq;         /* = rec->n_seq */
+  uint32_t reserved;      /* 0 */
+} swg_seq_set; /* 24 bytes */
+typedef struct swg_variant {
+  uint32_t record, kind_flags;
+  uint32_t pos;              /* 0-based on the target */
+  uint32_t ref_len, alt_len;
+  uint32_t q_pos;            /* 0-based on the query's forward strand */
+  uint64_t allele_offset;    /* into the pool: ref_len bytes of REF, then alt_len of ALT */
+} swg_variant; /* 32 bytes, no implicit padding */
+typedef struct swg_variant_pair {
+  uint32_t q_genome, t_genome;
+  uint64_t entries, compared, snvs;
+  uint64_t sub[12];          /* REF>ALT: A>C A>G A>T C>A C>G C>T G>A G>C G>T T>A T>C T>G */
+  uint64_t same, m_equal, n_columns;
+  uint64_t n_ins, ins_bases, n_del, del_bases;
+  uint64_t long_indels, unanchored;
+} swg_variant_pair; /* 200 bytes, no implicit padding */
+typedef struct swg_variant_request {
+  uint32_t set;                /* in: SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t t_genome, q_genome; /* in: a genome id or SWG_VARIANTS_ANY */
+  uint32_t max_indel;          /* in: 0 = no limit */
+  uint64_t reserved;           /* in: 0 */
+  uint64_t variant_capacity;   /* in: entries `variants` can hold */
+  swg_variant* variants;       /* in: caller-owned or NULL */
+  uint64_t pool_capacity;      /* in: bytes `pool` can hold */
+  uint8_t* pool;               /* in: caller-owned or NULL */
+  uint64_t pair_capacity;
+  swg_variant_pair* pairs;     /* written only when n_pairs <= pair_capacity */
+  uint64_t n_variants;         /* out */
+  uint64_t pool_bytes;         /* out */
+  uint64_t n_pairs;            /* out */
+  uint64_t ops;                /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;          /* out: entries with a state bit of 1 .. 8 */
+  uint64_t usable;             /* out: usable entries */
+  uint64_t no_sequence;        /* out */
+  uint64_t out_of_sequence;    /* out */
+  uint64_t columns;            /* out: columns compared (the sum of `compared`) */
+} swg_variant_request; /* 144 bytes, no implicit padding */
+/* Everything on the host.  seq_genome: [rec->n_seq]. */
+int swg_variant_records(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                        const swg_cigar_set* cigars, const swg_seq_set* seqs, swg_variant_request* req);
+/* Columns, strand, seq_genome, status, the three arrays of the set, seqs->offset and seqs->bases in device memory of ctx's GPU; the
+ * two set structures, the request and its arrays on the host. */
+int swg_variant_records_device(swg_ctx* ctx, const swg_records* rec, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                               const swg_cigar_set* cigars, const swg_seq_set* seqs, swg_variant_request* req);
+
 /* ---- ANI pre-pass for "aniN" identity thresholds (src/main.rs:296-688, src/cli.rs:76-130) -------------------
  * calculate_ani_stats: median over genome pairs (last-'#' prefixes, unordered) of Σmatches / Σblock_len, over
  *   SWG_ANI_ALL         every inter-genome line                                   main.rs:339-342, 392-498
@@ -1785,6 +1876,51 @@ int swg_fasta_file_index(const swg_fasta* f, uint64_t i);      /* which of the p
 const uint64_t* swg_fasta_offsets(const swg_fasta* f);         /* [n + 1]: record i = bases[offsets[i], offsets[i + 1]) */
 const uint8_t* swg_fasta_bases(const swg_fasta* f);            /* every record's bytes, as read (case kept) */
 const char* swg_fasta_last_error(void);
+
+/* ---- --vcf: the variant calls of an open PAF against FASTA records, as VCF 4.2 ----
+ * The handle's sequence names are matched to swg_fasta_name by exact name (of two FASTA records with one name the first); a PAF
+ * sequence without a FASTA record is absent, and so is one whose PAF length (on the line that mentions it last) differs from the
+ * FASTA record's: that one counts as length_mismatch, once per sequence.  The records of `set` with the LAST cg:Z: tag of each
+ * one's line as its entry go through swg_variant_records' definitions in batches as swg_paf_ucsc_chain_write cuts them; the bases
+ * of the sequences the set names are sent to the device once per call.  Genomes: the handle's seq_genome_two; ref_genome /
+ * query_genome: a two-part genome prefix with or without its trailing '#', or NULL = any.
+ *   VCF      ##fileformat=VCFv4.2, ##source=sweepga-gpu (no date line), one ##contig=<ID=,length=> per sequence that is the target
+ *            of a usable entry, in sequence-id order, the INFO lines, then CHROM POS(= pos + 1) . REF ALT . . QNAME=;QSTART=;
+ *            QSTRAND=+|-;REC= per variant; ';', '=', ',', '%' and bytes <= 0x20 of QNAME are percent-encoded.  With a query_genome
+ *            also ##FORMAT=<ID=GT,...>, one sample column named as that genome, and GT 1 on every line.  The lines are ordered by
+ *            (target sequence id, pos) with one stable device sort, ties in (record, op, column) order: sorted per contig, and the
+ *            same bytes for every batch_bytes.
+ *   summary  a header, then per genome pair, (query genome, target genome) ascending, the sums of swg_variant_pair and ts, tv
+ * A PAF without records of the set gives empty outputs and needs no device (ctx may be NULL).  Every refusal comes before a file
+ * is opened: set > 1, SWG_IV_KEPT without status, reserved != 0, a NULL fasta or opts, an unknown genome name: SWG_ERR_INVALID; a
+ * handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  counts may be NULL.  Errors: swg_alnstats_last_error(). */
+typedef struct swg_vcf_options {
+  uint32_t set;             /* SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t max_indel;       /* 0 = no limit */
+  const char* ref_genome;   /* the target's genome, or NULL = any */
+  const char* query_genome; /* the query's genome, or NULL = any */
+  uint64_t batch_bytes;     /* CIGAR text per device call; 0 = a default from the device's memory */
+  uint64_t reserved;        /* 0 */
+} swg_vcf_options; /* 40 bytes */
+typedef struct swg_vcf_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t usable;   /* usable entries */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t untagged; /* records without a cg:Z: tag */
+  uint64_t variants;
+  uint64_t snvs, n_ins, n_del; /* over the usable entries, as the summary */
+  uint64_t same, n_columns, m_equal;
+  uint64_t long_indels, unanchored;
+  uint64_t no_sequence, out_of_sequence; /* entries */
+  uint64_t length_mismatch;              /* sequences */
+  uint64_t batches;                      /* device calls */
+} swg_vcf_counts; /* 136 bytes */
+/* Either path may be NULL (not both); without vcf_path the variants are counted and not built. */
+int swg_paf_vcf_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_vcf_options* opts,
+                      const char* vcf_path, const char* summary_path, swg_vcf_counts* counts);
+/* The same as malloc'd texts (release each with swg_free); vcf_text or summary_text may be NULL (not both). */
+int swg_paf_vcf_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_vcf_options* opts,
+                     swg_vcf_counts* counts, char** vcf_text, uint64_t* vcf_len, char** summary_text, uint64_t* summary_len);
 /* Per contig, the bottom-s MULTISET of min(SipHash-1-3(le64(k) || window), SipHash-1-3(le64(k) || revcomp upper-cased))
  * over the windows of k bytes all in ACGTacgt, ascending (KmerSketch::from_sequence, mash.rs:78-131).  Contig i =
  * seq[offsets[i], offsets[i + 1]); counts_out[n_seq]; minimizers_out[n_seq * s], row i holds counts_out[i] values.  The

@@ -51,7 +51,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_gaps_records", "swg_gaps_records_device", "swg_paf_gaps",
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
            "swg_windows_records", "swg_windows_records_device", "swg_paf_windows",
-           "swg_divergence_records", "swg_divergence_records_device", "swg_paf_divergence"]
+           "swg_divergence_records", "swg_divergence_records_device", "swg_paf_divergence",
+           "swg_variant_records", "swg_variant_records_device", "swg_paf_vcf_write", "swg_paf_vcf_text"]
 
 
 class SwgError(RuntimeError):
@@ -375,6 +376,36 @@ class SwgDiffCounts(C.Structure):
                                           "del_bases", "n_skip", "skip_bases", "m_columns", "batches")]
 
 
+VARIANT_SUBS = tuple(f"{r}>{a}" for r in "ACGT" for a in "ACGT" if r != a)
+VARIANT_SUMS = ("entries", "compared", "snvs") + VARIANT_SUBS + ("same", "m_equal", "n_columns", "n_ins", "ins_bases", "n_del", "del_bases", "long_indels",
+                                                               "unanchored")
+
+
+class SwgSeqSet(C.Structure):
+    _fields_ = [("offset", C.c_void_p), ("bases", C.c_void_p), ("n_seq", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SwgVariantRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("t_genome", C.c_uint32), ("q_genome", C.c_uint32), ("max_indel", C.c_uint32), ("reserved", C.c_uint64),
+                ("variant_capacity", C.c_uint64), ("variants", C.c_void_p), ("pool_capacity", C.c_uint64), ("pool", C.c_void_p),
+                ("pair_capacity", C.c_uint64), ("pairs", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in ("n_variants", "pool_bytes", "n_pairs", "ops", "cigar_bad", "usable", "no_sequence", "out_of_sequence",
+                                           "columns")]
+
+
+class SwgVcfOptions(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("max_indel", C.c_uint32), ("ref_genome", C.c_char_p), ("query_genome", C.c_char_p), ("batch_bytes", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+VCF_COUNTS = ("records", "usable", "bad", "untagged", "variants", "snvs", "n_ins", "n_del", "same", "n_columns", "m_equal", "long_indels", "unanchored",
+              "no_sequence", "out_of_sequence", "length_mismatch", "batches")
+
+
+class SwgVcfCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VCF_COUNTS]
+
+
 class SwgClosureRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")]
 
@@ -663,6 +694,19 @@ def load():
     lib.swg_paf_diffs_text.restype = C.c_int
     lib.swg_paf_diffs_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SwgDiffCounts),
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_variant_records", "swg_variant_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SwgCigarSet), C.POINTER(SwgSeqSet),
+                      C.POINTER(SwgVariantRequest)]
+    lib.swg_fasta_open.restype, lib.swg_fasta_open.argtypes = C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.swg_fasta_close.restype, lib.swg_fasta_close.argtypes = None, [C.c_void_p]
+    lib.swg_fasta_last_error.restype, lib.swg_fasta_last_error.argtypes = C.c_char_p, []
+    lib.swg_paf_vcf_write.restype = C.c_int
+    lib.swg_paf_vcf_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgVcfOptions), C.c_char_p, C.c_char_p, C.POINTER(SwgVcfCounts)]
+    lib.swg_paf_vcf_text.restype = C.c_int
+    lib.swg_paf_vcf_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgVcfOptions), C.POINTER(SwgVcfCounts),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_divergence_records", "swg_divergence_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

@@ -153,6 +153,21 @@ struct swg_ucsc_sink {
 };
 // one batch into the sink: for every row with blocks its header (hdr[j]) and its block lines out of the device's text
 void swg_ucsc_splice(swg_ucsc_sink* sink, const swg_ucsc_chain* rows, uint64_t k, const std::string* hdr, const char* text, uint64_t text_bytes);
+// ---- variants (swg_variants.hip: kernels and record seams) ----
+// where: 0 = everything on the host, 1 = on the device, 2 = the host's with seqs->bases in device memory; entry_usable: host [k] or NULL
+int swg_variant_run(swg_ctx* ctx, const swg_records* rec, int where, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
+                    const swg_cigar_set* cigars, const swg_seq_set* seqs, swg_variant_request* req, uint8_t* entry_usable);
+// the bases of the sequences a PAF call names in a device block of their own (src[s] NULL: absent), and its release
+int swg_variant_bases_upload(swg_ctx* ctx, const uint8_t* const* src, const uint64_t* len, uint32_t n_seq, uint64_t* offset, uint8_t** d_bases);
+void swg_variant_bases_free(swg_ctx* ctx, uint8_t* d_bases);
+// order[i] = the index of the i-th variant by the key's low `bits` bits, ties in index order (one stable device sort)
+int swg_variant_order(swg_ctx* ctx, const uint64_t* keys, uint64_t n, int bits, uint32_t* order);
+// variants_text.cpp: the formatters and the merge of swg_paf_vcf_write, which need neither a handle nor a device
+void swg_vcf_escape(std::string& o, const char* s);
+void swg_vcf_header_text(std::string& o, const std::vector<std::string>& contig_name, const std::vector<uint64_t>& contig_len, const char* sample);
+void swg_vcf_line_text(std::string& o, const char* t_name, const char* q_name, const swg_variant& v, const uint8_t* alleles, bool genotype);
+void swg_variants_merge_pairs(std::vector<swg_variant_pair>* total, const swg_variant_pair* add, uint64_t n);
+std::string swg_variants_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_variant_pair>& pairs);
 // ---- differences (swg_diffs.hip: kernels and record seams; diffs_text.cpp: the two PAF seams) ----
 int swg_diff_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
                  const swg_cigar_set* cigars, swg_diff_request* req);

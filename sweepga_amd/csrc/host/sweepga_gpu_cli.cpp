@@ -432,6 +432,27 @@ void write_diffs(const std::string& rows_path, const std::string& summary_path, 
                  (unsigned long long)(c.del_bases + c.skip_bases), (unsigned long long)c.m_columns, (unsigned long long)c.bad, (unsigned long long)c.untagged);
 }
 
+// --vcf / --vcf-summary: the variant calls of swg_paf_vcf_write -- SNVs, insertions and deletions of the set's cg:Z: CIGARs with their
+// bases from the FASTA records, as VCF 4.2 (built on the device) -- and their sums per genome pair; either path may be empty.  What it
+// met goes to standard error in one line.  (The genome names were checked when the PAF was opened.)
+void write_vcf(const std::string& vcf_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const swg_fasta* fasta,
+               uint32_t set, const std::string& ref, const std::string& query, uint32_t max_indel, uint64_t batch, bool quiet) {
+  swg_vcf_options o{};
+  o.set = set, o.max_indel = max_indel, o.batch_bytes = batch;
+  o.ref_genome = ref.empty() ? nullptr : ref.c_str(), o.query_genome = query.empty() ? nullptr : query.c_str();
+  swg_vcf_counts c;
+  if (swg_paf_vcf_write(ctx, paf, status, fasta, &o, vcf_path.empty() ? nullptr : vcf_path.c_str(), summary_path.empty() ? nullptr : summary_path.c_str(),
+                        &c) != SWG_OK)
+    die(3, std::string("--vcf: ") + swg_alnstats_last_error());
+  if (!quiet)
+    std::fprintf(stderr, "[sweepga-gpu] --vcf: %llu variants (%llu SNVs, %llu insertions, %llu deletions), %llu same, %llu N columns, %llu equal under M ops, "
+                 "%llu long, %llu unanchored, %llu entries without sequence, %llu out of sequence, %llu bad, %llu without a cg:Z: tag\n",
+                 (unsigned long long)c.variants, (unsigned long long)c.snvs, (unsigned long long)c.n_ins,
+                 (unsigned long long)c.n_del, (unsigned long long)c.same, (unsigned long long)c.n_columns, (unsigned long long)c.m_equal,
+                 (unsigned long long)c.long_indels, (unsigned long long)c.unanchored, (unsigned long long)c.no_sequence, (unsigned long long)c.out_of_sequence,
+                 (unsigned long long)c.bad, (unsigned long long)c.untagged);
+}
+
 // --divergence / --divergence-summary: the two texts of swg_paf_divergence (exact matches, mismatches and indels per fixed window,
 // from the set's cg:Z: CIGARs, built on the device).  "-" = standard error.  What it met goes to standard error in one line.
 void write_divergence(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set,
@@ -535,6 +556,11 @@ int main(int argc, char** argv) {
   uint32_t diffs_set = SWG_IV_KEPT, diffs_kinds = SWG_DIFF_SNP | SWG_DIFF_INS | SWG_DIFF_DEL;
   uint64_t diffs_min_indel = 1, diffs_batch = 0;  // --diffs-min-indel; --diffs-batch: 0 = the library's default
   bool diffs_flag = false;  // (one of --diffs-set / --diffs-kinds / --diffs-min-indel / --diffs-batch was given)
+  std::string vcf_path, vcf_summary_path, vcf_ref, vcf_query;  // --vcf, --vcf-summary, --vcf-ref, --vcf-query: empty = not given
+  std::vector<std::string> vcf_fasta_paths;                    // --vcf-fasta, once per file
+  uint32_t vcf_set = SWG_IV_KEPT;
+  uint64_t vcf_max_indel = 10000, vcf_batch = 0;  // --vcf-max-indel: 0 = no limit; --vcf-batch: 0 = the library's default
+  bool vcf_flag = false;  // (a sub-option of --vcf was given)
   std::string divergence_path, divergence_summary_path, divergence_genome;  // --divergence, --divergence-summary: empty = no file; -genome: empty = any
   uint32_t divergence_set = SWG_IV_KEPT, divergence_axis = 0;
   uint64_t divergence_window = 10000, divergence_batch = 0;  // --divergence-window; --divergence-batch: 0 = the library's default
@@ -664,6 +690,38 @@ int main(int argc, char** argv) {
       path = value();
       if (path.empty()) die(2, "empty value for " + a);
       if (path == "-") die(2, a + " needs a file: the difference list is not a standard error report");
+    }
+    else if (a == "--vcf" || a == "--vcf-summary") {
+      std::string& path = a == "--vcf" ? vcf_path : vcf_summary_path;
+      path = value();
+      if (path.empty()) die(2, "empty value for " + a);
+      if (path == "-") die(2, a + " needs a file: the variant calls are not a standard error report");
+    }
+    else if (a == "--vcf-fasta") {
+      vcf_fasta_paths.push_back(value());
+      if (vcf_fasta_paths.back().empty() || vcf_fasta_paths.back() == "-") die(2, "--vcf-fasta needs a file");
+      vcf_flag = true;
+    }
+    else if (a == "--vcf-ref" || a == "--vcf-query") {
+      std::string& name = a == "--vcf-ref" ? vcf_ref : vcf_query;
+      name = value();
+      if (name.empty()) die(2, "empty value for " + a);
+      vcf_flag = true;
+    }
+    else if (a == "--vcf-set") {
+      const std::string v = value();
+      if (v == "kept") vcf_set = SWG_IV_KEPT;
+      else if (v == "all") vcf_set = SWG_IV_ALL;
+      else die(2, "invalid value for --vcf-set: kept or all");
+      vcf_flag = true;
+    }
+    else if (a == "--vcf-max-indel") {
+      if (!parse_metric_number(value(), &vcf_max_indel) || vcf_max_indel > 0xffffffffull) die(2, "invalid value for --vcf-max-indel: 0 .. 2^32 - 1");
+      vcf_flag = true;
+    }
+    else if (a == "--vcf-batch") {
+      if (!parse_metric_number(value(), &vcf_batch) || vcf_batch == 0) die(2, "invalid value for --vcf-batch: 1 or more bytes");
+      vcf_flag = true;
     }
     else if (a == "--diffs-set") {
       const std::string v = value();
@@ -845,6 +903,8 @@ int main(int argc, char** argv) {
                 "         [--ucsc-chain FILE] [--ucsc-chain-from target|query] [--ucsc-chain-set kept|all] [--ucsc-chain-batch BYTES]\n"
                 "         [--diffs FILE] [--diffs-summary FILE] [--diffs-set kept|all] [--diffs-kinds snp,ins,del,skip] [--diffs-min-indel N]\n"
                 "         [--diffs-batch BYTES]\n"
+                "         [--vcf FILE] [--vcf-summary FILE] --vcf-fasta FASTA [--vcf-fasta FASTA ...] [--vcf-ref GENOME] [--vcf-query GENOME]\n"
+                "         [--vcf-set kept|all] [--vcf-max-indel N] [--vcf-batch BYTES]\n"
                 "         [--divergence FILE|-] [--divergence-summary FILE|-] [--divergence-window N] [--divergence-axis query|target]\n"
                 "         [--divergence-genome NAME] [--divergence-set kept|all] [--divergence-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
@@ -948,6 +1008,15 @@ int main(int argc, char** argv) {
                 "  --diffs-kinds LIST              the kinds that give rows: snp,ins,del,skip (default snp,ins,del)\n"
                 "  --diffs-min-indel N             rows of ins, del and skip from N bases on (default 1; mismatches are never dropped)\n"
                 "  --diffs-batch BYTES             CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
+                "  --vcf FILE          write the variant calls of the cg:Z: CIGARs as VCF 4.2: one line per differing base under an X or M op and\n"
+                "                      per insertion or deletion, with its bases from the FASTA records (built on the device); sorted per contig\n"
+                "  --vcf-summary FILE  per genome pair the compared columns, the 12 substitution counts, insertions, deletions, ts and tv\n"
+                "  --vcf-fasta FASTA               the sequences, matched to the PAF's names by exact name; once per file (needed)\n"
+                "  --vcf-ref GENOME                only mappings whose target is of this genome (default any)\n"
+                "  --vcf-query GENOME              only mappings whose query is of this genome; it names the sample column (default any, no sample)\n"
+                "  --vcf-set kept|all              the records that are read (default kept)\n"
+                "  --vcf-max-indel N               insertions and deletions up to N bases (default 10000; 0 = no limit)\n"
+                "  --vcf-batch BYTES               CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --divergence FILE   after the filter: one line per window of every sequence that carries an inter-genome mapping of the set --\n"
                 "                      `sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels`, exact\n"
                 "                      from the cg:Z: CIGARs (built on the device), empty windows included; integers only: column identity is\n"
@@ -1004,6 +1073,15 @@ int main(int argc, char** argv) {
   const bool ucsc = !ucsc_path.empty();
   const bool diffs = !diffs_path.empty() || !diffs_summary_path.empty();
   if (!diffs && diffs_flag) die(2, "--diffs-set, --diffs-kinds, --diffs-min-indel and --diffs-batch need --diffs or --diffs-summary");
+  const bool vcf = !vcf_path.empty() || !vcf_summary_path.empty();
+  if (!vcf && vcf_flag) die(2, "--vcf-fasta, --vcf-ref, --vcf-query, --vcf-set, --vcf-max-indel and --vcf-batch need --vcf or --vcf-summary");
+  if (vcf && vcf_fasta_paths.empty()) die(2, "--vcf and --vcf-summary need --vcf-fasta: the bases are not in a PAF");
+  swg_fasta* vcf_fasta = nullptr;
+  if (vcf) {  // read now: an unreadable FASTA is a usage error, found before anything is begun
+    std::vector<const char*> paths;
+    for (const std::string& f : vcf_fasta_paths) paths.push_back(f.c_str());
+    if (swg_fasta_open(paths.data(), (int)paths.size(), threads, &vcf_fasta) != SWG_OK) die(2, std::string("--vcf-fasta: ") + swg_fasta_last_error());
+  }
   const bool divergence = !divergence_path.empty() || !divergence_summary_path.empty();
   if (!divergence && divergence_flag)
     die(2, "--divergence-window, --divergence-axis, --divergence-genome, --divergence-set and --divergence-batch need --divergence or --divergence-summary");
@@ -1098,7 +1176,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence && !vcf)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1139,6 +1217,22 @@ int main(int argc, char** argv) {
     const std::string msg = swg_paf_last_error();
     gpu_init.join();
     die(2, msg);
+  }
+  // --vcf-ref / --vcf-query name genomes of this file: an unknown name is a usage error, found before the filter runs and before any
+  // report is written
+  if (vcf && swg_paf_records(paf)->n) {
+    for (const std::string* name : {&vcf_ref, &vcf_query}) {
+      if (name->empty()) continue;
+      bool found = false;
+      for (uint32_t g = 0, G = swg_paf_num_genomes_two(paf); g < G && !found; ++g) {
+        const std::string have = swg_paf_genome_two_prefix(paf, g);
+        found = have == *name || have == *name + "#";
+      }
+      if (!found) {
+        gpu_init.join();
+        die(2, std::string(name == &vcf_ref ? "--vcf-ref" : "--vcf-query") + ": unknown genome '" + *name + "'");
+      }
+    }
   }
   // --breadth reads 32-bit columns (swg_paf_breadth): refused here, not after a whole filter run and ahead of the output
   if (!breadth_path.empty() && (swg_paf_seq_offsets(paf) || swg_paf_record_offsets(paf, 0))) {
@@ -1292,6 +1386,14 @@ int main(int argc, char** argv) {
       const std::vector<uint8_t> every(n ? n : 1, 1);
       write_diffs(diffs_path, diffs_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel,
                   diffs_batch, quiet);
+    }
+    if (vcf) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_vcf(vcf_path, vcf_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), vcf_fasta, vcf_set, vcf_ref, vcf_query, (uint32_t)vcf_max_indel,
+                vcf_batch, quiet);
+      swg_fasta_close(vcf_fasta);
     }
     if (divergence) {  // nothing is dropped: kept = all
       std::fflush(out);
@@ -1484,6 +1586,13 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     write_diffs(diffs_path, diffs_summary_path, ctx, paf, status.data(), diffs_set, diffs_kinds, (uint32_t)diffs_min_indel, diffs_batch, quiet);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --diffs: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --vcf / --vcf-summary: likewise, the bases on the device once, one stable device sort after the last batch
+  if (vcf) {
+    const auto tb = clk::now();
+    write_vcf(vcf_path, vcf_summary_path, ctx, paf, status.data(), vcf_fasta, vcf_set, vcf_ref, vcf_query, (uint32_t)vcf_max_indel, vcf_batch, quiet);
+    swg_fasta_close(vcf_fasta);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --vcf: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --divergence / --divergence-summary: likewise, one device call per batch over all records
   if (divergence) {
