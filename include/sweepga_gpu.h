@@ -1150,6 +1150,96 @@ int swg_paf_ucsc_chain_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* stat
 int swg_paf_ucsc_chain_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, uint32_t set, uint32_t from, uint64_t batch_bytes,
                             swg_ucsc_counts* counts, char** text, uint64_t* len);
 
+/* ---- lift slices: each lifted region as an alignment of its own, with its sliced CIGAR, on the device -------
+ * Hit, clip [ca, cb), the walk offsets x and y, column, entry state and row order are those of the lift and of the base-exact lift
+ * above.  Take an exact row (flag SWG_LIFT_EXACT) with aligned > 0, and let g0 < g1 be the column numbers of its record, in walk
+ * order, so that A = columns g0 .. g1 - 1; x(g), y(g) are the walk offsets of column g.  The SLICE of the row is
+ *   target  [t_start + y(g0), t_start + y(g1 - 1) + 1)
+ *   query   [q_start + x(g0), q_start + x(g1 - 1) + 1) on '+',  [q_end - 1 - x(g1 - 1), q_end - x(g0)) on '-'
+ * On the source axis this lies inside [ca, cb): the clip trimmed to its first and last aligned base; on the other axis it is the
+ * row's dst exactly.  aligned and matches are the row's own; block = (x(g1 - 1) - x(g0) + 1) + (y(g1 - 1) - y(g0) + 1) - aligned in
+ * 64 bits: columns plus inserted plus deleted bases inside the slice.
+ * CIGAR text: with i0, i1 the ops that hold columns g0 and g1 - 1, A the exclusive prefix sum of the columns relative to the record's
+ * first op, and pos[r] the byte of op r's letter in the entry's text: `<g1 - g0><letter i0>` when i0 == i1; otherwise
+ * `<A[i0 + 1] - g0><letter i0>`, then the entry's bytes [pos[i0] + 1, pos[i1 - 1] + 1) verbatim (empty when i1 == i0 + 1; zero-length
+ * ops and S, H, P in between are copied as they stand), then `<g1 - A[i1]><letter i1>`.  The text is never longer than the entry's
+ * own, so text_len fits 32 bits; parsed as the entry of a record with the slice's four coordinates and strand it has state 0.
+ * Flag bit 3 (SWG_SLICE_HAS_EQ): the whole entry has at least one '=' column (then `matches` is a count of matches, else it is 0
+ * and only `aligned` says anything).
+ * Rows without a slice are counted: a row without SWG_LIFT_EXACT as n_interp, an exact row with aligned == 0 as n_empty, an exact row
+ * with 0 < aligned < min_aligned as n_short (min_aligned 0 is 1).  Slices are in the lift's row order; text_first runs over the slices
+ * in that order, their texts end to end without separators.
+ * Capacity protocol of swg_ucsc_chain_records: slices is written when n_slices <= slice_capacity, text when text_bytes <=
+ * text_capacity (each only when non-NULL), state whenever non-NULL, the counts whenever the call succeeds.  Refusals of
+ * swg_lift_exact_records; besides 2^32 rows or more, or 2^32 bytes of slice text or more, in one call: SWG_ERR_RANGE.  m == 0, or no
+ * records, or no entries, needs no device work (every count 0 but for what the set alone gives).  Scratch from the arena on top of
+ * the exact lift's: 4 bytes per op (pos), 81 bytes per row (the row's slice, its copy plan and a flag), 92 bytes per slice (slice,
+ * copy plan, the scanned length, its row), the text itself, and nothing per tile: the text kernel cuts the output into tiles of
+ * SWG_SLICE_TEXT_TILE bytes, one work-group each, which search their first slice themselves. */
+#define SWG_SLICE_HAS_EQ 8u
+#define SWG_SLICE_TEXT_TILE 4096u
+typedef struct swg_lift_slice {
+  uint32_t region, record;
+  uint32_t q_start, q_end;
+  uint32_t t_start, t_end;
+  uint32_t flags;            /* bits 0 and 1 as in swg_lift_row: strand, axis; bit 3: SWG_SLICE_HAS_EQ */
+  uint32_t aligned, matches;
+  uint32_t text_len;
+  uint64_t block;
+  uint64_t text_first;       /* into text */
+} swg_lift_slice; /* 56 bytes */
+typedef struct swg_lift_slice_request {
+  uint32_t set, axes;        /* as in swg_lift_request */
+  uint32_t min_aligned;      /* slices with fewer aligned columns are counted, not written */
+  uint32_t reserved;         /* 0 */
+  uint64_t slice_capacity;   /* in: entries `slices` can hold */
+  swg_lift_slice* slices;    /* in: caller-owned or NULL; written only when n_slices <= slice_capacity */
+  uint64_t text_capacity;
+  char* text;                /* written only when text_bytes <= text_capacity */
+  uint8_t* state;            /* in: caller-owned [k] or NULL; written whenever non-NULL */
+  uint64_t n_rows;           /* out: rows of the lift */
+  uint64_t n_slices;         /* out */
+  uint64_t n_interp;         /* out: rows without SWG_LIFT_EXACT */
+  uint64_t n_empty;          /* out: exact rows without an aligned column */
+  uint64_t n_short;          /* out: exact rows with 0 < aligned < min_aligned */
+  uint64_t text_bytes;       /* out */
+  uint64_t ops;              /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;        /* out: entries with a state bit of 1 .. 8 */
+} swg_lift_slice_request; /* 120 bytes */
+/* Everything on the host. */
+int swg_lift_slice_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                           const swg_cigar_set* cigars, swg_lift_slice_request* req);
+/* Columns, strand, status, regions and the three arrays of the set in device memory of ctx's GPU; the set structure, the request
+ * and its arrays on the host. */
+int swg_lift_slice_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                                  const swg_cigar_set* cigars, swg_lift_slice_request* req);
+/* SWG_SLICE_TEXT_TILE as the library was built with it. */
+uint32_t swg_lift_slice_text_tile(void);
+typedef struct swg_lift_paf_counts {
+  uint64_t rows;     /* rows of the lift over all regions */
+  uint64_t slices;   /* lines written */
+  uint64_t interp;   /* rows whose record has no usable CIGAR */
+  uint64_t empty;    /* exact rows without an aligned column */
+  uint64_t too_short; /* exact rows below min_aligned */
+  uint64_t hits;     /* entries uploaded, summed over the batches (a record hit from two batches counts twice) */
+  uint64_t bad;      /* of those, entries with a state bit of 1 .. 8 */
+  uint64_t batches;  /* slice calls */
+} swg_lift_paf_counts; /* 64 bytes */
+/* Each slice of BED regions lifted through an open PAF as one PAF line, in slice order: BED parser and refusals of swg_paf_lift,
+ * the entries are the LAST cg:Z: tag of each hit record's line as in swg_paf_lift_exact.  Tab-separated:
+ *   q_name q_len q_start q_end strand t_name t_len t_start t_end col10 block mapq cg:Z:<text> rn:Z:<label> ri:i:<record>
+ * col10 = matches when bit 3 is set, else aligned; q_len, t_len and mapq are copied from the record's own line; names from the
+ * handle.  One plain lift gives the hits per region; the BED is then cut into batches of consecutive regions whose cost, the sum
+ * over their hits of (cg length + 24), stays within batch_bytes (0: the default of swg_paf_ucsc_chain_write; a region above the batch
+ * is a batch of its own; one region of 2^32 or more is SWG_ERR_RANGE).  Each batch is one hit list and one slice call; a record hit
+ * from two batches is uploaded twice.  The output is the same bytes for every batch_bytes.  counts may be NULL.  An empty BED or a
+ * PAF without records gives an empty file and needs no device (ctx may be NULL).  Errors: swg_alnstats_last_error(). */
+int swg_paf_lift_paf_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                           uint32_t min_aligned, uint64_t batch_bytes, const char* out_path, swg_lift_paf_counts* counts);
+/* The same as one malloc'd text (release with swg_free). */
+int swg_paf_lift_paf_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
+                          uint32_t min_aligned, uint64_t batch_bytes, swg_lift_paf_counts* counts, char** text, uint64_t* len);
+
 /* ---- differences: every mismatch run, insertion and deletion of the CIGARs, on the device -------------------
  * The CIGAR set, the walk offsets x / y and the entry states 1 .. 16 are those of the base-exact lift above.  An entry is USABLE when
  * its state is 0 and its record is in `set` (SWG_IV_ALL, or SWG_IV_KEPT: status != 0).  Each op of a usable entry with letter c and

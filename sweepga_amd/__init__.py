@@ -23,6 +23,7 @@ from .windows import Windows, WindowsResult, windows_records, windows_records_de
 from .dotplot import Dotplot, DotplotResult, dotplot_records, dotplot_records_device  # noqa: F401
 from .lift import Lift, LiftClosure, LiftClosureResult, LiftResult, lift_closure_records, lift_closure_records_device, lift_records, lift_records_device  # noqa: F401
 from .lift import LiftExactResult, lift_exact_records, lift_exact_records_device, lift_hit_records, lift_hit_records_device  # noqa: F401
+from .lift import LiftPaf, LiftSliceResult, lift_slice_records, lift_slice_records_device  # noqa: F401  (its SLICE_DTYPE: sweepga_amd.lift)
 from .ucsc import UcscChain, UcscResult, ucsc_chain_records, ucsc_chain_records_device  # noqa: F401  (its CHAIN_DTYPE / BLOCK_DTYPE: sweepga_amd.ucsc)
 from .diffs import Diffs, DiffsResult, diff_records, diff_records_device  # noqa: F401  (its ROW_DTYPE / PAIR_DTYPE: sweepga_amd.diffs)
 from .divergence import Divergence, DivergenceResult, divergence_records, divergence_records_device  # noqa: F401  (its ROW_DTYPE / SEQ_DTYPE: sweepga_amd.divergence)

@@ -45,6 +45,7 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_lift_closure_records", "swg_lift_closure_records_device", "swg_paf_lift_closure",
            "swg_lift_exact_records", "swg_lift_exact_records_device", "swg_lift_hit_records", "swg_lift_hit_records_device",
            "swg_paf_lift_exact", "swg_paf_lift_exact_counts",
+           "swg_lift_slice_records", "swg_lift_slice_records_device", "swg_lift_slice_text_tile", "swg_paf_lift_paf_write", "swg_paf_lift_paf_text",
            "swg_ucsc_chain_records", "swg_ucsc_chain_records_device", "swg_paf_ucsc_chain_write", "swg_paf_ucsc_chain_text",
            "swg_diff_records", "swg_diff_records_device", "swg_paf_diffs_write", "swg_paf_diffs_text",
            "swg_mosaic_records", "swg_mosaic_records_device", "swg_paf_mosaic",
@@ -312,6 +313,21 @@ class SwgLiftExactRequest(C.Structure):
     _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("n", C.c_uint64), ("candidates", C.c_uint64 * 2), ("capacity", C.c_uint64),
                 ("rows", C.c_void_p), ("summary", C.c_void_p), ("state", C.c_void_p), ("ops", C.c_uint64), ("cigar_bad", C.c_uint64),
                 ("exact_rows", C.c_uint64)]
+
+
+class SwgLiftSlice(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("region", "record", "q_start", "q_end", "t_start", "t_end", "flags", "aligned", "matches", "text_len")]
+    _fields_ += [("block", C.c_uint64), ("text_first", C.c_uint64)]
+
+
+class SwgLiftSliceRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("axes", C.c_uint32), ("min_aligned", C.c_uint32), ("reserved", C.c_uint32), ("slice_capacity", C.c_uint64),
+                ("slices", C.c_void_p), ("text_capacity", C.c_uint64), ("text", C.c_void_p), ("state", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in ("n_rows", "n_slices", "n_interp", "n_empty", "n_short", "text_bytes", "ops", "cigar_bad")]
+
+
+class SwgLiftPafCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("rows", "slices", "interp", "empty", "too_short", "hits", "bad", "batches")]
 
 
 class SwgUcscBlock(C.Structure):
@@ -675,6 +691,18 @@ def load():
     lib.swg_paf_lift_exact.argtypes = lib.swg_paf_lift.argtypes
     lib.swg_paf_lift_exact_counts.restype = None
     lib.swg_paf_lift_exact_counts.argtypes = [C.POINTER(C.c_uint64)]
+    for name in ("swg_lift_slice_records", "swg_lift_slice_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SwgCigarSet), C.POINTER(SwgLiftSliceRequest)]
+    lib.swg_lift_slice_text_tile.restype = C.c_uint32
+    lib.swg_lift_slice_text_tile.argtypes = []
+    lib.swg_paf_lift_paf_write.restype = C.c_int
+    lib.swg_paf_lift_paf_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_char_p, C.POINTER(SwgLiftPafCounts)]
+    lib.swg_paf_lift_paf_text.restype = C.c_int
+    lib.swg_paf_lift_paf_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                          C.POINTER(SwgLiftPafCounts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for name in ("swg_ucsc_chain_records", "swg_ucsc_chain_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

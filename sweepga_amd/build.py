@@ -13,6 +13,7 @@ SOURCES = ["swg_context.hip", "swg_sort.hip", "swg_sweep.hip", "swg_filter.hip",
            "swg_mash.hip", "swg_alnstats.hip", "swg_sparsify.hip", "swg_breadth.hip", "swg_blocks.hip", "swg_components.hip", "swg_intervals.hip", "swg_sharing.hip", "swg_dotplot.hip", "swg_lift.hip", "swg_lift_closure.hip", os.path.join("host", "lift_text.cpp"),
            "swg_cigar.hip", os.path.join("host", "cigar_text.cpp"),
            "swg_ucsc.hip", os.path.join("host", "ucsc_text.cpp"),
+           "swg_slice.hip", os.path.join("host", "slice_text.cpp"),
            "swg_diffs.hip", os.path.join("host", "diffs_text.cpp"),
            "swg_divergence.hip", os.path.join("host", "divergence_text.cpp"),
            "swg_variants.hip", os.path.join("host", "variants_text.cpp"),

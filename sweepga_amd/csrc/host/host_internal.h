@@ -153,6 +153,20 @@ struct swg_ucsc_sink {
 };
 // one batch into the sink: for every row with blocks its header (hdr[j]) and its block lines out of the device's text
 void swg_ucsc_splice(swg_ucsc_sink* sink, const swg_ucsc_chain* rows, uint64_t k, const std::string* hdr, const char* text, uint64_t text_bytes);
+// ---- lift slices (swg_slice.hip: kernels and record seams; slice_text.cpp: the two PAF seams) ----
+int swg_lift_slice_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint8_t* status, const swg_lift_region* regions, uint64_t m,
+                       const swg_cigar_set* cigars, swg_lift_slice_request* req);
+// The regions of a BED text in line order under the rules of swg_paf_lift, with each one's label (lift_text.cpp: the parser of
+// swg_paf_lift against the handle's names); errors name `who` and the line.
+int swg_lift_bed_parse(const char* who, const swg_paf* p, const char* bed, uint64_t len, std::vector<swg_lift_region>* regions,
+                       std::vector<std::string>* labels);
+// first[b] .. first[b + 1]: the regions of batch b -- consecutive regions whose costs add up to at most batch_bytes, a region above
+// that alone.  m == 0: no batch (first = {0}).
+void swg_slice_plan_batches(const uint64_t* cost, uint64_t m, uint64_t batch_bytes, std::vector<uint64_t>* first);
+// one line of the slice PAF: q_name q_len q_start q_end strand t_name t_len t_start t_end col10 block mapq cg:Z:<text> rn:Z:<label>
+// ri:i:<record>; line: the record's own line (its columns 2, 7 and 12 are copied), cg / cg_len: the slice's text
+void swg_slice_line_text(std::string& o, const char* q_name, const char* t_name, const char* line, uint64_t line_len, const swg_lift_slice& s,
+                         const char* cg, const std::string& label);
 // ---- variants (swg_variants.hip: kernels and record seams) ----
 // where: 0 = everything on the host, 1 = on the device, 2 = the host's with seqs->bases in device memory; entry_usable: host [k] or NULL
 int swg_variant_run(swg_ctx* ctx, const swg_records* rec, int where, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,

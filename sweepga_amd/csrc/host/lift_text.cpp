@@ -250,6 +250,19 @@ int paf_lift(const char* who, bool exact, swg_ctx* ctx, const swg_paf* p, const 
 
 }  // namespace
 
+int swg_lift_bed_parse(const char* who, const swg_paf* p, const char* bed, uint64_t len, std::vector<swg_lift_region>* regions,
+                       std::vector<std::string>* labels) {
+  const uint32_t n_names = swg_paf_num_sequences(p);
+  std::unordered_map<std::string_view, uint32_t> ids;
+  ids.reserve(n_names);
+  for (uint32_t s = 0; s < n_names; ++s) ids.emplace(swg_paf_sequence_name(p, s), s);
+  std::vector<BedRegion> text;
+  const int rc = parse_bed(who, bed, len, ids, regions, &text);
+  if (rc != SWG_OK) return rc;
+  for (BedRegion& b : text) labels->push_back(std::move(b.label));
+  return SWG_OK;
+}
+
 extern "C" int swg_paf_lift(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const char* bed, uint64_t bed_len, uint32_t set, uint32_t axes,
                             char** out_text, uint64_t* out_len) {
   return paf_lift("swg_paf_lift", false, ctx, p, status, bed, bed_len, set, axes, out_text, out_len);

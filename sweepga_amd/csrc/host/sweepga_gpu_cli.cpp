@@ -417,6 +417,20 @@ void write_ucsc_chain(const std::string& path, swg_ctx* ctx, const swg_paf* paf,
                  (unsigned long long)c.bad, (unsigned long long)c.beyond, (unsigned long long)c.untagged, (unsigned long long)c.empty);
 }
 
+// --lift-paf: the slices of swg_paf_lift_paf_write, one PAF line per lifted region and record with its own coordinates and the part of
+// the record's cg:Z: CIGAR under the region (cut on the device); what it met goes to standard error in one line.
+void write_lift_paf(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const std::string& bed, uint32_t set, uint32_t axes,
+                    uint32_t min_aligned, uint64_t batch, bool quiet) {
+  swg_lift_paf_counts c;
+  if (swg_paf_lift_paf_write(ctx, paf, status, bed.data(), bed.size(), set, axes, min_aligned, batch, path.c_str(), &c) != SWG_OK)
+    die(3, std::string("--lift-paf: ") + swg_alnstats_last_error());
+  if (!quiet)
+    std::fprintf(stderr, "[sweepga-gpu] --lift-paf: %llu lines of %llu rows, %llu without a usable CIGAR, %llu without an aligned column, "
+                 "%llu below --lift-paf-min-aligned, %llu bad CIGARs, %llu device calls\n", (unsigned long long)c.slices, (unsigned long long)c.rows,
+                 (unsigned long long)c.interp, (unsigned long long)c.empty, (unsigned long long)c.too_short, (unsigned long long)c.bad,
+                 (unsigned long long)c.batches);
+}
+
 // --diffs / --diffs-summary: the difference list of swg_paf_diffs_write, one row per X, I, D or N op of the set's cg:Z: CIGARs (built on
 // the device), and its sums per genome pair; either path may be empty.  What it met goes to standard error in one line.
 void write_diffs(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set,
@@ -547,6 +561,9 @@ int main(int argc, char** argv) {
   std::string lift_regions_path, lift_path, lift_summary_path, lift_bed;  // --lift-regions, --lift, --lift-summary: empty = not given
   uint32_t lift_set = SWG_IV_KEPT, lift_axes = SWG_LIFT_AXIS_QUERY | SWG_LIFT_AXIS_TARGET;
   bool lift_flag = false;  // (--lift-set or --lift-axis was given)
+  std::string lift_paf_path;  // --lift-paf: empty = no file
+  uint64_t lift_paf_min_aligned = 1, lift_batch = 0;  // --lift-paf-min-aligned; --lift-batch: 0 = the library's default
+  bool lift_paf_flag = false;  // (--lift-paf-min-aligned or --lift-batch was given)
   bool lift_exact = false;  // --lift-exact: the rows of --lift through the CIGARs
   std::string ucsc_path;    // --ucsc-chain: empty = no file
   uint32_t ucsc_from = SWG_UCSC_FROM_TARGET, ucsc_set = SWG_IV_KEPT;
@@ -853,6 +870,20 @@ int main(int argc, char** argv) {
       else die(2, "invalid value for --mosaic-by: matches or length");
       mosaic_flag = true;
     }
+    else if (a == "--lift-paf") {
+      lift_paf_path = value();
+      if (lift_paf_path.empty()) die(2, "empty value for --lift-paf");
+      if (lift_paf_path == "-") die(2, "--lift-paf needs a file: a PAF is not a standard error report");
+    }
+    else if (a == "--lift-paf-min-aligned") {
+      if (!parse_metric_number(value(), &lift_paf_min_aligned) || lift_paf_min_aligned == 0 || lift_paf_min_aligned >> 32)
+        die(2, "invalid value for --lift-paf-min-aligned: 1 .. 4294967295 aligned columns");
+      lift_paf_flag = true;
+    }
+    else if (a == "--lift-batch") {
+      if (!parse_metric_number(value(), &lift_batch) || lift_batch == 0) die(2, "invalid value for --lift-batch: 1 or more bytes");
+      lift_paf_flag = true;
+    }
     else if (a == "--lift-set") {
       const std::string v = value();
       if (v == "kept") lift_set = SWG_IV_KEPT;
@@ -900,6 +931,7 @@ int main(int argc, char** argv) {
                 "         [--dotplot FILE] [--dotplot-size N|WxH] [--dotplot-layout FILE|-] [--dotplot-query PREFIX] [--dotplot-target PREFIX]\n"
                 "         [--lift-regions BED] [--lift FILE|-] [--lift-summary FILE|-] [--lift-set kept|all] [--lift-axis query|target|both]\n"
                 "         [--lift-exact]\n"
+                "         [--lift-paf FILE] [--lift-paf-min-aligned N] [--lift-batch BYTES]\n"
                 "         [--ucsc-chain FILE] [--ucsc-chain-from target|query] [--ucsc-chain-set kept|all] [--ucsc-chain-batch BYTES]\n"
                 "         [--diffs FILE] [--diffs-summary FILE] [--diffs-set kept|all] [--diffs-kinds snp,ins,del,skip] [--diffs-min-indel N]\n"
                 "         [--diffs-batch BYTES]\n"
@@ -1030,6 +1062,10 @@ int main(int argc, char** argv) {
                 "  --divergence-batch BYTES        CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --lift-set kept|all       the mappings the rows of --lift go through (default kept)\n"
                 "  --lift-axis query|target|both  regions lie on query sequences, target sequences or either (default both)\n"
+                "  --lift-paf FILE     write every lifted region of --lift-regions as a PAF line of its own: the coordinates and the part of the\n"
+                "                      record's cg:Z: CIGAR under the region, cut on the device; rn:Z: carries the BED label, ri:i: the record\n"
+                "  --lift-paf-min-aligned N  leave out slices with fewer than N aligned columns (default 1)\n"
+                "  --lift-batch BYTES  CIGAR text of the hit records per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --lift-hops N       walk the regions of --lift-regions through the mappings of --lift-set for up to N hops (1 .. 65535):\n"
                 "                      what a region reaches through a third genome when no mapping joins the two directly\n"
                 "  --lift-closure FILE `name start end label hop`: the disjoint pieces each region reaches, with the hop that found them\n"
@@ -1064,6 +1100,9 @@ int main(int argc, char** argv) {
   if (dotplot_path.empty() && dotplot_layout_path.empty() && dotplot_flag)
     die(2, "--dotplot-size, --dotplot-query and --dotplot-target need --dotplot or --dotplot-layout");
   const bool lift = !lift_regions_path.empty();
+  if (!lift && (!lift_paf_path.empty() || lift_paf_flag)) die(2, "--lift-paf, --lift-paf-min-aligned and --lift-batch need --lift-regions");
+  if (lift_paf_path.empty() && lift_paf_flag) die(2, "--lift-paf-min-aligned and --lift-batch need --lift-paf");
+  const bool lift_paf = !lift_paf_path.empty();
   if (!lift && (!lift_path.empty() || !lift_summary_path.empty() || lift_flag))
     die(2, "--lift, --lift-summary, --lift-set and --lift-axis need --lift-regions");
   if (!lift_hops && (!closure_path.empty() || !closure_summary_path.empty() || lift_min_length_flag))
@@ -1087,7 +1126,7 @@ int main(int argc, char** argv) {
     die(2, "--divergence-window, --divergence-axis, --divergence-genome, --divergence-set and --divergence-batch need --divergence or --divergence-summary");
   if (lift_hops && !lift) die(2, "--lift-hops needs --lift-regions");
   if (lift_hops && closure_path.empty() && closure_summary_path.empty()) die(2, "--lift-hops needs --lift-closure or --lift-closure-summary");
-  if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops) die(2, "--lift-regions needs --lift or --lift-summary");
+  if (lift && lift_path.empty() && lift_summary_path.empty() && !lift_hops && !lift_paf) die(2, "--lift-regions needs --lift or --lift-summary");
   const bool lift_once = lift && (!lift_path.empty() || !lift_summary_path.empty());  // the one-hop reports are asked for
   if (lift) {  // read now: an unreadable BED is a usage error, found before anything is begun
     FILE* f = std::fopen(lift_regions_path.c_str(), "rb");
@@ -1373,6 +1412,9 @@ int main(int argc, char** argv) {
       if (lift_hops)
         write_lift_closure(closure_path, closure_summary_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes,
                            (uint32_t)lift_hops, (uint32_t)lift_min_length);
+      if (lift_paf)
+        write_lift_paf(lift_paf_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), lift_bed, lift_set, lift_axes, (uint32_t)lift_paf_min_aligned,
+                       lift_batch, quiet);
     }
     if (ucsc) {  // nothing is dropped: kept = all
       std::fflush(out);
@@ -1573,6 +1615,11 @@ int main(int argc, char** argv) {
       write_lift_closure(closure_path, closure_summary_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes, (uint32_t)lift_hops,
                          (uint32_t)lift_min_length);
       if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift-hops: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tc).count());
+    }
+    if (lift_paf) {  // --lift-paf: every lifted region as an alignment of its own
+      const auto tc = clk::now();
+      write_lift_paf(lift_paf_path, ctx, paf, status.data(), lift_bed, lift_set, lift_axes, (uint32_t)lift_paf_min_aligned, lift_batch, quiet);
+      if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --lift-paf: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tc).count());
     }
   }
   // ---- --ucsc-chain: on the first context, the records in batches of bounded CIGAR text

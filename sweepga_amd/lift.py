@@ -8,7 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SwgCigarSet, SwgClosureRequest, SwgLiftExactRequest, SwgLiftRequest, default_context, load
+from ._lib import (SwgCigarSet, SwgClosureRequest, SwgLiftExactRequest, SwgLiftPafCounts, SwgLiftRequest, SwgLiftSliceRequest, default_context,
+                   load)
 from ._marshal import addr, host_column, raise_alnstats, records_from_numpy, records_from_tensors, take_texts, text_slots
 
 COLUMNS = ("q_id", "t_id", "q_start", "q_end", "t_start", "t_end")
@@ -388,3 +389,133 @@ class LiftClosure:
         raise_alnstats(lib, rc)
         text = [t.decode("utf-8", errors="surrogateescape") if t is not None else None for t in take_texts(lib, p, n, (rows, summary))]
         return cls(text[0], text[1])
+
+
+# ---- lift slices (csrc/swg_slice.hip): every exact row as an alignment of its own, with its sliced CIGAR --------------------------
+SLICE_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "record", "q_start", "q_end", "t_start", "t_end", "flags", "aligned", "matches", "text_len")]
+                       + [("block", np.uint64), ("text_first", np.uint64)])
+SLICE_HAS_EQ = 8
+SLICE_COUNTS = ("n_rows", "n_slices", "n_interp", "n_empty", "n_short", "text_bytes", "ops", "cigar_bad")
+PAF_COUNTS = ("rows", "slices", "interp", "empty", "too_short", "hits", "bad", "batches")
+
+
+def slice_text_tile():
+    """The output bytes one work-group of the text kernel writes (SWG_SLICE_TEXT_TILE as the library was built with it)."""
+    return int(load().swg_lift_slice_text_tile())
+
+
+class LiftSliceResult:
+    """slices: a SLICE_DTYPE array in the lift's row order, or None when slice_capacity did not hold them; text: the slices' CIGARs end
+    to end as bytes (slice s is text[text_first : text_first + text_len]), or None when text_capacity did not hold it; state: a uint8
+    per entry of the CIGAR set; counts: a dict of SLICE_COUNTS."""
+
+    def __init__(self, slices, text, state, counts):
+        self.slices, self.text, self.state, self.counts = slices, text, state, counts
+
+    def cigar(self, s):
+        w = self.slices[s]
+        return self.text[int(w["text_first"]):int(w["text_first"]) + int(w["text_len"])].decode("latin-1")
+
+
+def _slice_call(ctx, fn, rec, status_addr, regions_addr, m, cigars, k, set_, axes, min_aligned, slice_capacity, text_capacity, want_slices=True,
+                want_text=True):
+    """slice_capacity / text_capacity None: the two-call protocol (count, then fetch); a number: one call with arrays of that size.
+    want_slices / want_text False: that pointer is NULL."""
+    req = SwgLiftSliceRequest()
+    req.set, req.axes, req.min_aligned = int(set_), int(axes), int(min_aligned)
+    state = np.zeros(int(k), dtype=np.uint8)
+    req.state = state.ctypes.data if k else None
+    cs = None
+    if cigars is not None:
+        cs = SwgCigarSet()
+        cs.record, cs.offset, cs.text, cs.k = cigars[0], cigars[1], cigars[2], int(k)
+    call = lambda: ctx.check(fn(ctx.handle, C.byref(rec), status_addr, regions_addr, m, C.byref(cs) if cs is not None else None, C.byref(req)))   # noqa: E731
+    two_calls = slice_capacity is None or text_capacity is None
+    if two_calls:
+        call()
+        slice_capacity = int(req.n_slices) if slice_capacity is None else slice_capacity
+        text_capacity = int(req.text_bytes) if text_capacity is None else text_capacity
+    slices = np.zeros(int(slice_capacity), dtype=SLICE_DTYPE)
+    text = np.zeros(max(int(text_capacity), 1), dtype=np.uint8)
+    req.slice_capacity, req.slices = int(slice_capacity), slices.ctypes.data if want_slices else None
+    req.text_capacity, req.text = int(text_capacity), text.ctypes.data if want_text else None
+    call()
+    counts = {key: int(getattr(req, key)) for key in SLICE_COUNTS}
+    got_slices = want_slices and counts["n_slices"] <= slice_capacity
+    got_text = want_text and counts["text_bytes"] <= text_capacity
+    return LiftSliceResult(slices[:counts["n_slices"]] if got_slices else None, text[:counts["text_bytes"]].tobytes() if got_text else None, state, counts)
+
+
+def lift_slice_records(ctx, records, strand, n_seq, regions, cigar_records, cigars, status=None, set="all", axes="both", min_aligned=1,
+                       slice_capacity=None, text_capacity=None, want_slices=True, want_text=True):
+    """swg_lift_slice_records: the arguments of lift_exact_records, plus min_aligned and the two capacities.  Returns a LiftSliceResult."""
+    regs = regions_array(regions)
+    rec, keep = _host_records(records, strand, n_seq)
+    st = host_column(status, np.uint8, int(rec.n), "status", optional=True)
+    record, offset, text = cigars if cigar_records is None else cigar_set(cigar_records, cigars)
+    k = int(record.size)
+    return _slice_call(ctx, ctx.lib.swg_lift_slice_records, rec, addr(st), regs.ctypes.data if regs.size else None, regs.size,
+                       (record.ctypes.data, offset.ctypes.data, text.ctypes.data) if k else None, k, SETS.get(set, set), AXES.get(axes, axes), min_aligned,
+                       slice_capacity, text_capacity, want_slices, want_text)
+
+
+def lift_slice_records_device(ctx, columns, strand, n_seq, regions, n_regions, cigar_record, cigar_offset, cigar_text, k, status=None, set="all",
+                              axes="both", min_aligned=1, slice_capacity=None, text_capacity=None, want_slices=True, want_text=True):
+    """swg_lift_slice_records_device: the arguments of lift_exact_records_device, plus min_aligned and the two capacities.  Slices, text
+    and state come back on the host."""
+    rec = _device_records(columns, strand, n_seq, regions, n_regions, status)
+    k = int(k)
+    if k and (int(cigar_record.numel()) * cigar_record.element_size() < 4 * k or int(cigar_offset.numel()) * cigar_offset.element_size() < 8 * (k + 1)):
+        raise ValueError("the CIGAR set's record or offset tensor is shorter than k asks for")
+    cig = (int(cigar_record.data_ptr()), int(cigar_offset.data_ptr()), int(cigar_text.data_ptr())) if k else None
+    return _slice_call(ctx, ctx.lib.swg_lift_slice_records_device, rec, int(status.data_ptr()) if status is not None else None,
+                       int(regions.data_ptr()), int(n_regions), cig, k, SETS.get(set, set), AXES.get(axes, axes), min_aligned, slice_capacity,
+                       text_capacity, want_slices, want_text)
+
+
+class LiftPaf:
+    """BED regions lifted through an open PafFile, every slice as one PAF line with its own coordinates and its sliced cg:Z: (`text`);
+    `counts`: a dict of PAF_COUNTS; rows(): the lines split into fields, the numeric PAF columns as int."""
+
+    def __init__(self, text, counts):
+        self.text, self.counts = text, counts
+
+    def rows(self):
+        out = []
+        for ln in self.text.split("\n"):
+            if ln:
+                f = ln.split("\t")
+                out.append(tuple(int(v) if k in (1, 2, 3, 6, 7, 8, 9, 10, 11) else v for k, v in enumerate(f)))
+        return out
+
+    @staticmethod
+    def _args(paf, status, bed_text, set, axes, ctx):
+        ctx = getattr(ctx, "ctx", ctx)
+        lib = load()
+        bed = bed_text.encode("utf-8", errors="surrogateescape") if isinstance(bed_text, str) else bytes(bed_text)
+        rebased = bool(lib.swg_paf_seq_offsets(paf.handle)) or bool(lib.swg_paf_record_offsets(paf.handle, 0))   # (refused by the library)
+        if ctx is None and paf.n and bed.strip() and not rebased:
+            ctx = default_context()
+        st = host_column(status, np.uint8, paf.n, "status", optional=True)
+        return lib, ctx.handle if ctx is not None else None, st, bed, SETS.get(set, set), AXES.get(axes, axes)
+
+    @classmethod
+    def from_paf(cls, paf, status, bed_text, set="kept", axes="both", min_aligned=1, batch_bytes=0, ctx=None):
+        """swg_paf_lift_paf_text.  status None: set must be "all".  ctx as in Lift.from_paf.  batch_bytes: the cost of the regions per
+        device call (the CIGAR text of their hits), 0 = the library's default."""
+        lib, handle, st, bed, set_, axes_ = cls._args(paf, status, bed_text, set, axes, ctx)
+        counts, p, n = SwgLiftPafCounts(), C.c_void_p(), C.c_uint64()
+        raise_alnstats(lib, lib.swg_paf_lift_paf_text(handle, paf.handle, addr(st), bed, len(bed), set_, axes_, int(min_aligned), int(batch_bytes),
+                                                      C.byref(counts), C.byref(p), C.byref(n)))
+        text = C.string_at(p.value, n.value).decode("utf-8", errors="surrogateescape")
+        lib.swg_free(p)
+        return cls(text, {k: int(getattr(counts, k)) for k in PAF_COUNTS})
+
+    @classmethod
+    def write_paf(cls, paf, status, bed_text, path, set="kept", axes="both", min_aligned=1, batch_bytes=0, ctx=None):
+        """swg_paf_lift_paf_write: the same into a file -> the counts."""
+        lib, handle, st, bed, set_, axes_ = cls._args(paf, status, bed_text, set, axes, ctx)
+        counts = SwgLiftPafCounts()
+        raise_alnstats(lib, lib.swg_paf_lift_paf_write(handle, paf.handle, addr(st), bed, len(bed), set_, axes_, int(min_aligned), int(batch_bytes),
+                                                       str(path).encode(), C.byref(counts)))
+        return {k: int(getattr(counts, k)) for k in PAF_COUNTS}
