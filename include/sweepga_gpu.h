@@ -2011,6 +2011,105 @@ int swg_paf_vcf_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, con
 /* The same as malloc'd texts (release each with swg_free); vcf_text or summary_text may be NULL (not both). */
 int swg_paf_vcf_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_vcf_options* opts,
                      swg_vcf_counts* counts, char** vcf_text, uint64_t* vcf_len, char** summary_text, uint64_t* summary_len);
+
+/* ---- resolved CIGARs: every entry rewritten in canonical =/X form against the sequences (no reference counterpart; DESIGN.md
+ * section 36) ----
+ * The CIGAR set, the walk offsets x / y and the entry states are those of the base-exact lift; norm, comp, the query column at walk
+ * offset x, sequence presence and the bounds test are those of the variants above.  Integers and bytes only.
+ * An entry is USABLE when its state is 0, its record is in `set`, both sequences are present, and t_end <= len(t), q_end <= len(q).
+ * The first failing test counts: cigar_bad (a state bit of 1 .. 8), empty (state 16), no_sequence, out_of_sequence; an entry
+ * outside the set counts nowhere.  There are no genome filters.
+ * A COLUMN OP is an M, = or X op.  A COLUMN RUN is a maximal sequence of consecutive column ops in the entry's text; column ops of
+ * length 0 belong to it, any other op ends it, one of length 0 included.
+ * A column at target index p = t_start + y and walk offset x, r = norm(T[p]), a = the query column: eq = (r == a and r != N).  A
+ * column with an N on either side is never equal.
+ * OUTPUT TEXT of a usable entry, in text order: a column run of L > 0 columns becomes its maximal stretches of constant eq, each
+ * written `<length>=` or `<length>X` in decimal without leading zeros; a run with L = 0 becomes nothing; every other op is copied
+ * byte for byte, digits and letter (leading zeros and zero lengths stay).  The output, taken as an entry of the same record, has
+ * state 0 and the same advances; it holds no M, and inside a run no two neighbouring ops carry the same letter.
+ * One swg_eqx_entry per entry of the set, in set order (no compaction); an entry that is not usable has only `record` set.  The
+ * texts of the usable entries lie end to end, without separators, in set order; text_first runs over them.
+ * Capacity protocol of swg_ucsc_chain_records: entries is written when k <= entry_capacity, text when text_bytes <= text_capacity
+ * (each only when non-NULL; without a text pointer the text is counted and not built); the counts whenever the call succeeds.
+ * Refusals: those of swg_variant_records for the set, the columns, the sequences and the offsets (SWG_ERR_INVALID); 2^32 bytes of
+ * CIGAR text, 2^32 columns, 2^32 output ops or 2^32 output bytes or more in one call: SWG_ERR_RANGE (no range loop is built).
+ * k == 0 needs no device.  Scratch from the arena: the build's plus, per op, 1 + 4 + 1 + 16 bytes (kind, letter position, class,
+ * the scans of columns and verbatim ops); per entry 1 + 64; per column 1 (boundary flag and letter); per output op 4 + 8 + 8 (its
+ * column, the item, the scanned length); the text; the host seam stages 26 bytes per record, 8 per sequence and every base. */
+#define SWG_EQX_USABLE 1u  /* swg_eqx_entry.flags bit 0 */
+#define SWG_EQX_CHANGED 2u /* bit 1: the output bytes differ from the input bytes */
+#define SWG_EQX_COLUMN_TILE 4096u /* columns per work-group of the column pass */
+#define SWG_EQX_TEXT_TILE 4096u   /* output bytes per work-group of the text kernel */
+typedef struct swg_eqx_entry {
+  uint32_t record, flags;
+  uint32_t text_len, out_ops;
+  uint32_t matches, mismatches; /* columns with eq, the other columns */
+  uint32_t n_columns;           /* columns with an N: a subset of mismatches */
+  uint32_t eq_wrong, x_wrong;   /* columns under = with eq false, under X with eq true */
+  uint32_t m_columns;           /* columns under M */
+  uint32_t inserted, deleted;   /* bases under I, under D (N ops count in neither) */
+  uint64_t block;               /* matches + mismatches + inserted + deleted */
+  uint64_t text_first;          /* into text */
+} swg_eqx_entry; /* 64 bytes, no implicit padding */
+typedef struct swg_eqx_request {
+  uint32_t set;            /* in: SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t reserved;       /* in: 0 */
+  uint64_t entry_capacity; /* in: entries `entries` can hold */
+  swg_eqx_entry* entries;  /* in: caller-owned or NULL; written only when k <= entry_capacity */
+  uint64_t text_capacity;
+  char* text;              /* written only when text_bytes <= text_capacity */
+  uint64_t ops;            /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;      /* out: entries with a state bit of 1 .. 8 */
+  uint64_t empty;          /* out: entries of state 16 */
+  uint64_t usable, no_sequence, out_of_sequence;
+  uint64_t columns;        /* out: matches + mismatches */
+  uint64_t out_ops, text_bytes;
+  uint64_t changed;        /* out: usable entries with SWG_EQX_CHANGED */
+  uint64_t matches, mismatches, n_columns, eq_wrong, x_wrong, m_columns; /* out: over the usable entries */
+} swg_eqx_request; /* 168 bytes, no implicit padding */
+/* Everything on the host. */
+int swg_eqx_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                    swg_eqx_request* req);
+/* Columns, strand, status, the three arrays of the set, seqs->offset and seqs->bases in device memory of ctx's GPU; the two set
+ * structures, the request and its arrays on the host. */
+int swg_eqx_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                           swg_eqx_request* req);
+/* --eqx: the records of `set` of an open PAF, in record order, each usable one's line byte for byte but for column 10 (= matches),
+ * column 11 (= block) and the value of its LAST cg:Z: tag (= the output text).  Other tags (NM:i, de:f, gi:f, ...) are copied and
+ * may be stale.  A record that is not usable (no tag, a bad or empty entry, a sequence that is missing or of another length, out of
+ * bounds) is copied unchanged under SWG_EQX_KEEP and left out under SWG_EQX_DROP.  Sequence names are matched to the FASTA records
+ * as swg_paf_vcf_write does it (length_mismatch included); the bases go to the device once per call; batches come from
+ * swg_paf_ucsc_chain_write's planner over the cost text length + min(q_end - q_start, t_end - t_start), which bounds an entry's
+ * columns and, at 2 bytes per column plus the input text, its output: one device pass per batch with that bound as the text
+ * capacity.  The file is the same bytes for every batch_bytes.  A set without records gives an empty file and needs no device (ctx
+ * may be NULL).  Refusals, all before a file is opened: set > 1, unresolved > 1, reserved != 0, SWG_IV_KEPT without status, a NULL
+ * fasta or opts: SWG_ERR_INVALID; a handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  counts may be NULL.  Errors:
+ * swg_alnstats_last_error(). */
+#define SWG_EQX_KEEP 0u
+#define SWG_EQX_DROP 1u
+typedef struct swg_eqx_options {
+  uint32_t set;         /* SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t unresolved;  /* SWG_EQX_KEEP or SWG_EQX_DROP */
+  uint64_t batch_bytes; /* cost per device call; 0 = a default from the device's memory */
+  uint64_t reserved;    /* 0 */
+} swg_eqx_options; /* 24 bytes */
+typedef struct swg_eqx_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t usable;   /* lines rewritten */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t untagged; /* records without a cg:Z: tag */
+  uint64_t no_sequence, out_of_sequence; /* entries */
+  uint64_t length_mismatch;              /* sequences */
+  uint64_t changed;  /* usable entries whose text changed */
+  uint64_t lines;    /* lines written */
+  uint64_t columns, matches, mismatches, eq_wrong, x_wrong, m_columns;
+  uint64_t batches;  /* device calls */
+} swg_eqx_counts; /* 128 bytes */
+int swg_paf_eqx_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_eqx_options* opts,
+                      const char* out_path, swg_eqx_counts* counts);
+/* The same as one malloc'd text (release with swg_free). */
+int swg_paf_eqx_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_eqx_options* opts,
+                     swg_eqx_counts* counts, char** text, uint64_t* len);
 /* Per contig, the bottom-s MULTISET of min(SipHash-1-3(le64(k) || window), SipHash-1-3(le64(k) || revcomp upper-cased))
  * over the windows of k bytes all in ACGTacgt, ascending (KmerSketch::from_sequence, mash.rs:78-131).  Contig i =
  * seq[offsets[i], offsets[i + 1]); counts_out[n_seq]; minimizers_out[n_seq * s], row i holds counts_out[i] values.  The

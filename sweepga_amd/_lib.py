@@ -53,7 +53,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_place_records", "swg_place_records_device", "swg_paf_place",
            "swg_windows_records", "swg_windows_records_device", "swg_paf_windows",
            "swg_divergence_records", "swg_divergence_records_device", "swg_paf_divergence",
-           "swg_variant_records", "swg_variant_records_device", "swg_paf_vcf_write", "swg_paf_vcf_text"]
+           "swg_variant_records", "swg_variant_records_device", "swg_paf_vcf_write", "swg_paf_vcf_text",
+           "swg_eqx_records", "swg_eqx_records_device", "swg_paf_eqx_write", "swg_paf_eqx_text"]
 
 
 class SwgError(RuntimeError):
@@ -422,6 +423,28 @@ class SwgVcfCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VCF_COUNTS]
 
 
+EQX_FIELDS = ("ops", "cigar_bad", "empty", "usable", "no_sequence", "out_of_sequence", "columns", "out_ops", "text_bytes", "changed", "matches",
+              "mismatches", "n_columns", "eq_wrong", "x_wrong", "m_columns")
+
+
+class SwgEqxRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("reserved", C.c_uint32), ("entry_capacity", C.c_uint64), ("entries", C.c_void_p), ("text_capacity", C.c_uint64),
+                ("text", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in EQX_FIELDS]
+
+
+class SwgEqxOptions(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("unresolved", C.c_uint32), ("batch_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+EQX_COUNTS = ("records", "usable", "bad", "untagged", "no_sequence", "out_of_sequence", "length_mismatch", "changed", "lines", "columns", "matches",
+              "mismatches", "eq_wrong", "x_wrong", "m_columns", "batches")
+
+
+class SwgEqxCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in EQX_COUNTS]
+
+
 class SwgClosureRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")]
 
@@ -735,6 +758,15 @@ def load():
     lib.swg_paf_vcf_text.restype = C.c_int
     lib.swg_paf_vcf_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgVcfOptions), C.POINTER(SwgVcfCounts),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for name in ("swg_eqx_records", "swg_eqx_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.POINTER(SwgCigarSet), C.POINTER(SwgSeqSet), C.POINTER(SwgEqxRequest)]
+    lib.swg_paf_eqx_write.restype = C.c_int
+    lib.swg_paf_eqx_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgEqxOptions), C.c_char_p, C.POINTER(SwgEqxCounts)]
+    lib.swg_paf_eqx_text.restype = C.c_int
+    lib.swg_paf_eqx_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgEqxOptions), C.POINTER(SwgEqxCounts), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_uint64)]
     for name in ("swg_divergence_records", "swg_divergence_records_device"):
         f = getattr(lib, name)
         f.restype = C.c_int

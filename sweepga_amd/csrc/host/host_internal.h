@@ -182,6 +182,14 @@ void swg_vcf_header_text(std::string& o, const std::vector<std::string>& contig_
 void swg_vcf_line_text(std::string& o, const char* t_name, const char* q_name, const swg_variant& v, const uint8_t* alleles, bool genotype);
 void swg_variants_merge_pairs(std::vector<swg_variant_pair>* total, const swg_variant_pair* add, uint64_t n);
 std::string swg_variants_summary_text(const std::vector<std::string>& genome_name, const std::vector<swg_variant_pair>& pairs);
+// ---- resolved CIGARs (swg_eqx.hip: kernels and record seams; eqx_text.cpp: the two PAF seams) ----
+// where: as swg_variant_run
+int swg_eqx_run(swg_ctx* ctx, const swg_records* rec, int where, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                swg_eqx_request* req);
+// A usable record's line: `line` (len bytes, with or without its line end) with column 10 = matches, column 11 = block and the
+// value of its last cg:Z: tag (cg, cg_len: where swg_cigar_tag_find found it) = text[0 .. text_len); a '\n' ends it.
+void swg_eqx_line_text(std::string& o, const char* line, uint64_t len, const char* cg, uint64_t cg_len, uint64_t matches, uint64_t block,
+                       const char* text, uint64_t text_len);
 // ---- differences (swg_diffs.hip: kernels and record seams; diffs_text.cpp: the two PAF seams) ----
 int swg_diff_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
                  const swg_cigar_set* cigars, swg_diff_request* req);

@@ -467,6 +467,27 @@ void write_vcf(const std::string& vcf_path, const std::string& summary_path, swg
                  (unsigned long long)c.bad, (unsigned long long)c.untagged);
 }
 
+// --eqx: the PAF of swg_paf_eqx_write -- the set's records with every cg:Z: resolved to =/X against the FASTA records, columns 10 and 11
+// exact (built on the device).  What it met goes to standard error in one line; eq_wrong and x_wrong, when not zero, say that PAF and
+// FASTA do not belong together.
+void write_eqx(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const swg_fasta* fasta, uint32_t set, uint32_t unresolved,
+               uint64_t batch, bool quiet) {
+  swg_eqx_options o{};
+  o.set = set, o.unresolved = unresolved, o.batch_bytes = batch;
+  swg_eqx_counts c;
+  if (swg_paf_eqx_write(ctx, paf, status, fasta, &o, path.c_str(), &c) != SWG_OK) die(3, std::string("--eqx: ") + swg_alnstats_last_error());
+  if (quiet) return;
+  std::fprintf(stderr, "[sweepga-gpu] --eqx: %llu lines, %llu resolved (%llu changed): %llu columns, %llu matches, %llu mismatches, %llu under M ops; "
+               "%llu entries without sequence, %llu out of sequence, %llu bad, %llu without a cg:Z: tag, %llu sequences of another length",
+               (unsigned long long)c.lines, (unsigned long long)c.usable, (unsigned long long)c.changed, (unsigned long long)c.columns,
+               (unsigned long long)c.matches, (unsigned long long)c.mismatches, (unsigned long long)c.m_columns, (unsigned long long)c.no_sequence,
+               (unsigned long long)c.out_of_sequence, (unsigned long long)c.bad, (unsigned long long)c.untagged, (unsigned long long)c.length_mismatch);
+  if (c.eq_wrong || c.x_wrong)
+    std::fprintf(stderr, "; eq_wrong %llu, x_wrong %llu: '=' over differing and 'X' over equal bases -- is this the FASTA the PAF was made from?",
+                 (unsigned long long)c.eq_wrong, (unsigned long long)c.x_wrong);
+  std::fputc('\n', stderr);
+}
+
 // --divergence / --divergence-summary: the two texts of swg_paf_divergence (exact matches, mismatches and indels per fixed window,
 // from the set's cg:Z: CIGARs, built on the device).  "-" = standard error.  What it met goes to standard error in one line.
 void write_divergence(const std::string& rows_path, const std::string& summary_path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, uint32_t set,
@@ -578,6 +599,11 @@ int main(int argc, char** argv) {
   uint32_t vcf_set = SWG_IV_KEPT;
   uint64_t vcf_max_indel = 10000, vcf_batch = 0;  // --vcf-max-indel: 0 = no limit; --vcf-batch: 0 = the library's default
   bool vcf_flag = false;  // (a sub-option of --vcf was given)
+  std::string eqx_path;                     // --eqx: empty = not given
+  std::vector<std::string> eqx_fasta_paths;  // --eqx-fasta, once per file
+  uint32_t eqx_set = SWG_IV_KEPT, eqx_unresolved = SWG_EQX_KEEP;
+  uint64_t eqx_batch = 0;  // --eqx-batch: 0 = the library's default
+  bool eqx_flag = false;   // (a sub-option of --eqx was given)
   std::string divergence_path, divergence_summary_path, divergence_genome;  // --divergence, --divergence-summary: empty = no file; -genome: empty = any
   uint32_t divergence_set = SWG_IV_KEPT, divergence_axis = 0;
   uint64_t divergence_window = 10000, divergence_batch = 0;  // --divergence-window; --divergence-batch: 0 = the library's default
@@ -739,6 +765,34 @@ int main(int argc, char** argv) {
     else if (a == "--vcf-batch") {
       if (!parse_metric_number(value(), &vcf_batch) || vcf_batch == 0) die(2, "invalid value for --vcf-batch: 1 or more bytes");
       vcf_flag = true;
+    }
+    else if (a == "--eqx") {
+      eqx_path = value();
+      if (eqx_path.empty()) die(2, "empty value for --eqx");
+      if (eqx_path == "-") die(2, "--eqx needs a file: the resolved PAF is not a standard error report");
+    }
+    else if (a == "--eqx-fasta") {
+      eqx_fasta_paths.push_back(value());
+      if (eqx_fasta_paths.back().empty() || eqx_fasta_paths.back() == "-") die(2, "--eqx-fasta needs a file");
+      eqx_flag = true;
+    }
+    else if (a == "--eqx-set") {
+      const std::string v = value();
+      if (v == "kept") eqx_set = SWG_IV_KEPT;
+      else if (v == "all") eqx_set = SWG_IV_ALL;
+      else die(2, "invalid value for --eqx-set: kept or all");
+      eqx_flag = true;
+    }
+    else if (a == "--eqx-unresolved") {
+      const std::string v = value();
+      if (v == "keep") eqx_unresolved = SWG_EQX_KEEP;
+      else if (v == "drop") eqx_unresolved = SWG_EQX_DROP;
+      else die(2, "invalid value for --eqx-unresolved: keep or drop");
+      eqx_flag = true;
+    }
+    else if (a == "--eqx-batch") {
+      if (!parse_metric_number(value(), &eqx_batch) || eqx_batch == 0) die(2, "invalid value for --eqx-batch: 1 or more bytes");
+      eqx_flag = true;
     }
     else if (a == "--diffs-set") {
       const std::string v = value();
@@ -937,6 +991,7 @@ int main(int argc, char** argv) {
                 "         [--diffs-batch BYTES]\n"
                 "         [--vcf FILE] [--vcf-summary FILE] --vcf-fasta FASTA [--vcf-fasta FASTA ...] [--vcf-ref GENOME] [--vcf-query GENOME]\n"
                 "         [--vcf-set kept|all] [--vcf-max-indel N] [--vcf-batch BYTES]\n"
+                "         [--eqx FILE] --eqx-fasta FASTA [--eqx-fasta FASTA ...] [--eqx-set kept|all] [--eqx-unresolved keep|drop] [--eqx-batch BYTES]\n"
                 "         [--divergence FILE|-] [--divergence-summary FILE|-] [--divergence-window N] [--divergence-axis query|target]\n"
                 "         [--divergence-genome NAME] [--divergence-set kept|all] [--divergence-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
@@ -1049,6 +1104,12 @@ int main(int argc, char** argv) {
                 "  --vcf-set kept|all              the records that are read (default kept)\n"
                 "  --vcf-max-indel N               insertions and deletions up to N bases (default 10000; 0 = no limit)\n"
                 "  --vcf-batch BYTES               CIGAR text per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
+                "  --eqx FILE          write the records as PAF with every cg:Z: resolved to =/X against the FASTA (M ops told apart base by base,\n"
+                "                      = and X ops checked), column 10 the exact matches, column 11 the block length; other tags are copied\n"
+                "  --eqx-fasta FASTA               the sequences, matched to the PAF's names by exact name; once per file (needed)\n"
+                "  --eqx-set kept|all              the records that are written (default kept)\n"
+                "  --eqx-unresolved keep|drop      a record that cannot be resolved is copied unchanged, or left out (default keep)\n"
+                "  --eqx-batch BYTES               CIGAR text and columns per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --divergence FILE   after the filter: one line per window of every sequence that carries an inter-genome mapping of the set --\n"
                 "                      `sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels`, exact\n"
                 "                      from the cg:Z: CIGARs (built on the device), empty windows included; integers only: column identity is\n"
@@ -1120,6 +1181,15 @@ int main(int argc, char** argv) {
     std::vector<const char*> paths;
     for (const std::string& f : vcf_fasta_paths) paths.push_back(f.c_str());
     if (swg_fasta_open(paths.data(), (int)paths.size(), threads, &vcf_fasta) != SWG_OK) die(2, std::string("--vcf-fasta: ") + swg_fasta_last_error());
+  }
+  const bool eqx = !eqx_path.empty();
+  if (!eqx && eqx_flag) die(2, "--eqx-fasta, --eqx-set, --eqx-unresolved and --eqx-batch need --eqx");
+  if (eqx && eqx_fasta_paths.empty()) die(2, "--eqx needs --eqx-fasta: the bases are not in a PAF");
+  swg_fasta* eqx_fasta = nullptr;
+  if (eqx) {  // read now: an unreadable FASTA is a usage error, found before anything is begun
+    std::vector<const char*> paths;
+    for (const std::string& f : eqx_fasta_paths) paths.push_back(f.c_str());
+    if (swg_fasta_open(paths.data(), (int)paths.size(), threads, &eqx_fasta) != SWG_OK) die(2, std::string("--eqx-fasta: ") + swg_fasta_last_error());
   }
   const bool divergence = !divergence_path.empty() || !divergence_summary_path.empty();
   if (!divergence && divergence_flag)
@@ -1215,7 +1285,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence && !vcf)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence && !vcf && !eqx)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1437,6 +1507,13 @@ int main(int argc, char** argv) {
                 vcf_batch, quiet);
       swg_fasta_close(vcf_fasta);
     }
+    if (eqx) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_eqx(eqx_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), eqx_fasta, eqx_set, eqx_unresolved, eqx_batch, quiet);
+      swg_fasta_close(eqx_fasta);
+    }
     if (divergence) {  // nothing is dropped: kept = all
       std::fflush(out);
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
@@ -1640,6 +1717,13 @@ int main(int argc, char** argv) {
     write_vcf(vcf_path, vcf_summary_path, ctx, paf, status.data(), vcf_fasta, vcf_set, vcf_ref, vcf_query, (uint32_t)vcf_max_indel, vcf_batch, quiet);
     swg_fasta_close(vcf_fasta);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --vcf: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --eqx: likewise, the bases on the device once, one device pass per batch
+  if (eqx) {
+    const auto tb = clk::now();
+    write_eqx(eqx_path, ctx, paf, status.data(), eqx_fasta, eqx_set, eqx_unresolved, eqx_batch, quiet);
+    swg_fasta_close(eqx_fasta);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --eqx: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --divergence / --divergence-summary: likewise, one device call per batch over all records
   if (divergence) {
