@@ -456,6 +456,11 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
   uint32_t heads = 0;  // chains headed in this thread's elements (a statistic: all chains, passing the filter or not)
   for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const uint32_t b = chunks[c].bb, e = chunks[c].be;
+    const uint32_t pad = RANKED ? chunks[c].pad : 0u;
+    // A marked chunk needs no t_end: pair_sort hands the call over on any member with t_start >= t_end (the form requires its
+    // check of degenerate members), so a chain's smallest t_start lies below its largest t_end whatever they are -- the column
+    // is not loaded, not staged and not folded there, and only the query span is tested.
+    const bool rkd = RANKED && (pad & CHUNK_RANKED) != 0u;
     uint32_t len = e > b ? e - b : 0;  // 0: a long unit's place holder
     if (len >= (uint32_t)LABEL_CAP) len = 0;  // (pair-resident path: a chunk too long for this LDS layout is pair_label_long's)
     __syncthreads();
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
         r_pr[u] = pred[p];
         r_qe[u] = s_qe[p];
         r_ts[u] = s_ts[p];
-        r_te[u] = s_te[p];
+        r_te[u] = rkd ? 0u : s_te[p];
         r_m[u] = s_m ? s_m[p] : 0u;  // (nullptr: the weighted identity is not asked for -- the pair-resident path without an identity floor)
         r_b[u] = s_m ? s_b[p] : 0u;
         r_qs[u] = s_qs[p];
@@ -487,7 +492,7 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
           l_hd[k] = r_pr[u] != NONE ? NO : (uint16_t)k;          // (a member's entry is written by its head below)
           l_qe[k] = r_qe[u];
           l_ts[k] = r_ts[u];
-          l_te[k] = r_te[u];
+          if (!rkd) l_te[k] = r_te[u];
           if constexpr (MB) {
             l_m[k] = r_m[u];
             l_b[k] = r_b[u];
@@ -495,8 +500,6 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
         }
       }
       __syncthreads();
-      const uint32_t pad = RANKED ? chunks[c].pad : 0u;
-      const bool rkd = RANKED && (pad & CHUNK_RANKED) != 0u;
       uint32_t pass = 0;  // (ranked form) bit u: the thread's element of row u heads a passing chain
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -510,15 +513,28 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
         ++heads;
         uint32_t qe = r_qe[u], ts = r_ts[u], te = r_te[u];
         uint64_t sm = r_m[u], sb = r_b[u];
-        for (uint16_t nx = succ[k]; nx != NO; nx = succ[nx]) {
-          const uint32_t a = l_qe[nx], t0 = l_ts[nx], t1 = l_te[nx];
-          l_hd[nx] = (uint16_t)k;
-          qe = a > qe ? a : qe;
-          ts = t0 < ts ? t0 : ts;
-          te = t1 > te ? t1 : te;
-          if constexpr (MB) {
-            sm += l_m[nx];
-            sb += l_b[nx];
+        if (rkd) {  // (uniform; RANKED instances have no identity columns)
+          for (uint16_t nx = succ[k]; nx != NO; nx = succ[nx]) {
+            const uint32_t a = l_qe[nx], t0 = l_ts[nx];
+            l_hd[nx] = (uint16_t)k;
+            qe = a > qe ? a : qe;
+            ts = t0 < ts ? t0 : ts;
+            if constexpr (MB) {
+              sm += l_m[nx];
+              sb += l_b[nx];
+            }
+          }
+        } else {
+          for (uint16_t nx = succ[k]; nx != NO; nx = succ[nx]) {
+            const uint32_t a = l_qe[nx], t0 = l_ts[nx], t1 = l_te[nx];
+            l_hd[nx] = (uint16_t)k;
+            qe = a > qe ? a : qe;
+            ts = t0 < ts ? t0 : ts;
+            te = t1 > te ? t1 : te;
+            if constexpr (MB) {
+              sm += l_m[nx];
+              sb += l_b[nx];
+            }
           }
         }
         const uint32_t qs0 = r_qs[u];
@@ -548,7 +564,7 @@ __global__ __launch_bounds__(NT, RANKED ? 8 : 1) void chain_label_kernel(uint32_
             l_qe[k] = qe;
             l_ts[k] = ts;
             l_te[k] = qs0;
-            if (!(qs0 < qe && ts < te)) atomicOr(R.flags, R.fallback_bit);
+            if (!(qs0 < qe)) atomicOr(R.flags, R.fallback_bit);  // (ts < te: see rkd above)
           } else {
             succ[k] = NO;  // (what its members will find: the chain fails)
           }

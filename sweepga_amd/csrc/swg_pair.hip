@@ -1889,7 +1889,7 @@ __global__ __launch_bounds__(NT) void pair_chains_kernel(PairChainArgs A) {
 // "both spans positive", and runs once more under the exact rule if it met such a chain.
 // KP: the kept '+' chains of a pair that are staged in LDS for the inversion capture (a longer list is searched in memory).
 template <int NT, int KP>
-__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(PairFinishArgs A) {  // (large class: two work-groups per CU)
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : NT >= 256 ? 7 : 1) void pair_finish_kernel(PairFinishArgs A) {  // (large class: two work-groups per CU; middle class: seven waves per SIMD)
   constexpr int U = 4;  // positions per thread and round: their loads are requested together
   __shared__ uint32_t ws[NT / 64 + 1];
   __shared__ uint64_t ws64[NT / 64 + 1];
@@ -1905,17 +1905,20 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
 #endif
   // a pair_sort work-group gave the call up (a pair too dense for the LDS batches ...): nothing written from here on is used
   // (the host sees the same flag and runs the global-sort stage)
-  if (A.C->flags & PF_FALLBACK) return;
+  // (the flag word is requested with the list entry and tested once the pair's run and info are there: the lists and the runs are
+  // written before pair_sort, which is who gives up)
+  const uint32_t call_flags = A.C->flags;
   const uint32_t rk = blockIdx.x < A.n_xl ? A.list_xl[blockIdx.x] : A.list[blockIdx.x - A.n_xl];
   const PairRun run = A.runs[rk];
   const PairInfo pi = A.info[rk];
-  const uint32_t a = run.a, m = pi.m, m_plus = pi.m_plus, M = pi.M;
+  const bool gave_up = (call_flags & PF_FALLBACK) != 0u;
+  const uint32_t a = run.a, m = gave_up ? 0u : pi.m, m_plus = pi.m_plus, M = pi.M;  // (one test for "nothing to do here")
   PairSum sm;
   sm.n_pass = sm.n_kept = 0;
   sm.minmem = NONE;
   sm.base = 0;
   if (m == 0) {
-    if (tid == 0) A.sum[rk] = sm;
+    if (tid == 0 && !gave_up) A.sum[rk] = sm;
     return;
   }
   // ---- the chains that pass the span / identity filter, ranked in position order ('+' chains first); the kept '+' chains
@@ -2102,25 +2105,52 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
   // rank in its chunk plus the passing chains of the chunks before: no flags to read, no scan over the positions, no record to
   // fetch.  A pair's chunks tile its positions in order, '+' first, in a stretch of the list that follows from its place.
   const uint32_t slot0 = A.chunks ? a / PAIR_CELL + 2u * rk : 0u;
-  const bool ranked = A.chunks && slot0 < A.cap_chunks && (A.chunks[slot0].pad & CHUNK_RANKED) != 0u;
-  if (ranked) {
-    __shared__ uint32_t rk_beg[RANKED_MAX_CHUNKS], rk_base[RANKED_MAX_CHUNKS + 1], rk_n[3];
-    if (A.ranked_stat && tid == 0) {
-      atomicAdd(&A.ranked_stat[0], 1ull);
-      atomicAdd(&A.ranked_stat[1], (unsigned long long)run.n);
-    }
-    if (tid < 64) {  // the chunk stretch: begins, and the exclusive prefix of the counts
-      uint32_t lim = run.n / PAIR_CELL + 2u;  // (the next pair's stretch begins at least this far on)
+  __shared__ uint32_t rk_beg[RANKED_MAX_CHUNKS], rk_base[RANKED_MAX_CHUNKS + 1], rk_n[3];
+  // ---- requested here, used further down (calls with the form on): none of these loads depends on anything the kernel computes
+  // beyond a, m, m_plus and M, so they are under way while the first wavefront stages the chunk stretch.  Every index is clamped
+  // to the pair's own stretch [a, a + M) and to its cap_chunks slots.
+  // The first wavefront: the descriptors of the chunk stretch and the labelling's counts together (a count is masked by its
+  // descriptor afterwards); lane 0's descriptor is the pair's first chunk and carries the mark.
+  // The loads are issued without branches around them (a position or a slot out of range is clamped to the first one and its
+  // value dropped), so the waits further down are for exactly the loads they need and not for whatever might be outstanding.
+  uint32_t lim = 0, cnt0 = 0, nck = 0;
+  SpecBlock d0;
+  d0.ue = d0.bb = d0.be = d0.pad = 0u;
+  uint32_t hd_nx[US];
+#pragma unroll
+  for (int u = 0; u < US; ++u) hd_nx[u] = NONE;
+  if (A.chunks) {
+    if (tid < 64 && slot0 < A.cap_chunks) {
+      lim = run.n / PAIR_CELL + 2u;  // (the next pair's stretch begins at least this far on)
       lim = lim < RANKED_MAX_CHUNKS ? lim : RANKED_MAX_CHUNKS;
       lim = lim < A.cap_chunks - slot0 ? lim : A.cap_chunks - slot0;
-      uint32_t carry = 0, nck = 0, kp = 0;
-      for (uint32_t j0 = 0; j0 < lim; j0 += 64) {
+      const uint32_t j = (uint32_t)tid < lim ? (uint32_t)tid : 0u;
+      d0 = A.chunks[slot0 + j];
+      cnt0 = A.chunk_pass[slot0 + j];  // (a lane at or beyond lim holds slot 0's words: dropped where they are used)
+    }
+    // Every thread: its first round of the anchors loop
+#pragma unroll
+    for (int u = 0; u < US; ++u) {
+      const uint32_t p = (uint32_t)u * NT + (uint32_t)tid;
+      hd_nx[u] = A.hd[a + (p < m ? p : 0u)];
+    }
+    if (tid < 64) {  // the chunk stretch: begins, and the exclusive prefix of the counts
+      const bool mark = (__shfl(d0.pad, 0, 64) & CHUNK_RANKED) != 0u;
+      uint32_t carry = 0, nc = 0, kp = 0;
+      for (uint32_t j0 = 0; mark && j0 < lim; j0 += 64) {
         const uint32_t j = j0 + (uint32_t)tid;
-        SpecBlock d;
-        d.ue = d.bb = d.be = d.pad = 0u;
-        if (j < lim) d = A.chunks[slot0 + j];
-        const bool valid = d.be > d.bb;  // (the list is zeroed per call: the slots behind the pair's last chunk are empty)
-        const uint32_t cnt = valid ? A.chunk_pass[slot0 + j] : 0u;
+        SpecBlock d = d0;
+        uint32_t cnt = cnt0;
+        if (j0) {
+          d.ue = d.bb = d.be = d.pad = 0u;
+          cnt = 0u;
+          if (j < lim) {
+            d = A.chunks[slot0 + j];
+            cnt = A.chunk_pass[slot0 + j];
+          }
+        }
+        const bool valid = j < lim && d.be > d.bb;  // (the list is zeroed per call: the slots behind the pair's last chunk are empty)
+        cnt = valid ? cnt : 0u;
         uint32_t inc = cnt;
 #pragma unroll
         for (int dd = 1; dd < 64; dd <<= 1) {
@@ -2132,20 +2162,28 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
           rk_base[j] = carry + inc - cnt;
         }
         kp += valid && (d.pad & 1u) == 0u ? cnt : 0u;
-        nck += (uint32_t)__popcll(__ballot(valid));
+        nc += (uint32_t)__popcll(__ballot(valid));
         carry += __shfl(inc, 63, 64);
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) kp += __shfl_xor(kp, o, 64);
       if (tid == 0) {
-        rk_base[nck] = carry;
-        rk_n[0] = nck;
+        rk_base[nc] = carry;
+        rk_n[0] = nc | (mark ? 0x80000000u : 0u);  // (the mark goes to the other wavefronts with the count: at most 128 chunks)
         rk_n[1] = kp;
         rk_n[2] = carry;
       }
     }
-    __syncthreads();
-    const uint32_t nck = rk_n[0];
+    lds_barrier();  // (LDS only: what was requested above stays in flight)
+    nck = rk_n[0];
+  }
+  const bool ranked = (nck >> 31) != 0u;  // (the mark itself, not what the stretch holds)
+  nck &= 0x7fffffffu;
+  if (ranked) {
+    if (A.ranked_stat && tid == 0) {
+      atomicAdd(&A.ranked_stat[0], 1ull);
+      atomicAdd(&A.ranked_stat[1], (unsigned long long)run.n);
+    }
     kP = rk_n[1];
     n_kept = rk_n[2];
     kM = n_kept - kP;
@@ -2159,19 +2197,27 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
     if (tid == 0) A.sum[rk] = sm;
     FT_STAMP(0);
     // ---- anchors: a member's chunk is the last one that begins at or before it.  A thread's positions only ever grow, so it
-    // follows the chunks with a cursor: the next chunk's begin and this one's base stay in registers between crossings
+    // follows the chunks with a cursor: the next chunk's begin and this one's base stay in registers between crossings.  The
+    // loop is rotated: round r + 1's hd values are requested before round r is turned into fin.  A whole round loads and stores
+    // without a branch, so the wait at its top is for the hd values alone and the round before's stores stay in flight; the
+    // pair's last, partial round tests its positions.
     uint32_t cj = 0, c_base = rk_base[0], c_next = nck > 1u ? rk_beg[1] : NONE;
-    for (uint32_t p0 = 0; p0 < m; p0 += NT * US) {
+    auto anchors_round = [&](const uint32_t p0, auto whole_c) {
+      constexpr bool WHOLE = decltype(whole_c)::value;
       uint32_t r[US];
 #pragma unroll
-      for (int u = 0; u < US; ++u) {
-        const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
-        r[u] = p < m ? A.hd[a + p] : NONE;
+      for (int u = 0; u < US; ++u) r[u] = hd_nx[u];
+      if (WHOLE) {  // (a partial round is the last one)
+#pragma unroll
+        for (int u = 0; u < US; ++u) {
+          const uint32_t p = p0 + NT * US + (uint32_t)u * NT + (uint32_t)tid;
+          hd_nx[u] = A.hd[a + (p < m ? p : 0u)];
+        }
       }
 #pragma unroll
       for (int u = 0; u < US; ++u) {
         const uint32_t p = p0 + (uint32_t)u * NT + (uint32_t)tid;
-        if (p >= m) continue;
+        if (!WHOLE && p >= m) continue;
         while (p >= c_next) {  // (p < m < NONE: ends at the last chunk)
           ++cj;
           c_base = rk_base[cj];
@@ -2184,36 +2230,54 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
         }
         A.fin[a + p] = f;
       }
-    }
+    };
+    uint32_t p0 = 0;
+    for (; p0 + NT * US <= m; p0 += NT * US) anchors_round(p0, std::true_type{});
+    if (p0 < m) anchors_round(p0, std::false_type{});
     for (uint32_t p = m + (uint32_t)tid; p < M; p += NT) A.fin[a + p] = 0u;
     // ---- the kept '+' chains, chunk after chunk, for the inversion capture: chain c of the pair is chain c - base of the last
-    // chunk whose base is at or below c.  More than KP of them go to lists in memory: q_start and q_end in place -- chain c
+    // chunk whose base is at or below c.  Up to KP of them go to LDS: the searches and the three gathers of two rounds of
+    // chains are requested together (one round ahead).  More than KP go to lists in memory: q_start and q_end in place -- chain c
     // comes from position (chunk begin + c - base) >= c, and a round's values are all loaded before the first is stored -- the
     // t_start values likewise to the head of the pair's stretch of HeadRec words, the running maxima behind them.
     if (!A.scaffolds_only && kP > 0 && M > m_plus) {
-      const bool in_lds = kP <= (uint32_t)KP;
-      uint32_t *const g_qs = A.f_qs + a, *const g_qe = A.f_qe + a, *const g_ts = A.rec_w + (size_t)8 * a;
-      for (uint32_t c0 = 0; c0 < kP; c0 += NT) {
-        const uint32_t c = c0 + (uint32_t)tid;
-        uint32_t v_qs = 0, v_qe = 0, v_ts = 0;
-        if (c < kP) {
-          uint32_t lo = 0, hi = nck;
-          while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (rk_base[mid] <= c) lo = mid; else hi = mid;
-          }
-          const uint32_t b = rk_beg[lo], i = c - rk_base[lo];
-          v_qs = A.f_qs[a + b + i];
-          v_qe = A.f_qe[a + b + i];
-          v_ts = A.rec_w[(size_t)8 * (a + b) + i];
+      auto triple_at = [&](uint32_t c, uint32_t& v_qs, uint32_t& v_qe, uint32_t& v_ts) {
+        uint32_t lo = 0, hi = nck;
+        while (hi - lo > 1u) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (rk_base[mid] <= c) lo = mid; else hi = mid;
         }
-        if (in_lds) {
-          if (c < kP) {
-            l_qs[c] = v_qs;
-            l_qe[c] = v_qe;
-            l_ts[c] = v_ts;
+        const uint32_t b = rk_beg[lo], i = c - rk_base[lo];
+        v_qs = A.f_qs[a + b + i];
+        v_qe = A.f_qe[a + b + i];
+        v_ts = A.rec_w[(size_t)8 * (a + b) + i];
+      };
+      if (kP <= (uint32_t)KP) {
+        constexpr int RT = 2;  // rounds of NT chains in flight: one round ahead
+        for (uint32_t c0 = 0; c0 < kP; c0 += RT * NT) {
+          uint32_t v_qs[RT], v_qe[RT], v_ts[RT];
+#pragma unroll
+          for (int k = 0; k < RT; ++k) {
+            const uint32_t c = c0 + (uint32_t)k * NT + (uint32_t)tid;
+            v_qs[k] = v_qe[k] = v_ts[k] = 0u;
+            if (c < kP) triple_at(c, v_qs[k], v_qe[k], v_ts[k]);
           }
-        } else {
+#pragma unroll
+          for (int k = 0; k < RT; ++k) {
+            const uint32_t c = c0 + (uint32_t)k * NT + (uint32_t)tid;
+            if (c < kP) {
+              l_qs[c] = v_qs[k];
+              l_qe[c] = v_qe[k];
+              l_ts[c] = v_ts[k];
+            }
+          }
+        }
+      } else {
+        uint32_t *const g_qs = A.f_qs + a, *const g_qe = A.f_qe + a, *const g_ts = A.rec_w + (size_t)8 * a;
+        for (uint32_t c0 = 0; c0 < kP; c0 += NT) {
+          const uint32_t c = c0 + (uint32_t)tid;
+          uint32_t v_qs = 0, v_qe = 0, v_ts = 0;
+          if (c < kP) triple_at(c, v_qs, v_qe, v_ts);
           __syncthreads();
           if (c < kP) {
             g_qs[c] = v_qs;
@@ -2310,12 +2374,42 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 1) void pair_finish_kernel(Pair
     const uint32_t* __restrict__ c_ts = in_lds ? l_ts : g_ts;
     const uint32_t* __restrict__ c_pm = in_lds ? l_pm : g_pm;
     const uint64_t gap = A.gap, max_dev = A.max_dev;
+    // The ranked body requests a position's record index, its coordinates and the labelling's word in hd -- which says whether
+    // the position is an anchor already, and depends on nothing this kernel writes -- one round ahead, without a branch around
+    // the requests (past the pair's last position they read its first one, and the values are dropped).  The first body loads
+    // where it uses, and tests the anchors' results, which the barrier above has made visible.
+    uint32_t n_iw = 0, n_qs = 0, n_qe = 0, n_ts = 0, n_te = 0, n_hd = NONE;
+    if (ranked) {
+      const uint32_t pc = m_plus + (uint32_t)tid < M ? m_plus + (uint32_t)tid : 0u;
+      n_iw = A.s_idx[a + pc];
+      n_qs = A.s_qs[a + pc];
+      n_qe = A.s_qe[a + pc];
+      n_ts = A.s_ts[a + pc];
+      n_te = A.s_te[a + pc];
+      n_hd = A.hd[a + (pc < m ? pc : 0u)];
+    }
     for (uint32_t p = m_plus + tid; p < M; p += NT) {
-      const uint32_t iw = A.s_idx[a + p];
-      if (p >= m && (iw >> 31) == 0) continue;  // an alive non-member on the '+' strand
+      uint32_t iw;
+      uint64_t qs, qe, ts, te;
+      if (ranked) {
+        iw = n_iw;
+        qs = n_qs, qe = n_qe, ts = n_ts, te = n_te;
+        const uint32_t hdw = n_hd, pn = p + NT < M ? p + NT : 0u;
+        n_iw = A.s_idx[a + pn];
+        n_qs = A.s_qs[a + pn];
+        n_qe = A.s_qe[a + pn];
+        n_ts = A.s_ts[a + pn];
+        n_te = A.s_te[a + pn];
+        n_hd = A.hd[a + (pn < m ? pn : 0u)];
+        if (p >= m && (iw >> 31) == 0) continue;  // an alive non-member on the '+' strand
+        if (p < m && hdw != NONE) continue;       // already an anchor
+      } else {
+        iw = A.s_idx[a + p];
+        if (p >= m && (iw >> 31) == 0) continue;  // an alive non-member on the '+' strand
+        qs = A.s_qs[a + p], qe = A.s_qe[a + p], ts = A.s_ts[a + p], te = A.s_te[a + p];
+        if (A.fin ? A.fin[a + p] != 0u : A.chain[iw & 0x7fffffffu] != 0u) continue;  // already an anchor
+      }
       const uint32_t i = iw & 0x7fffffffu;
-      const uint64_t qs = A.s_qs[a + p], qe = A.s_qe[a + p], ts = A.s_ts[a + p], te = A.s_te[a + p];
-      if (A.fin ? A.fin[a + p] != 0u : A.chain[i] != 0u) continue;  // already an anchor
       const uint64_t qc = (qs + qe) / 2, tc = (ts + te) / 2;
       const uint64_t lim = qe > ~0ull - gap ? ~0ull : qe + gap;  // chain.query_start.saturating_sub(gap) <= qe
       uint32_t l = 0, r = kP;  // first chain with q_start > lim
