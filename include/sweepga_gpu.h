@@ -2110,6 +2110,120 @@ int swg_paf_eqx_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, con
 /* The same as one malloc'd text (release with swg_free). */
 int swg_paf_eqx_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_eqx_options* opts,
                      swg_eqx_counts* counts, char** text, uint64_t* len);
+
+/* ---- alignment blocks with their gapped bases: the two rows of every block, as MAF reads them (no reference counterpart;
+ * DESIGN.md section 37) ----
+ * The CIGAR set, the walk offsets x / y and the entry states are those of the base-exact lift; sequence presence and the bounds
+ * test are those of the variants; USABLE is that of the resolved CIGARs above, and the first failing test counts as there:
+ * cigar_bad, empty, no_sequence, out_of_sequence.  Integers and bytes only.
+ * ALIGNMENT COLUMNS: an op of length l gives l columns under M, =, X, I, D or N and none under S, H, P.  The target row of a column
+ * holds the target byte under M = X D N and '-' under I; the query row holds the query byte under M = X I and '-' under D and N.
+ * BYTES are copied as read (case and IUPAC codes kept, no norm): the target byte is T[t_start + y]; the query byte at walk offset x
+ * is Q[q_start + x] on '+' and comp_raw(Q[q_end - 1 - x]) on '-'.  comp_raw swaps A-T, C-G, R-Y, K-M, B-V, D-H, maps U to A, the
+ * same in lower case, and leaves every other byte (S, W, N, '-', '*', ...) unchanged: the table SWG_MAF_COMP_RAW below.
+ * BREAKERS AND BLOCKS: with split_gap = g > 0 an I, D or N op with l >= g is a BREAKER; with g = 0 there is none.  The breakers
+ * taken out of a usable entry, every maximal run of the remaining consecutive ops is a CANDIDATE; one with an aligned column (an M,
+ * = or X op of length > 0) is a BLOCK, the others count as gap_only.  Zero-length ops, S, H and P belong to the run they stand in
+ * and give no columns.  A block keeps its leading and trailing gap columns (no trimming).  Bases under breakers appear in no block
+ * and are summed in skipped_t / skipped_q.  The bases of a gap_only candidate (an I op shorter than g between two breakers, as in
+ * 3D1I3D with g = 3) appear in no block and in NEITHER skipped sum: per entry, the blocks' bases plus skipped_* equal the record's
+ * lengths only when gap_only counts none of its candidates.
+ * BLOCK FIELDS, with x0, y0 the walk offsets at the block's first op, q_bases / t_bases its advances, aligned its aligned columns:
+ * columns = q_bases + t_bases - aligned; the target interval is [t_start + y0, + t_bases); the query interval on the forward strand
+ * is [q_start + x0, + q_bases) on '+' and [q_end - x0 - q_bases, + q_bases) on '-'.  op_first / op_end count from the entry's first
+ * op.  One swg_maf_block per block, in (entry, op) order.
+ * TEXT: per block the target row (columns bytes), then the query row (columns bytes); the blocks lie end to end in block order,
+ * without separators; text_first runs over them in 64 bits.
+ * Capacity protocol of swg_eqx_records: blocks is written when n_blocks <= block_capacity, text when text_bytes <= text_capacity
+ * (each only when non-NULL; without a text pointer the text kernel does not run); the counts whenever the call succeeds.
+ * Refusals: those of swg_eqx_records for the set, the columns, the sequences and the offsets (SWG_ERR_INVALID); 2^32 bytes of CIGAR
+ * text or 2^32 alignment columns (of all candidates) or more in one call: SWG_ERR_RANGE (no range loop is built).  k == 0 needs no
+ * device.  Scratch from the arena: the build's plus, per op, 8 + 8 + 1 bytes (the scans of columns and breakers, the start flag);
+ * per entry 1; per candidate 4 + 64 + 40 + 1; per block 4 + 64 + 40 + 8; the text; the host seam stages as swg_eqx_records. */
+#define SWG_MAF_MINUS 1u       /* swg_maf_block.flags bit 0: the record's strand is '-' */
+#define SWG_MAF_TEXT_TILE 4096u /* output bytes per work-group of the text kernel */
+#define SWG_MAF_COMP_RAW                                                                                                            \
+  {0,   1,   2,   3,   4,   5,   6,   7,   8,   9,   10,  11,  12,  13,  14,  15,  16,  17,  18,  19,  20,  21,  22,  23,  24,  25,   \
+   26,  27,  28,  29,  30,  31,  32,  33,  34,  35,  36,  37,  38,  39,  40,  41,  42,  43,  44,  45,  46,  47,  48,  49,  50,  51,   \
+   52,  53,  54,  55,  56,  57,  58,  59,  60,  61,  62,  63,  64,  'T', 'V', 'G', 'H', 69,  70,  'C', 'D', 73,  74,  'M', 76,  'K',  \
+   78,  79,  80,  81,  'Y', 83,  'A', 'A', 'B', 87,  88,  'R', 90,  91,  92,  93,  94,  95,  96,  't', 'v', 'g', 'h', 101, 102, 'c',  \
+   'd', 105, 106, 'm', 108, 'k', 110, 111, 112, 113, 'y', 115, 'a', 'a', 'b', 119, 120, 'r', 122, 123, 124, 125, 126, 127, 128, 129,  \
+   130, 131, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149, 150, 151, 152, 153, 154, 155,  \
+   156, 157, 158, 159, 160, 161, 162, 163, 164, 165, 166, 167, 168, 169, 170, 171, 172, 173, 174, 175, 176, 177, 178, 179, 180, 181,  \
+   182, 183, 184, 185, 186, 187, 188, 189, 190, 191, 192, 193, 194, 195, 196, 197, 198, 199, 200, 201, 202, 203, 204, 205, 206, 207,  \
+   208, 209, 210, 211, 212, 213, 214, 215, 216, 217, 218, 219, 220, 221, 222, 223, 224, 225, 226, 227, 228, 229, 230, 231, 232, 233,  \
+   234, 235, 236, 237, 238, 239, 240, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250, 251, 252, 253, 254, 255}
+typedef struct swg_maf_block {
+  uint32_t record, entry;     /* the record, and its entry's place in the set */
+  uint32_t op_first, op_end;  /* the block's ops, counted from the entry's first op */
+  uint32_t t_start, t_bases;
+  uint32_t q_start, q_bases;  /* on the forward strand */
+  uint32_t aligned, columns;
+  uint32_t flags, walk_x;     /* SWG_MAF_MINUS; x0 */
+  uint64_t text_first;        /* into text: the target row, then the query row */
+  uint64_t reserved;          /* 0 */
+} swg_maf_block; /* 64 bytes, no implicit padding */
+typedef struct swg_maf_request {
+  uint32_t set;            /* in: SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t split_gap;      /* in: g; 0 = no breakers */
+  uint64_t block_capacity; /* in: blocks `blocks` can hold */
+  swg_maf_block* blocks;   /* in: caller-owned or NULL; written only when n_blocks <= block_capacity */
+  uint64_t text_capacity;
+  char* text;              /* written only when text_bytes <= text_capacity */
+  uint64_t ops;            /* out: ops parsed over the whole set */
+  uint64_t cigar_bad;      /* out: entries with a state bit of 1 .. 8 */
+  uint64_t empty;          /* out: entries of state 16 */
+  uint64_t usable, no_sequence, out_of_sequence;
+  uint64_t n_blocks, gap_only; /* out: candidates with and without an aligned column */
+  uint64_t breakers;           /* out: breaker ops of usable entries */
+  uint64_t skipped_t, skipped_q; /* out: bases under them */
+  uint64_t columns, aligned;   /* out: over the blocks */
+  uint64_t text_bytes;         /* out: 2 * columns */
+} swg_maf_request; /* 152 bytes, no implicit padding */
+/* Everything on the host. */
+int swg_maf_records(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                    swg_maf_request* req);
+/* Columns, strand, status, the three arrays of the set, seqs->offset and seqs->bases in device memory of ctx's GPU; the two set
+ * structures, the request and its arrays on the host. */
+int swg_maf_records_device(swg_ctx* ctx, const swg_records* rec, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                           swg_maf_request* req);
+/* --maf: the blocks of the records of `set` of an open PAF as MAF.  `##maf version=1\n`, then per block, in (record, block) order,
+ *   a score=<aligned>
+ *   s <tname> <t_start> <t_bases> + <tlen> <target row>
+ *   s <qname> <qs> <q_bases> <+|-> <qlen> <query row>
+ *   <empty line>
+ * with single spaces; qs = q_start on '+' and qlen - q_start - q_bases on '-' (MAF's reverse-strand coordinate); the names are the
+ * handle's, the lengths columns 2 and 7 of the record's own line.  score is the block's aligned columns: no bases are compared.  A
+ * record of the set that is not usable writes nothing and is counted.  Sequence names are matched to the FASTA records as
+ * swg_paf_vcf_write does it (length_mismatch included); the bases go to the device once per call; the entry is the LAST cg:Z: of
+ * the line; batches come from swg_paf_ucsc_chain_write's planner over the cost text length + (q_end - q_start) + (t_end - t_start),
+ * which bounds a usable entry's alignment columns and, at 2 bytes per column, its output: one device pass per batch with that bound
+ * as the text capacity.  The file is the same bytes for every batch_bytes.  A set without records gives the header line alone and
+ * needs no device (ctx may be NULL).  Refusals, all before a file is opened: set > 1, reserved != 0, SWG_IV_KEPT without status, a
+ * NULL fasta or opts: SWG_ERR_INVALID; a handle whose columns are rebased: SWG_ERR_UNSUPPORTED.  counts may be NULL.  Errors:
+ * swg_alnstats_last_error(). */
+typedef struct swg_maf_options {
+  uint32_t set;         /* SWG_IV_ALL or SWG_IV_KEPT */
+  uint32_t split_gap;   /* g; 0 = one block per record */
+  uint64_t batch_bytes; /* cost per device call; 0 = a default from the device's memory */
+  uint64_t reserved;    /* 0 */
+} swg_maf_options; /* 24 bytes */
+typedef struct swg_maf_counts {
+  uint64_t records;  /* records of the set */
+  uint64_t usable;   /* entries walked */
+  uint64_t bad;      /* entries with a state bit of 1 .. 8 */
+  uint64_t untagged; /* records without a cg:Z: tag */
+  uint64_t no_sequence, out_of_sequence; /* entries */
+  uint64_t length_mismatch;              /* sequences */
+  uint64_t blocks, gap_only, breakers, skipped_t, skipped_q, columns, aligned;
+  uint64_t file_bytes; /* bytes written */
+  uint64_t batches;    /* device calls */
+} swg_maf_counts; /* 128 bytes */
+int swg_paf_maf_write(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_maf_options* opts,
+                      const char* out_path, swg_maf_counts* counts);
+/* The same as one malloc'd text (release with swg_free). */
+int swg_paf_maf_text(swg_ctx* ctx, const swg_paf* p, const uint8_t* status, const swg_fasta* fasta, const swg_maf_options* opts,
+                     swg_maf_counts* counts, char** text, uint64_t* len);
 /* Per contig, the bottom-s MULTISET of min(SipHash-1-3(le64(k) || window), SipHash-1-3(le64(k) || revcomp upper-cased))
  * over the windows of k bytes all in ACGTacgt, ascending (KmerSketch::from_sequence, mash.rs:78-131).  Contig i =
  * seq[offsets[i], offsets[i + 1]); counts_out[n_seq]; minimizers_out[n_seq * s], row i holds counts_out[i] values.  The

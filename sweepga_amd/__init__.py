@@ -29,6 +29,7 @@ from .diffs import Diffs, DiffsResult, diff_records, diff_records_device  # noqa
 from .divergence import Divergence, DivergenceResult, divergence_records, divergence_records_device  # noqa: F401  (its ROW_DTYPE / SEQ_DTYPE: sweepga_amd.divergence)
 from .variants import VARIANT_DTYPE, Variants, VariantsResult, variant_records, variant_records_device  # noqa: F401  (its PAIR_DTYPE: sweepga_amd.variants)
 from .eqx import EQX_ENTRY_DTYPE, Eqx, EqxResult, eqx_records, eqx_records_device  # noqa: F401
+from .maf import MAF_BLOCK_DTYPE, Maf, MafResult, maf_records, maf_records_device  # noqa: F401
 from .ani import (AniMethod, AniMethodKind, NSort, calculate_ani_stats, parse_ani_method,  # noqa: F401
                   parse_identity_value)
 

@@ -54,7 +54,8 @@ SYMBOLS = ["swg_abi_version", "swg_create", "swg_destroy", "swg_last_error", "sw
            "swg_windows_records", "swg_windows_records_device", "swg_paf_windows",
            "swg_divergence_records", "swg_divergence_records_device", "swg_paf_divergence",
            "swg_variant_records", "swg_variant_records_device", "swg_paf_vcf_write", "swg_paf_vcf_text",
-           "swg_eqx_records", "swg_eqx_records_device", "swg_paf_eqx_write", "swg_paf_eqx_text"]
+           "swg_eqx_records", "swg_eqx_records_device", "swg_paf_eqx_write", "swg_paf_eqx_text",
+           "swg_maf_records", "swg_maf_records_device", "swg_paf_maf_write", "swg_paf_maf_text"]
 
 
 class SwgError(RuntimeError):
@@ -445,6 +446,28 @@ class SwgEqxCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in EQX_COUNTS]
 
 
+MAF_FIELDS = ("ops", "cigar_bad", "empty", "usable", "no_sequence", "out_of_sequence", "n_blocks", "gap_only", "breakers", "skipped_t", "skipped_q",
+              "columns", "aligned", "text_bytes")
+
+
+class SwgMafRequest(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("split_gap", C.c_uint32), ("block_capacity", C.c_uint64), ("blocks", C.c_void_p), ("text_capacity", C.c_uint64),
+                ("text", C.c_void_p)]
+    _fields_ += [(k, C.c_uint64) for k in MAF_FIELDS]
+
+
+class SwgMafOptions(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("split_gap", C.c_uint32), ("batch_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+MAF_COUNTS = ("records", "usable", "bad", "untagged", "no_sequence", "out_of_sequence", "length_mismatch", "blocks", "gap_only", "breakers", "skipped_t",
+              "skipped_q", "columns", "aligned", "file_bytes", "batches")
+
+
+class SwgMafCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in MAF_COUNTS]
+
+
 class SwgClosureRow(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("region", "seq", "start", "end", "hop", "reserved")]
 
@@ -766,6 +789,15 @@ def load():
     lib.swg_paf_eqx_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgEqxOptions), C.c_char_p, C.POINTER(SwgEqxCounts)]
     lib.swg_paf_eqx_text.restype = C.c_int
     lib.swg_paf_eqx_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgEqxOptions), C.POINTER(SwgEqxCounts), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_uint64)]
+    for name in ("swg_maf_records", "swg_maf_records_device"):
+        f = getattr(lib, name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SwgRecords), C.c_void_p, C.POINTER(SwgCigarSet), C.POINTER(SwgSeqSet), C.POINTER(SwgMafRequest)]
+    lib.swg_paf_maf_write.restype = C.c_int
+    lib.swg_paf_maf_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgMafOptions), C.c_char_p, C.POINTER(SwgMafCounts)]
+    lib.swg_paf_maf_text.restype = C.c_int
+    lib.swg_paf_maf_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SwgMafOptions), C.POINTER(SwgMafCounts), C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_uint64)]
     for name in ("swg_divergence_records", "swg_divergence_records_device"):
         f = getattr(lib, name)

@@ -18,6 +18,7 @@ SOURCES = ["swg_context.hip", "swg_sort.hip", "swg_sweep.hip", "swg_filter.hip",
            "swg_divergence.hip", os.path.join("host", "divergence_text.cpp"),
            "swg_variants.hip", os.path.join("host", "variants_text.cpp"),
            "swg_eqx.hip", os.path.join("host", "eqx_text.cpp"),
+           "swg_maf.hip", os.path.join("host", "maf_text.cpp"),
            "swg_mosaic.hip", os.path.join("host", "mosaic_text.cpp"),
            "swg_gaps.hip", os.path.join("host", "gaps_text.cpp"),
            "swg_place.hip", os.path.join("host", "place_text.cpp"),

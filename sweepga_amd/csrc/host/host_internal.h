@@ -190,6 +190,14 @@ int swg_eqx_run(swg_ctx* ctx, const swg_records* rec, int where, const uint8_t* 
 // value of its last cg:Z: tag (cg, cg_len: where swg_cigar_tag_find found it) = text[0 .. text_len); a '\n' ends it.
 void swg_eqx_line_text(std::string& o, const char* line, uint64_t len, const char* cg, uint64_t cg_len, uint64_t matches, uint64_t block,
                        const char* text, uint64_t text_len);
+// ---- alignment blocks as MAF (swg_maf.hip: kernels and record seams; maf_text.cpp: the two PAF seams) ----
+// where: as swg_variant_run
+int swg_maf_run(swg_ctx* ctx, const swg_records* rec, int where, const uint8_t* status, const swg_cigar_set* cigars, const swg_seq_set* seqs,
+                swg_maf_request* req);
+// One block as MAF: `a score=<aligned>`, the two `s` lines and an empty line.  line: the record's own line (its columns 2 and 7 are
+// the lengths); rows: the block's target row, then its query row, b.columns bytes each.
+void swg_maf_block_text(std::string& o, const char* t_name, const char* q_name, const char* line, uint64_t line_len, const swg_maf_block& b,
+                        const char* rows);
 // ---- differences (swg_diffs.hip: kernels and record seams; diffs_text.cpp: the two PAF seams) ----
 int swg_diff_run(swg_ctx* ctx, const swg_records* rec, bool on_device, const uint32_t* seq_genome, uint32_t n_genome, const uint8_t* status,
                  const swg_cigar_set* cigars, swg_diff_request* req);

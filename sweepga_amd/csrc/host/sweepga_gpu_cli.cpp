@@ -467,6 +467,24 @@ void write_vcf(const std::string& vcf_path, const std::string& summary_path, swg
                  (unsigned long long)c.bad, (unsigned long long)c.untagged);
 }
 
+// --maf: the MAF of swg_paf_maf_write -- the blocks of the set's records, the two rows of each gathered through the CIGAR on the device.
+// What it met goes to standard error in one line.
+void write_maf(const std::string& path, swg_ctx* ctx, const swg_paf* paf, const uint8_t* status, const swg_fasta* fasta, uint32_t set, uint32_t split_gap,
+               uint64_t batch, bool quiet) {
+  swg_maf_options o{};
+  o.set = set, o.split_gap = split_gap, o.batch_bytes = batch;
+  swg_maf_counts c;
+  if (swg_paf_maf_write(ctx, paf, status, fasta, &o, path.c_str(), &c) != SWG_OK) die(3, std::string("--maf: ") + swg_alnstats_last_error());
+  if (quiet) return;
+  std::fprintf(stderr, "[sweepga-gpu] --maf: %llu blocks of %llu records (%llu usable): %llu columns, %llu aligned; %llu breakers over %llu target and %llu "
+               "query bases, %llu runs of gaps only; %llu entries without sequence, %llu out of sequence, %llu bad, %llu without a cg:Z: tag, %llu "
+               "sequences of another length\n",
+               (unsigned long long)c.blocks, (unsigned long long)c.records, (unsigned long long)c.usable, (unsigned long long)c.columns,
+               (unsigned long long)c.aligned, (unsigned long long)c.breakers, (unsigned long long)c.skipped_t, (unsigned long long)c.skipped_q,
+               (unsigned long long)c.gap_only, (unsigned long long)c.no_sequence, (unsigned long long)c.out_of_sequence, (unsigned long long)c.bad,
+               (unsigned long long)c.untagged, (unsigned long long)c.length_mismatch);
+}
+
 // --eqx: the PAF of swg_paf_eqx_write -- the set's records with every cg:Z: resolved to =/X against the FASTA records, columns 10 and 11
 // exact (built on the device).  What it met goes to standard error in one line; eq_wrong and x_wrong, when not zero, say that PAF and
 // FASTA do not belong together.
@@ -604,6 +622,11 @@ int main(int argc, char** argv) {
   uint32_t eqx_set = SWG_IV_KEPT, eqx_unresolved = SWG_EQX_KEEP;
   uint64_t eqx_batch = 0;  // --eqx-batch: 0 = the library's default
   bool eqx_flag = false;   // (a sub-option of --eqx was given)
+  std::string maf_path;                     // --maf: empty = not given
+  std::vector<std::string> maf_fasta_paths;  // --maf-fasta, once per file
+  uint32_t maf_set = SWG_IV_KEPT;
+  uint64_t maf_split_gap = 0, maf_batch = 0;  // --maf-split-gap: 0 = one block per record; --maf-batch: 0 = the library's default
+  bool maf_flag = false;                      // (a sub-option of --maf was given)
   std::string divergence_path, divergence_summary_path, divergence_genome;  // --divergence, --divergence-summary: empty = no file; -genome: empty = any
   uint32_t divergence_set = SWG_IV_KEPT, divergence_axis = 0;
   uint64_t divergence_window = 10000, divergence_batch = 0;  // --divergence-window; --divergence-batch: 0 = the library's default
@@ -765,6 +788,31 @@ int main(int argc, char** argv) {
     else if (a == "--vcf-batch") {
       if (!parse_metric_number(value(), &vcf_batch) || vcf_batch == 0) die(2, "invalid value for --vcf-batch: 1 or more bytes");
       vcf_flag = true;
+    }
+    else if (a == "--maf") {
+      maf_path = value();
+      if (maf_path.empty()) die(2, "empty value for --maf");
+      if (maf_path == "-") die(2, "--maf needs a file: the MAF is not a standard error report");
+    }
+    else if (a == "--maf-fasta") {
+      maf_fasta_paths.push_back(value());
+      if (maf_fasta_paths.back().empty() || maf_fasta_paths.back() == "-") die(2, "--maf-fasta needs a file");
+      maf_flag = true;
+    }
+    else if (a == "--maf-set") {
+      const std::string v = value();
+      if (v == "kept") maf_set = SWG_IV_KEPT;
+      else if (v == "all") maf_set = SWG_IV_ALL;
+      else die(2, "invalid value for --maf-set: kept or all");
+      maf_flag = true;
+    }
+    else if (a == "--maf-split-gap") {
+      if (!parse_metric_number(value(), &maf_split_gap) || maf_split_gap >> 32) die(2, "invalid value for --maf-split-gap: 0 .. 4294967295 bases");
+      maf_flag = true;
+    }
+    else if (a == "--maf-batch") {
+      if (!parse_metric_number(value(), &maf_batch) || maf_batch == 0) die(2, "invalid value for --maf-batch: 1 or more bytes");
+      maf_flag = true;
     }
     else if (a == "--eqx") {
       eqx_path = value();
@@ -992,6 +1040,7 @@ int main(int argc, char** argv) {
                 "         [--vcf FILE] [--vcf-summary FILE] --vcf-fasta FASTA [--vcf-fasta FASTA ...] [--vcf-ref GENOME] [--vcf-query GENOME]\n"
                 "         [--vcf-set kept|all] [--vcf-max-indel N] [--vcf-batch BYTES]\n"
                 "         [--eqx FILE] --eqx-fasta FASTA [--eqx-fasta FASTA ...] [--eqx-set kept|all] [--eqx-unresolved keep|drop] [--eqx-batch BYTES]\n"
+                "         [--maf FILE] --maf-fasta FASTA [--maf-fasta FASTA ...] [--maf-set kept|all] [--maf-split-gap N] [--maf-batch BYTES]\n"
                 "         [--divergence FILE|-] [--divergence-summary FILE|-] [--divergence-window N] [--divergence-axis query|target]\n"
                 "         [--divergence-genome NAME] [--divergence-set kept|all] [--divergence-batch BYTES]\n"
                 "         [--lift-hops N] [--lift-closure FILE|-] [--lift-closure-summary FILE|-] [--lift-min-length N]\n"
@@ -1110,6 +1159,14 @@ int main(int argc, char** argv) {
                 "  --eqx-set kept|all              the records that are written (default kept)\n"
                 "  --eqx-unresolved keep|drop      a record that cannot be resolved is copied unchanged, or left out (default keep)\n"
                 "  --eqx-batch BYTES               CIGAR text and columns per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
+                "  --maf FILE          write the records as MAF: per block `a score=`, the target's and the query's `s` line with their gapped bases (as\n"
+                "                      the FASTA has them; the query reverse-complemented on '-') and an empty line; score is the block's aligned columns,\n"
+                "                      no bases are compared\n"
+                "  --maf-fasta FASTA               the sequences, matched to the PAF's names by exact name; once per file (needed)\n"
+                "  --maf-set kept|all              the records that are written (default kept)\n"
+                "  --maf-split-gap N               an I, D or N op of N bases or more ends a block and its bases are left out; k/m suffixes (default 0: one\n"
+                "                                  block per record)\n"
+                "  --maf-batch BYTES               CIGAR text and bases per device call; k/m/g suffixes (default: from the device's memory; for tests)\n"
                 "  --divergence FILE   after the filter: one line per window of every sequence that carries an inter-genome mapping of the set --\n"
                 "                      `sequence start end n aligned matches mismatches m_columns unaligned inserted mismatch_runs indels`, exact\n"
                 "                      from the cg:Z: CIGARs (built on the device), empty windows included; integers only: column identity is\n"
@@ -1190,6 +1247,15 @@ int main(int argc, char** argv) {
     std::vector<const char*> paths;
     for (const std::string& f : eqx_fasta_paths) paths.push_back(f.c_str());
     if (swg_fasta_open(paths.data(), (int)paths.size(), threads, &eqx_fasta) != SWG_OK) die(2, std::string("--eqx-fasta: ") + swg_fasta_last_error());
+  }
+  const bool maf = !maf_path.empty();
+  if (!maf && maf_flag) die(2, "--maf-fasta, --maf-set, --maf-split-gap and --maf-batch need --maf");
+  if (maf && maf_fasta_paths.empty()) die(2, "--maf needs --maf-fasta: the bases are not in a PAF");
+  swg_fasta* maf_fasta = nullptr;
+  if (maf) {  // read now: an unreadable FASTA is a usage error, found before anything is begun
+    std::vector<const char*> paths;
+    for (const std::string& f : maf_fasta_paths) paths.push_back(f.c_str());
+    if (swg_fasta_open(paths.data(), (int)paths.size(), threads, &maf_fasta) != SWG_OK) die(2, std::string("--maf-fasta: ") + swg_fasta_last_error());
   }
   const bool divergence = !divergence_path.empty() || !divergence_summary_path.empty();
   if (!divergence && divergence_flag)
@@ -1285,7 +1351,7 @@ int main(int argc, char** argv) {
   double create_ms = 0.0, warm_ms = 0.0;
   std::thread gpu_init([&] {
     if (no_filter && breadth_path.empty() && components_path.empty() && lost_path.empty() && covered_path.empty() && sharing_path.empty() &&
-        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence && !vcf && !eqx)
+        sharing_bed_path.empty() && dotplot_path.empty() && !lift && !mosaic && !place && !windows && !ucsc && !diffs && !divergence && !vcf && !eqx && !maf)
       return;  // (--no-filter opens a device only for these reports)
     for (int d : devices) {
       if (no_filter && !ctxs.empty()) break;  // (... and the report runs on the first context)
@@ -1514,6 +1580,13 @@ int main(int argc, char** argv) {
       write_eqx(eqx_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), eqx_fasta, eqx_set, eqx_unresolved, eqx_batch, quiet);
       swg_fasta_close(eqx_fasta);
     }
+    if (maf) {  // nothing is dropped: kept = all
+      std::fflush(out);
+      if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
+      const std::vector<uint8_t> every(n ? n : 1, 1);
+      write_maf(maf_path, ctxs.empty() ? nullptr : ctxs[0], paf, every.data(), maf_fasta, maf_set, (uint32_t)maf_split_gap, maf_batch, quiet);
+      swg_fasta_close(maf_fasta);
+    }
     if (divergence) {  // nothing is dropped: kept = all
       std::fflush(out);
       if (n && init_rc != SWG_OK) die(3, "no usable GPU: " + init_err);
@@ -1724,6 +1797,13 @@ int main(int argc, char** argv) {
     write_eqx(eqx_path, ctx, paf, status.data(), eqx_fasta, eqx_set, eqx_unresolved, eqx_batch, quiet);
     swg_fasta_close(eqx_fasta);
     if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --eqx: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
+  }
+  // ---- --maf: likewise, the bases on the device once, one device pass per batch
+  if (maf) {
+    const auto tb = clk::now();
+    write_maf(maf_path, ctx, paf, status.data(), maf_fasta, maf_set, (uint32_t)maf_split_gap, maf_batch, quiet);
+    swg_fasta_close(maf_fasta);
+    if (!quiet) std::fprintf(stderr, "[sweepga-gpu] --maf: %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - tb).count());
   }
   // ---- --divergence / --divergence-summary: likewise, one device call per batch over all records
   if (divergence) {

@@ -43,6 +43,7 @@
 #include "swg_diffs_walk.h"
 #include "swg_diffs_letters.h"
 #include "swg_eqx_walk.h"
+#include "swg_seq_usable.h"
 #include "host/host_internal.h"
 
 namespace {
@@ -52,6 +53,7 @@ using swg_lift_ix::LiftCols;
 using namespace swg_cigar;
 using namespace swg_diffs;
 using namespace swg_eqx;
+using namespace swg_seq_usable;  // Seqs, count_votes, offsets_descend, usable_of, entry_at, load_quad
 
 static_assert(sizeof(swg_eqx_entry) == 64 && sizeof(swg_eqx_request) == 168 && sizeof(swg_eqx_options) == 24 && sizeof(swg_eqx_counts) == 128,
               "include/sweepga_gpu.h states these sizes");
@@ -64,17 +66,11 @@ constexpr int TTILE = (int)SWG_EQX_TEXT_TILE;
 static_assert(TB == 256 && CTILE % (4 * TB) == 0 && TTILE % 4 == 0, "whole rounds of the work-group per tile");
 static_assert(CTILE / TB * 64 < (1 << SUM_BITS), "a wavefront's columns of one tile fit a field of the packed sums");
 
-struct Seqs {  // device pointers
-  const uint64_t* offset;
-  const uint8_t* bases;
-  uint64_t n_bases;
-};
-
 unsigned grid_of(uint64_t items) { return (unsigned)((items + TB - 1) / TB); }
 
 __global__ __launch_bounds__(TB) void eqx_offsets_kernel(const uint64_t* __restrict__ offset, uint32_t n_seq, unsigned long long* __restrict__ scalars) {
   const uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-  if (s < n_seq && offset[s + 1] < offset[s]) atomicOr(&scalars[F_BAD_OFFSET], 1ull);
+  if (offsets_descend(offset, n_seq, s)) atomicOr(&scalars[F_BAD_OFFSET], 1ull);
 }
 
 __global__ __launch_bounds__(TB) void eqx_letters_kernel(CigarSet S, int aligned, uint8_t* __restrict__ kind, uint32_t* __restrict__ pos) {
@@ -90,29 +86,15 @@ __global__ __launch_bounds__(TB) void eqx_letters_kernel(CigarSet S, int aligned
   }
 }
 
-__device__ __forceinline__ void count_votes(bool vote, unsigned long long* slot) {
-  const uint64_t votes = __ballot(vote);
-  if ((threadIdx.x & 63) == 0 && votes) atomicAdd(slot, (unsigned long long)__popcll(votes));
-}
-
 __global__ __launch_bounds__(TB) void eqx_entries_kernel(CigarSet S, LiftCols c, uint32_t n_seq, uint32_t set, const uint64_t* __restrict__ seq_off,
                                                          uint8_t* __restrict__ usable, swg_eqx_entry* __restrict__ entries,
                                                          unsigned long long* __restrict__ scalars) {
   const uint64_t j = (uint64_t)blockIdx.x * TB + threadIdx.x;
   bool ok = false, empty = false, bad_id = false, no_seq = false, out_seq = false;
   if (j < S.k) {
-    const uint32_t rec = S.record[j], st = reinterpret_cast<const uint8_t*>(S.state)[j];
-    empty = st == ST_EMPTY;
-    if (set == SWG_IV_ALL || c.status[rec] != 0) {
-      const uint32_t q = c.id[0][rec], t = c.id[1][rec];
-      bad_id = q >= n_seq || t >= n_seq;
-      if (!bad_id && st == 0) {
-        const uint64_t q0 = seq_off[q], q1 = seq_off[q + 1], t0 = seq_off[t], t1 = seq_off[t + 1];
-        no_seq = !(q1 > q0 && t1 > t0);
-        out_seq = !no_seq && !(c.end[0][rec] <= q1 - q0 && c.end[1][rec] <= t1 - t0);
-        ok = !no_seq && !out_seq;
-      }
-    }
+    const uint32_t rec = S.record[j];
+    const Usable u = usable_of(S, c, n_seq, set, seq_off, j);
+    ok = u.ok, empty = u.empty, bad_id = u.bad_id, no_seq = u.no_seq, out_seq = u.out_seq;
     usable[j] = ok ? 1 : 0;
     uint4* o = reinterpret_cast<uint4*>(entries + j);  // 64 bytes: four 16-byte stores (arena blocks are 16-byte aligned)
     o[0] = make_uint4(rec, 0u, 0u, 0u);
@@ -125,16 +107,6 @@ __global__ __launch_bounds__(TB) void eqx_entries_kernel(CigarSet S, LiftCols c,
   if (__ballot(bad_id) && (threadIdx.x & 63) == 0) atomicOr(&scalars[F_BAD_ID], 1ull);
 }
 
-// the last entry j in [lo, hi] with op_first[j] <= r (op_first[lo] <= r): of several entries that begin at one op all but the last
-// are empty
-__device__ __forceinline__ uint32_t entry_at(const uint32_t* __restrict__ op_first, uint32_t lo, uint32_t hi, uint32_t r) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-    if (op_first[mid] <= r) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 // the last op r in [lo, hi] with C[r] <= s (C[lo] <= s, hi < ops, s < C[ops]): the op that column s belongs to
 __device__ __forceinline__ uint32_t op_at(const uint64_t* __restrict__ C, uint32_t lo, uint32_t hi, uint64_t s) {
   while (lo < hi) {
@@ -237,19 +209,6 @@ __device__ __forceinline__ ColOp locate(const CigarSet& S, const LiftCols& c, co
   o.q_at = o.minus ? q0 + c.end[0][rec] - 1 - x : q0 + c.start[0][rec] + x;
   return o;
 }
-// the four bytes at bases[at .. at + 4), all inside the bases, byte 0 in bits 0 .. 7: one aligned 32-bit load, or two and a shift
-// where both lie inside the bases, else four byte loads
-__device__ __forceinline__ uint32_t load_quad(const Seqs& seqs, uint64_t at) {
-  const uint8_t* p = seqs.bases + at;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const uint32_t sh = (uint32_t)(a & 3u);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a - sh);
-  if (sh == 0) return w[0];
-  if (reinterpret_cast<const uint8_t*>(w) >= seqs.bases && reinterpret_cast<const uint8_t*>(w + 2) <= seqs.bases + seqs.n_bases)
-    return (uint32_t)((((uint64_t)w[1] << 32) | w[0]) >> (8 * sh));
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
 struct Pending {  // the sums of the entry a lane's last columns lay in
   uint32_t e;
   ColumnSums s;
